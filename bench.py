@@ -12,10 +12,10 @@ HEADLINE call shape (`config.workload` says so): frames are submitted --views-pe
 time through rasterize_views -- the C ABI's gsr_forward_batch / gsr_backward_batch: every kernel covers all views of the
 submission, nothing on the host waits for the device inside a frame, gradients of the shared cloud are summed over the views on
 the device -- with --streams (default 1) submissions in flight on their own HIP streams.  K steps that are not a multiple of the
-batch end with a smaller batch.  The timed region is `--repeats` (default 5) blocks of exactly K steps, every block bracketed by
+batch end with a smaller batch.  The timed region is `--repeats` (default 1, with --full 5) blocks of exactly K steps, every block bracketed by
 barrier + synchronize; `value` / `ms_per_step` are the MEDIAN block (max over ranks per block), all blocks are listed.
 
-Beside the headline the line carries (rank 0, measured right after the timed region, never inside it):
+With --full, beside the headline the line carries (rank 0, measured right after the timed region, never inside it):
   kernels_ms / roofline -- a single-stream pass with hipEvents around every stage on the launch stream: the dominant kernel's
                   ALGORITHMIC bytes / its measured duration against the 8 TB/s HBM peak (and the ~6.3 TB/s a copy reaches), its
                   VALU issue rate, and -- only if profiles/pmc_traffic.json was taken on exactly this workload and call shape -- the
@@ -35,6 +35,17 @@ Beside the headline the line carries (rank 0, measured right after the timed reg
 
 `--gpus N` with N > 1 and no torch.distributed.run environment re-launches itself under torch.distributed.run with N ranks
 (one per GPU, RCCL); it refuses loudly when the box has fewer than N GPUs.
+
+A plain run does only what the headline needs: set-up, warm-up, ONE timed block of exactly K steps with nothing but the frames
+in it (no in-region events or clock probes), and a line with the headline fields (`metric`, `value`, `unit`, `ms_per_step`,
+`higher_is_better`, `dtype`, the call shape).  Everything else listed above -- the five timed blocks, the in-region instrumentation,
+kernels_ms / roofline, drop_in and its variants, forward_only, rgb_time_equiv, the gather anchor, cpu_baseline -- runs only with
+`--full`.  The untimed warm-up walks the timed block's own steps in pieces of two submissions per stream, so it costs about
+--warmup-seconds whatever K is.
+
+`--dump-outputs DIR` writes what the timed path handed its caller in its last step, as float32 .npy files (benchlib/outputs.py): the
+frame of the last step, its radii and the gradients of the last submission, a fixed seeded sample of the per-Gaussian rows.  The
+inputs are seeded, so two builds can be compared output for output with the same arguments.
 """
 import argparse
 import json
@@ -58,7 +69,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
-from benchlib import cpu_baseline as _cpu_baseline, dist as _dist, roofline as _roofline  # noqa: E402
+from benchlib import cpu_baseline as _cpu_baseline, dist as _dist, outputs as _outputs, roofline as _roofline  # noqa: E402
 from benchlib.roofline import HBM_ACHIEVABLE_GBS, HBM_PEAK_GBS, STAGE_KERNEL, VALU_PEAK_GWIPS, stage_kernel  # noqa: E402,F401
 from benchlib.timing import GC_RECOVER_S, union_ms  # noqa: E402,F401
 from benchlib.workload import CONFIGS, algorithmic_bytes, kernels_sha, view_of  # noqa: E402,F401
@@ -97,7 +108,13 @@ def main():
     ap.add_argument("--gather-probe", action="store_true", help=argparse.SUPPRESS)    # 1-rank RCCL anchor, run as a child under RANK=0 WORLD_SIZE=1
     ap.add_argument("--no-stage-events", action="store_true",
                     help="no per-stage hipEvents anywhere (for timeline traces: an event pair costs ~10 us of bubble per stage)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps each; the median block is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (five timed blocks with in-region events, per-stage kernel "
+                         "times and roofline, drop-in API figures, forward-only, rgb time, gather anchor, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed blocks of --steps steps each; the median block is reported (default: 1, with --full 5)")
     ap.add_argument("--cpu-frames", type=int, default=5, help="frames of the all-core CPU baseline (after 1 warm-up)")
     ap.add_argument("--no-cpu-1core", action="store_true", help="skip the 1-core CPU figure (about a minute of CPU time)")
     ap.add_argument("--streams", type=int, default=int(os.environ.get("GSR_BENCH_STREAMS", "0")),
@@ -110,6 +127,9 @@ def main():
                          "(frames then travel through host memory; not a performance mode)")
     ap.add_argument("--device-index", type=int, default=-1, help="GPU of this rank (default: LOCAL_RANK)")
     args = ap.parse_args()
+    if args.repeats is None:       # (the gather probe is a child process of a --full run)
+        args.repeats = 5 if (args.full or args.gather_probe) else 1
+    full = args.full
     cfg = CONFIGS[args.config]
     args.workload = args.workload or cfg["workload"]
     args.width = args.width or cfg["width"]
@@ -192,10 +212,18 @@ def main():
 
     # ---- instrumentation INSIDE the timed region: two hipEvents around every submission on the stream it runs on (GPU time of the
     # timed steps themselves, not of a pass taken afterwards) and one shader-clock probe per submission on a side stream (the
-    # clock the chip sustains under exactly this load).  Costs two event records and one 64-lane kernel per submission.
+    # clock the chip sustains under exactly this load).  Costs two event records and one 64-lane kernel per submission.  --full only.
     sub_events = []          # (tag, start event, end event)
     sub_tag = [None]         # None: not recording
-    probe = _native.ClockProbe(dev, capacity=1024)
+    probe = _native.ClockProbe(dev, capacity=1024) if full else None
+
+    # --dump-outputs: the submission that ends at global step dump_at[0] keeps what it handed its caller
+    dump_at = [None]
+    dumped = {}
+
+    def keep(i, n, imgs, radii, L):
+        if dump_at[0] == i + n:
+            dumped.update(frames=imgs, radii=radii, grads={k: t.grad for k, t in L.items() if t.grad is not None})
 
     def bracket(fn):
         if sub_tag[0] is None:
@@ -214,13 +242,15 @@ def main():
         v = view_of(i, rank, world, n_views, shard)
         L = leafsets[tslot]
         if with_grad:
-            img, _ = rasterizers[v](**L)
+            img, radii = rasterizers[v](**L)
             (img * G).sum().backward()
+            keep(i, 1, img.detach()[None], radii[None], L)
             for t in L.values():
                 t.grad = None
             return img.detach()
         with torch.no_grad():
-            img, _ = rasterizers[v](**L)
+            img, radii = rasterizers[v](**L)
+        keep(i, 1, img[None], radii[None], L)
         return img
 
     literal_mode = [False]
@@ -257,15 +287,17 @@ def main():
         L = leafsets[tslot]
         sts = [settings[view_of(i + k, rank, world, n_views, shard)] for k in range(n)]
         if with_grad:
-            imgs, _ = rasterize_views(L["means3D"], L["means2D"], L["opacities"], sts, shs=L["shs"], scales=L["scales"],
-                                      rotations=L["rotations"])
+            imgs, radii = rasterize_views(L["means3D"], L["means2D"], L["opacities"], sts, shs=L["shs"], scales=L["scales"],
+                                          rotations=L["rotations"])
             (imgs * G).sum().backward()
+            keep(i, n, imgs.detach(), radii, L)
             for t in L.values():
                 t.grad = None
             return imgs.detach()
         with torch.no_grad():
-            imgs, _ = rasterize_views(L["means3D"], L["means2D"], L["opacities"], sts, shs=L["shs"], scales=L["scales"],
-                                      rotations=L["rotations"])
+            imgs, radii = rasterize_views(L["means3D"], L["means2D"], L["opacities"], sts, shs=L["shs"], scales=L["scales"],
+                                          rotations=L["rotations"])
+        keep(i, n, imgs, radii, L)
         return imgs
 
     timing_gather = [False]
@@ -417,10 +449,24 @@ def main():
     # (3 frames per stream and 3 on the caller's stream) so that a small W does not put first-touch costs in the timing,
     # plus frames until --warmup-seconds have passed: the chip settles at the clock it sustains under this load
     warm = max(args.warmup, 3 * max(1, args.streams))
+    piece = VPC * max(1, args.streams) * 2
+    wpos = [0]
+
+    def warm_piece():
+        """The next untimed piece of the first timed block's own steps (same views, same batch shapes), `piece` steps at most: a
+        warm-up round costs milliseconds, not a block, whatever --steps is."""
+        n = min(piece, args.steps - wpos[0])
+        run_steps(warm + wpos[0], n)
+        wpos[0] = (wpos[0] + n) % args.steps
+        return n
+
     t_w = time.perf_counter()
-    run_steps(0, max(warm, VPC * max(1, args.streams) * 2), streams=1)      # primes the caller's stream and allocator pool
-    run_steps(0, max(warm, VPC * max(1, args.streams) * 2))
-    warm_steps = 2 * max(warm, VPC * max(1, args.streams) * 2)
+    run_steps(0, piece, streams=1)      # primes the caller's stream and allocator pool
+    run_steps(0, max(warm, piece))
+    warm_steps = piece + max(warm, piece)
+    if args.steps % VPC:                # the timed block's short last submission
+        run_steps(warm + args.steps - args.steps % VPC, args.steps % VPC)
+        warm_steps += args.steps % VPC
     torch.cuda.synchronize()
     more = torch.zeros(1, dtype=torch.int32)
     while True:
@@ -432,17 +478,17 @@ def main():
             more.copy_(mt)
         if not int(more[0]):
             break
-        run_steps(0, max(args.steps, VPC))
-        warm_steps += max(args.steps, VPC)
+        warm_steps += warm_piece()
         torch.cuda.synchronize()
     # first use of the in-region instrumentation happens HERE, not in the first timed block: the probe kernel's code object is
     # loaded on its first launch and torch grows its event pool (7 ms in the first block otherwise)
-    sub_tag[0] = "warm"
-    run_steps(0, max(args.steps, VPC))
-    sub_tag[0] = None
-    warm_steps += max(args.steps, VPC)
-    torch.cuda.synchronize()
-    sub_events.clear()
+    if full:
+        sub_tag[0] = "warm"
+        run_steps(0, max(args.steps, VPC))
+        sub_tag[0] = None
+        warm_steps += max(args.steps, VPC)
+        torch.cuda.synchronize()
+        sub_events.clear()
     warm_seconds = time.perf_counter() - t_w
     fence()
     # Python's cyclic garbage collector is kept out of the timed region, as timeit does: a generation-2 collection is a 30 ms host
@@ -455,8 +501,7 @@ def main():
     # untimed blocks run until GC_RECOVER_S of load have passed (rank 0's clock decides, like the warm-up above)
     t_g = time.perf_counter()
     while True:
-        run_steps(0, max(args.steps, VPC))
-        warm_steps += max(args.steps, VPC)
+        warm_steps += warm_piece()
         torch.cuda.synchronize()
         more[0] = int(time.perf_counter() - t_g < GC_RECOVER_S)
         if use_dist:
@@ -471,24 +516,27 @@ def main():
     block_base = []          # one event per timed block, recorded on the caller's stream when the block starts
     tail_events = []         # per block: (last render work done, last gather done) -> the gather time nothing hides
     nxt = warm
-    timing_gather[0] = True
-    probe_first = probe.n
+    timing_gather[0] = full
+    probe_first = probe.n if full else 0
     probe_block = []
     _native.OVERLAP_STATS.update(calls=0, overlapped=0)
     # the two render kernels are timed INSIDE the timed region (one hipEvent pair per forward and per backward on the launch
     # stream): `roofline.avg_ms` is the dominant kernel's duration among the very launches `value` counts
-    if not args.no_stage_events:
+    if full and not args.no_stage_events:
         _native.set_profiling(2)
     for b in range(max(1, args.repeats)):
-        base = torch.cuda.Event(enable_timing=True)
-        base.record(torch.cuda.current_stream(dev))
-        block_base.append(base)
-        sub_tag[0] = b
-        probe_block.append(probe.n)
+        if full:
+            base = torch.cuda.Event(enable_timing=True)
+            base.record(torch.cuda.current_stream(dev))
+            block_base.append(base)
+            sub_tag[0] = b
+            probe_block.append(probe.n)
+        if args.dump_outputs and b == max(1, args.repeats) - 1:
+            dump_at[0] = nxt + args.steps
         t0 = time.perf_counter()
         run_steps(nxt, args.steps)
         sub_tag[0] = None
-        if do_gather:
+        if do_gather and full:
             ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ea.record(torch.cuda.current_stream(dev))       # behind every submission of the block (run_steps joined its workers)
             eb.record(gather_stream)
@@ -497,8 +545,9 @@ def main():
         block_dt.append(time.perf_counter() - t0)
         nxt += args.steps
     timing_gather[0] = False
+    dump_at[0] = None
     inreg = {}
-    if not args.no_stage_events:
+    if full and not args.no_stage_events:
         for name, t in _native.get_profile():
             inreg.setdefault(name, []).append(t)
         _native.set_profiling(0)
@@ -508,25 +557,28 @@ def main():
                 for k, v in inreg.items()}
     overlap_timed = "%d of %d" % (_native.OVERLAP_STATS["overlapped"], _native.OVERLAP_STATS["calls"])
     gc.enable()
-    sclk_timed = probe.mhz(probe_first)
-    probe_block.append(probe.n)
+    sclk_timed = probe.mhz(probe_first) if full else []
+    probe_block.append(probe.n if full else 0)
     sclk_blocks = [round(float(np.median(sclk_timed[a - probe_first:b - probe_first])), 1) if b > a else None
                    for a, b in zip(probe_block[:-1], probe_block[1:])] if sclk_timed else None
     gather_ms = [float(a.elapsed_time(b)) for a, b in gather_events] if gather_events else None
     gather_exposed_ms = [max(0.0, float(a.elapsed_time(b))) for a, b in tail_events] if tail_events else None
     # GPU time of the timed steps: the union of the submissions' [start, end] intervals on the device clock, per block
     gpu_busy_ms, sub_ms = [], []
-    for b in range(len(block_dt)):
+    for b in range(len(block_base)):
         iv = [(float(block_base[b].elapsed_time(e0)), float(block_base[b].elapsed_time(e1))) for tag, e0, e1 in sub_events if tag == b]
         gpu_busy_ms.append(union_ms(iv))
         sub_ms.append([round(b1 - a1, 3) for a1, b1 in sorted(iv)])
     sub_events.clear()
     block_dt_local = list(block_dt)
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        outputs = _outputs.write(args.dump_outputs, dumped["frames"][-1], dumped["radii"][-1], dumped["grads"])
 
     avg_ms, single = {}, None
     sclk_stage = []
     per_view = drop_in = fwd_only = rgb_time = None
-    if rank == 0 and not args.no_stage_events:
+    if full and rank == 0 and not args.no_stage_events:
         # whole --views-per-call submissions only: `kernels_ms` is a mean per LAUNCH and is divided by the views of a launch below
         # (a pass that mixed 12- and 8-view launches understated every per-frame figure by 17 %: the driver's --steps 20 run of
         # round 3 and its "18 % faster kernels")
@@ -536,7 +588,7 @@ def main():
         sclk_stage = probe.mhz(probe_stage)
         single = {"frames_per_s": round(n1 / d1, 3), "ms_per_frame": round(d1 / n1 * 1e3, 4), "frames": n1,
                   "note": "one submission in flight, hipEvents around every stage (each pair costs ~10 us of bubble)"}
-    if rank == 0 and not args.no_per_view and not args.no_stage_events:
+    if full and rank == 0 and not args.no_per_view and not args.no_stage_events:
         # ---- the drop-in API: the reference's call pattern, one GaussianRasterizer call per view (simple_raw_render.py:259-278)
         drop_in = {"call": "GaussianRasterizer(settings_v)(means3D, means2D, opacities, shs=, scales=, rotations=) per view + "
                            "loss.backward() per view" if grad else "GaussianRasterizer(...) per view under no_grad",
@@ -607,7 +659,7 @@ def main():
         torch.cuda.synchronize()
         drop_in["fresh_processes"] = _dist.drop_in_fresh_processes(args, os.path.abspath(__file__), W, H)
     gather_anchor = None
-    if world == 1 and not use_dist and not args.no_per_view and not args.no_gather:
+    if full and world == 1 and not use_dist and not args.no_per_view and not args.no_gather:
         torch.cuda.synchronize()
         gather_anchor = _dist.gather_anchor(args, os.path.abspath(__file__), W, H, dev_index)
     per_rank_blocks = None
@@ -626,7 +678,7 @@ def main():
         devs = [dict(zip(("rank", "local_rank", "device", "host_threads"), (int(x) for x in r.tolist()))) for r in allr]
     dt = float(np.median(block_dt))
 
-    if rank == 0:
+    if full and rank == 0:
         # ---- workload statistics for the bytes model, averaged over the views rank 0 rendered
         used = sorted({view_of(warm + i, 0, world, n_views, shard) for i in range(args.steps * max(1, args.repeats))})
         stats = dict(V=0.0, R=0.0, L=0.0, C_fwd=0.0, C_bwd=0.0)
@@ -667,6 +719,7 @@ def main():
                 ref_ctx = json.load(f)
         except (OSError, ValueError):
             pass
+    if rank == 0:
         shape = ("%d views per rasterize_views call (C ABI gsr_forward_batch%s), %d call%s in flight per rank" % (
             VPC, " / gsr_backward_batch" if grad else "", args.streams, "s" if args.streams != 1 else "")) if VPC > 1 else (
             "one GaussianRasterizer call per view (the reference's call pattern), %d in flight per rank" % args.streams)
@@ -677,8 +730,8 @@ def main():
             "ms_per_step_blocks": [round(x / args.steps * 1e3, 4) for x in block_dt],
             "warmup": args.warmup,
             "warmup_effective": {"steps": int(warm_steps), "seconds": round(warm_seconds, 3),
-                                 "note": "--warmup steps, allocator / stream priming, then whole blocks until --warmup-seconds "
-                                         "(%.2f) had passed, the garbage collection, then whole blocks for %.2f s more (the collection "
+                                 "note": "--warmup steps, allocator / stream priming, then pieces of the timed block until --warmup-seconds "
+                                         "(%.2f) had passed, the garbage collection, then pieces for %.2f s more (the collection "
                                          "idles the GPU for tens of ms and the clock needs ~50 ms of load to come back); all untimed"
                                          % (args.warmup_seconds, GC_RECOVER_S)},
             "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True,
@@ -687,20 +740,6 @@ def main():
                                              "note": "opt-in (GSR_OVERLAP=1): the library then starts a call's front end beside the previous "
                                                      "call's backward when every input tensor is provably unchanged (_native._OnSideStream); "
                                                      "off by default: every kernel runs in the caller's stream order"},
-            # GPU time of the TIMED steps themselves (rank 0): per block, the union of the submissions' [start, end] hipEvent
-            # intervals on the streams they ran on (loss kernels included), and the block's wall time over it
-            "gpu_ms_per_step_timed": round(float(np.median(gpu_busy_ms)) / args.steps, 4) if gpu_busy_ms else None,
-            "gpu_ms_per_step_timed_blocks": [round(x / args.steps, 4) for x in gpu_busy_ms],
-            "gpu_ms_submissions_blocks": sub_ms if sum(len(x) for x in sub_ms) <= 64 else None,   # per block, every submission's own span
-            "wall_over_gpu": round(float(np.median([w * 1e3 / g for w, g in zip(block_dt_local, gpu_busy_ms) if g > 0])), 4)
-            if gpu_busy_ms and all(g > 0 for g in gpu_busy_ms) else None,
-            "sclk_mhz": {"timed_region": round(float(np.median(sclk_timed)), 1) if sclk_timed else None,
-                         "timed_region_min_max": [round(min(sclk_timed), 1), round(max(sclk_timed), 1)] if sclk_timed else None,
-                         "timed_blocks": sclk_blocks,
-                         "stage_pass": round(float(np.median(sclk_stage)), 1) if sclk_stage else None,
-                         "probes": len(sclk_timed) + len(sclk_stage),
-                         "how": "one-wave probe kernel per submission on a side stream, beside the frame's kernels: s_memtime "
-                                "(shader cycles) over s_memrealtime (%d kHz)" % probe.khz},
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "%s %dx%d %s, %d circle views, %s profile, SH degree %d (M=%d); %s; %s%s" % (
                 args.workload, W, H, "fwd+bwd" if grad else "fwd", n_views, args.profile, D, M, shape,
@@ -710,46 +749,71 @@ def main():
                 "baseline_config": cfg["what"],
                 "call_shape": {"views_per_call": VPC, "calls_in_flight": args.streams,
                                "entry_point": "rasterize_views" if VPC > 1 else "GaussianRasterizer.forward"},
-                "points": P, "num_rendered_avg": int(stats["R"]), "list_pairs_avg": int(stats["L"]),
+                "points": P},
+            "kernels_sha": kernels_sha(),
+            "multi_gpu_status": "measured on %d GPU(s)" % world if (world > 1 and not host_collectives) else
+                                "no run on more than one GPU has been measured (one-GPU machines only): the N > 1 path is rehearsed "
+                                "with gloo ranks sharing one GPU (tests/test_gpu_bench.py) and 8 CPU ranks (tests/test_cpu_multiview.py)",
+            "views_per_call": VPC, "streams_per_rank": args.streams,
+            "full": full,
+        }
+        if outputs is not None:
+            out["outputs"] = {"dir": args.dump_outputs, "arrays": outputs,
+                              "what": "the frame of the last timed step, its radii and the gradients of the last timed submission "
+                                      "(summed over its views); float32, per-Gaussian rows a fixed seeded sample"}
+        if full:
+            out["config"].update({
+                "num_rendered_avg": int(stats["R"]), "list_pairs_avg": int(stats["L"]),
                 "list_pairs_note": "num_rendered = pairs of the reference's tile rectangles (reported bit-exact); list_pairs = pairs the "
                                    "library emits and sorts: rectangles clipped to where alpha can reach 1/255 (gsr_params.reference_lists = 0, "
                                    "the default; GSR_REFERENCE_LISTS=1 restores the reference's lists)",
                 "visible_avg": int(stats["V"]),
-                "consumed_entries_fwd_avg": int(stats["C_fwd"]), "consumed_entries_bwd_avg": int(stats["C_bwd"])},
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "kernels_sha": kernels_sha(),
-            # the reference's API as its caller uses it: per view, settings built inside the loop, one call, one backward; one thread,
-            # one stream, in order (drop_in_api has the variants)
-            "drop_in": None if drop_in is None else {
-                "frames_per_s": drop_in["frames_per_s"].get("literal"), "unit": "frames/s",
-                "fraction_of_value": round(drop_in["frames_per_s"].get("literal", 0.0) / (world * args.steps / dt), 4),
-                "what": "the reference caller's loop body as it stands (simple_raw_render.py:260-278): per view the settings are built "
-                        "for the call (fresh tensors), GaussianRasterizer(settings)(means3D, means2D, opacities, shs=, scales=, "
-                        "rotations=), loss.backward(); ONE thread, ONE stream, plain stream order (the library's default)",
-                "host_exposed_us": drop_in.get("host_exposed_us"),
-                "fresh_processes": drop_in.get("fresh_processes")},
-            "reference_build_context": ref_ctx,
-            "multi_gpu_status": "measured on %d GPU(s)" % world if (world > 1 and not host_collectives) else
-                                "no run on more than one GPU has been measured (one-GPU leases only): the N > 1 path is rehearsed with "
-                                "gloo ranks sharing one GPU (tests/test_gpu_bench.py) and 8 CPU ranks (tests/test_cpu_multiview.py)",
-            # world-size-1 anchor of the frame gather (a child process with a 1-rank RCCL group): frames/s with the gather of every
-            # submission's frames on its side stream vs without -- what the first measured 8-GPU run starts from
-            "gather_world1_anchor": gather_anchor,
-            "kernels_ms": {k: round(v, 4) for k, v in avg_ms.items()},
-            "kernel_timing": "hipEvents on the launch stream, single-stream pass right after the timed region",
-            "views_per_call": VPC, "kernels_ms_per_frame": {k: round(v / VPC, 4) for k, v in avg_ms.items()},
-            # per stage: algorithmic bytes of a launch (the per-call-shape model of algorithmic_bytes) over its measured duration
-            "kernels_algorithmic_GBps": {k: round(bytes_per[k] * VPC / (v * 1e-3) / 1e9, 1) for k, v in avg_ms.items()
-                                         if k in bytes_per and v > 0},
-            "streams_per_rank": args.streams, "single_stream": single,
-            "drop_in_api": drop_in, "per_view_api_frames_per_s": per_view,
-            "forward_only": fwd_only, "rgb_time_equiv": rgb_time,
-            "frame_hbm": {"algorithmic_bytes": int(frame_bytes), "gpu_ms_sum": round(frame_gpu_ms, 4),
-                          "GBps": round(frame_bytes / (frame_gpu_ms * 1e-3) / 1e9, 1) if frame_gpu_ms else None,
-                          "frac_of_8000": round(frame_bytes / (frame_gpu_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if frame_gpu_ms else None,
-                          "frac_of_6300": round(frame_bytes / (frame_gpu_ms * 1e-3) / 1e9 / HBM_ACHIEVABLE_GBS, 4) if frame_gpu_ms else None},
-        }
+                "consumed_entries_fwd_avg": int(stats["C_fwd"]), "consumed_entries_bwd_avg": int(stats["C_bwd"])})
+            out.update({
+                # GPU time of the TIMED steps themselves (rank 0): per block, the union of the submissions' [start, end] hipEvent
+                # intervals on the streams they ran on (loss kernels included), and the block's wall time over it
+                "gpu_ms_per_step_timed": round(float(np.median(gpu_busy_ms)) / args.steps, 4) if gpu_busy_ms else None,
+                "gpu_ms_per_step_timed_blocks": [round(x / args.steps, 4) for x in gpu_busy_ms],
+                "gpu_ms_submissions_blocks": sub_ms if sum(len(x) for x in sub_ms) <= 64 else None,   # per block, every submission's own span
+                "wall_over_gpu": round(float(np.median([w * 1e3 / g for w, g in zip(block_dt_local, gpu_busy_ms) if g > 0])), 4)
+                if gpu_busy_ms and all(g > 0 for g in gpu_busy_ms) else None,
+                "sclk_mhz": {"timed_region": round(float(np.median(sclk_timed)), 1) if sclk_timed else None,
+                             "timed_region_min_max": [round(min(sclk_timed), 1), round(max(sclk_timed), 1)] if sclk_timed else None,
+                             "timed_blocks": sclk_blocks,
+                             "stage_pass": round(float(np.median(sclk_stage)), 1) if sclk_stage else None,
+                             "probes": len(sclk_timed) + len(sclk_stage),
+                             "how": "one-wave probe kernel per submission on a side stream, beside the frame's kernels: s_memtime "
+                                    "(shader cycles) over s_memrealtime (%d kHz)" % probe.khz},
+                "roofline": roofline,
+                "cpu_baseline": cpu,
+                # the reference's API as its caller uses it: per view, settings built inside the loop, one call, one backward; one
+                # thread, one stream, in order (drop_in_api has the variants)
+                "drop_in": None if drop_in is None else {
+                    "frames_per_s": drop_in["frames_per_s"].get("literal"), "unit": "frames/s",
+                    "fraction_of_value": round(drop_in["frames_per_s"].get("literal", 0.0) / (world * args.steps / dt), 4),
+                    "what": "the reference caller's loop body as it stands (simple_raw_render.py:260-278): per view the settings are built "
+                            "for the call (fresh tensors), GaussianRasterizer(settings)(means3D, means2D, opacities, shs=, scales=, "
+                            "rotations=), loss.backward(); ONE thread, ONE stream, plain stream order (the library's default)",
+                    "host_exposed_us": drop_in.get("host_exposed_us"),
+                    "fresh_processes": drop_in.get("fresh_processes")},
+                "reference_build_context": ref_ctx,
+                # world-size-1 anchor of the frame gather (a child process with a 1-rank RCCL group): frames/s with the gather of every
+                # submission's frames on its side stream vs without -- what the first measured 8-GPU run starts from
+                "gather_world1_anchor": gather_anchor,
+                "kernels_ms": {k: round(v, 4) for k, v in avg_ms.items()},
+                "kernel_timing": "hipEvents on the launch stream, single-stream pass right after the timed region",
+                "kernels_ms_per_frame": {k: round(v / VPC, 4) for k, v in avg_ms.items()},
+                # per stage: algorithmic bytes of a launch (the per-call-shape model of algorithmic_bytes) over its measured duration
+                "kernels_algorithmic_GBps": {k: round(bytes_per[k] * VPC / (v * 1e-3) / 1e9, 1) for k, v in avg_ms.items()
+                                             if k in bytes_per and v > 0},
+                "single_stream": single,
+                "drop_in_api": drop_in, "per_view_api_frames_per_s": per_view,
+                "forward_only": fwd_only, "rgb_time_equiv": rgb_time,
+                "frame_hbm": {"algorithmic_bytes": int(frame_bytes), "gpu_ms_sum": round(frame_gpu_ms, 4),
+                              "GBps": round(frame_bytes / (frame_gpu_ms * 1e-3) / 1e9, 1) if frame_gpu_ms else None,
+                              "frac_of_8000": round(frame_bytes / (frame_gpu_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if frame_gpu_ms else None,
+                              "frac_of_6300": round(frame_bytes / (frame_gpu_ms * 1e-3) / 1e9 / HBM_ACHIEVABLE_GBS, 4) if frame_gpu_ms else None},
+            })
         if use_dist:
             out["per_rank_frames_per_s"] = [round(args.steps / float(np.median(b)), 1) for b in per_rank_blocks]
             out["distributed"] = {"world_size": dist.get_world_size(), "world": dist.get_world_size(), "backend": dist.get_backend(),

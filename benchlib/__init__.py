@@ -5,4 +5,5 @@
     roofline      the `roofline` object: HBM fraction of the dominant kernel, counter traffic and SIMD occupancy from profiles/pmc_traffic.json
     cpu_baseline  the `cpu_baseline` object: the plain-C oracle timed on the host cores this process may use
     dist          self-launch under torch.distributed.run, the child processes for side figures (drop-in probes, world-1 gather anchor)
+    outputs       --dump-outputs: the arrays the timed path's last step handed its caller, as float32 .npy files
 """

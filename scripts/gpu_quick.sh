@@ -5,7 +5,7 @@ OUT=$PWD/gpurun_out/quick
 mkdir -p $OUT
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_api.py tests/test_gpu_batch.py tests/test_gpu_fullsize.py -x -q -m gpu 2>&1 | tail -3
 for extra in "" "--views-per-call 1"; do
-python bench.py --steps 48 --warmup 12 --repeats 3 --no-cpu-baseline --no-per-view $extra > $OUT/b.json 2>$OUT/b.err
+python bench.py --full --steps 48 --warmup 12 --repeats 3 --no-cpu-baseline --no-per-view $extra > $OUT/b.json 2>$OUT/b.err
 python - $OUT/b.json <<'PY'
 import json,sys
 try:

@@ -7,7 +7,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 1500 python -m pytest tests/test_gpu_parity.py tests/test_gpu_api.py tests/test_gpu_batch.py tests/test_gpu_hostpath.py -x -q -m gpu 2>&1 | grep -v "amdgpu.ids" | tail -5 > $OUT/tests.log
 cat $OUT/tests.log
-python bench.py ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err
 python - "$OUT/bench.json" <<'PY'
 import json, sys
 try:

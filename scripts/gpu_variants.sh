@@ -7,7 +7,7 @@ IFS=';' read -ra VARS <<< "$1"
 for v in "${VARS[@]}"; do
   name=${v%%|*}; flags=${v#*|}
   GSR_EXTRA_FLAGS="$flags" python gaussian-pcloud-render_amd/build.py --force > $OUT/build_$name.log 2>&1 || { echo "$name: build failed"; tail -5 $OUT/build_$name.log; continue; }
-  python bench.py --steps 48 --warmup 12 --repeats 3 --no-cpu-baseline --no-per-view ${BENCH_EXTRA:-} > $OUT/$name.json 2>$OUT/$name.err
+  python bench.py --full --steps 48 --warmup 12 --repeats 3 --no-cpu-baseline --no-per-view ${BENCH_EXTRA:-} > $OUT/$name.json 2>$OUT/$name.err
   python - $OUT/$name.json $name <<'PY'
 import json,sys
 try:

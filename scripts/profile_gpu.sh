@@ -9,9 +9,9 @@ MODE=${3:-full}         # "trace": kernel-trace stats only (no PMC passes)
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-python $PWD/bench.py $EXTRA > $OUT/bench.json 2> $OUT/bench.err
+python $PWD/bench.py --full $EXTRA > $OUT/bench.json 2> $OUT/bench.err
 tail -c 600 $OUT/bench.json
-BENCH="python $PWD/bench.py --steps 24 --warmup 3 --repeats 2 --no-cpu-baseline --no-per-view --streams 1 $EXTRA"
+BENCH="python $PWD/bench.py --full --steps 24 --warmup 3 --repeats 2 --no-cpu-baseline --no-per-view --streams 1 $EXTRA"
 (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- $BENCH > $OUT/bench_trace.log 2>&1)
 if [ "$MODE" != "trace" ]; then
 (cd /tmp && rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d $OUT/pmc_fetch -o pmc -- $BENCH > $OUT/bench_pmc_fetch.log 2>&1)
@@ -31,7 +31,7 @@ fi
 # host-side audit: GPU idle time, copies and blocking API calls per rasterizer call (single stream, no stage events)
 # (one long timed block; the untimed blocks before it -- priming, instrumentation warm-up, the block behind the garbage collection --
 # each end in a synchronize, so the audited window is cut from the last quarter of the trace: inside the timed block)
-TL="python $PWD/bench.py --steps 480 --warmup 12 --repeats 1 --warmup-seconds 0 --no-cpu-baseline --no-per-view --streams 1 --no-stage-events $EXTRA"
+TL="python $PWD/bench.py --full --steps 480 --warmup 12 --repeats 1 --warmup-seconds 0 --no-cpu-baseline --no-per-view --streams 1 --no-stage-events $EXTRA"
 (cd /tmp && rocprofv3 --kernel-trace --memory-copy-trace --hip-trace --output-format csv -d $OUT/tl12 -o tl -- $TL > $OUT/tl12.log 2>&1)
 (cd /tmp && rocprofv3 --kernel-trace --memory-copy-trace --hip-trace --output-format csv -d $OUT/tl1 -o tl -- $TL --views-per-call 1 > $OUT/tl1.log 2>&1)
 { echo "== bench.py --streams 1 --no-stage-events, 12 views per rasterize_views call =="; python $PWD/scripts/timeline.py $OUT/tl12 0.74 12;
@@ -41,14 +41,14 @@ find $OUT/tl12 $OUT/tl1 -name "*.csv" -size +1M -delete
 # secondary lines: configs[1] (200K voxelised, 1080p, forward only) and configs[4] (2M points, 4K, fwd+bwd, the
 # 8 views of a turn in one call on this one GPU)
 if [ "$MODE" != "trace" ]; then
-python $PWD/bench.py --config 1 --no-cpu-baseline --no-per-view > $OUT/bench_config1.json 2> $OUT/bench_config1.err
-python $PWD/bench.py --config 4 --steps 16 --warmup 8 --no-cpu-baseline --no-per-view > $OUT/bench_config4.json 2> $OUT/bench_config4.err
-python $PWD/bench.py --config 3 --steps 16 --warmup 8 --no-cpu-baseline --no-per-view > $OUT/bench_config3.json 2> $OUT/bench_config3.err
+python $PWD/bench.py --full --config 1 --no-cpu-baseline --no-per-view > $OUT/bench_config1.json 2> $OUT/bench_config1.err
+python $PWD/bench.py --full --config 4 --steps 16 --warmup 8 --no-cpu-baseline --no-per-view > $OUT/bench_config4.json 2> $OUT/bench_config4.err
+python $PWD/bench.py --full --config 3 --steps 16 --warmup 8 --no-cpu-baseline --no-per-view > $OUT/bench_config3.json 2> $OUT/bench_config3.err
 tail -c 300 $OUT/bench_config1.err $OUT/bench_config4.err $OUT/bench_config3.err
 fi
 python $PWD/scripts/compare_ref.py 0 > $OUT/compare_ref.json 2> $OUT/compare_ref.err
 # the round driver's command line (20-step blocks: one 12-view and one 8-view submission each)
-python $PWD/bench.py --steps 20 --warmup 5 > $OUT/bench_driver_shape.json 2> $OUT/bench_driver_shape.err
+python $PWD/bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_shape.json 2> $OUT/bench_driver_shape.err
 python $PWD/scripts/summarize_prof.py $OUT > $OUT/summary.txt 2>&1
 head -40 $OUT/summary.txt
 # keep the merge small: drop the raw per-dispatch traces, keep stats + counter CSVs

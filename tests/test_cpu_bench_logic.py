@@ -109,3 +109,32 @@ def test_cpu_quota_is_read_from_the_cgroup(tmp_path):
     (tmp_path / "cpu.max").write_text("max 100000\n")
     assert cpu_quota_cores(str(tmp_path)) is None
     assert cpu_quota_cores(str(tmp_path / "absent")) is None
+
+
+def test_dumped_outputs_are_a_fixed_sample_within_64_mb():
+    """--dump-outputs (benchlib/outputs.py): float32 arrays, a 1080p frame whole and a 4K frame sampled, the same seeded rows of
+    every per-Gaussian array from call to call, 64 MB at most in all."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    from benchlib import outputs
+    rng = np.random.default_rng(5)
+    P = 300_000
+    radii = rng.integers(0, 40, P).astype(np.int32)
+    grads = {"means3D": rng.normal(size=(P, 3)), "shs": rng.normal(size=(P, 16, 3)).astype(np.float32)}
+    for H, W in ((1080, 1920), (2160, 3840)):
+        frame = rng.random((3, H, W), dtype=np.float32)
+        a, b = outputs.select(frame, radii, grads), outputs.select(frame, radii, grads)
+        assert sorted(a) == ["grad_means3D", "grad_shs", "image", "radii"]
+        assert all(x.dtype == np.float32 for x in a.values()) and sum(x.nbytes for x in a.values()) <= outputs.MAX_BYTES
+        assert all((a[k] == b[k]).all() for k in a)
+        n = a["radii"].shape[0]
+        assert 0 < n <= outputs.MAX_ROWS and a["grad_shs"].shape == (n, 16, 3) and a["grad_means3D"].shape == (n, 3)
+        rows = outputs.sample(P, n, 1)
+        assert (a["radii"] == radii[rows]).all() and (a["grad_shs"] == grads["shs"][rows]).all()
+        if H * W <= outputs.MAX_PIXELS:
+            assert (a["image"] == frame).all()
+        else:
+            px = outputs.sample(H * W, outputs.MAX_PIXELS, 0)
+            assert a["image"].shape == (3, outputs.MAX_PIXELS) and (a["image"] == frame.reshape(3, -1)[:, px]).all()
+    small = outputs.select(np.zeros((3, 4, 5), np.float32), radii[:10], {"opacities": np.ones((10, 1))})
+    assert small["image"].shape == (3, 4, 5) and small["radii"].shape == (10,) and small["grad_opacities"].shape == (10, 1)

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -20,8 +21,8 @@ def _last_json(out):
 
 
 def test_single_rank_line_has_the_contract_fields(gpu_device):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--drop-in-processes", "2"] + SMALL, capture_output=True, text=True,
-                       timeout=900, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--drop-in-processes", "2"] + SMALL, capture_output=True,
+                       text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -54,10 +55,43 @@ def test_single_rank_line_has_the_contract_fields(gpu_device):
     assert "no run on more than one GPU has been measured" in d["multi_gpu_status"]
 
 
+def test_plain_run_times_exactly_the_steps_and_dumps_its_outputs(gpu_device, tmp_path):
+    """Without --full: one timed block of exactly --steps steps, the headline fields and nothing measured beside them; with
+    --dump-outputs the last step's frame, radii and gradients as float32 .npy files, identical inputs (and so an identical frame)
+    from run to run."""
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", str(out)] + SMALL, capture_output=True,
+                           text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _last_json(r.stdout)
+        for key in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype"):
+            assert key in d, key
+        assert d["steps"] == 8 and d["repeats"] == 1 and len(d["ms_per_step_blocks"]) == 1 and d["full"] is False
+        assert d["value"] > 0 and abs(d["ms_per_step"] - 1e3 / d["value"]) <= 1e-3 * d["ms_per_step"] + 1e-4
+        assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        for key in ("roofline", "cpu_baseline", "drop_in", "kernels_ms", "sclk_mhz", "gpu_ms_per_step_timed"):
+            assert key not in d, key
+        files = sorted(p.name for p in out.iterdir())
+        assert files == sorted(n + ".npy" for n in d["outputs"]["arrays"])
+        arrays = {f[:-4]: np.load(str(out / f)) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["image"].shape == (3, 256, 256) and arrays["radii"].shape == (20000,) and (arrays["radii"] > 0).any()
+        for leaf in ("means3D", "means2D", "shs", "opacities", "scales", "rotations"):
+            g = arrays["grad_" + leaf]
+            assert g.shape[0] == 20000 and np.abs(g).max() > 0, leaf
+        dumps.append(arrays)
+    assert (dumps[0]["image"] == dumps[1]["image"]).all() and (dumps[0]["radii"] == dumps[1]["radii"]).all()
+    g0, g1 = dumps[0]["grad_means3D"], dumps[1]["grad_means3D"]     # float atomics: sums in another order
+    assert np.abs(g0 - g1).max() <= 1e-4 * np.abs(g0).max()
+
+
 def test_two_ranks_complete(gpu_device):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--device-index", "0",
-           "--no-cpu-baseline"] + SMALL
+           "--full", "--no-cpu-baseline"] + SMALL
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _last_json(r.stdout)
@@ -118,7 +152,7 @@ def test_config3_shape_two_ranks_p2p_gather_on_one_gpu(gpu_device):
     step), frames gathered on rank 0 with the grouped send / receive fallback; the line carries per-rank rates and the exposed
     gather time."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--device-index", "0",
-                        "--no-cpu-baseline", "--repeats", "2", "--config", "3", "--gather-mode", "p2p", "--no-per-view",
+                        "--full", "--no-cpu-baseline", "--repeats", "2", "--config", "3", "--gather-mode", "p2p", "--no-per-view",
                         "--workload", "synth-THuman-256", "--points", "20000", "--width", "256", "--height", "256", "--steps", "8",
                         "--warmup", "2"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
@@ -137,7 +171,7 @@ def test_eight_rank_rehearsal_on_one_gpu(config, gpu_device):
     issues the same collectives in the same order (or the run hangs), the line carries one rate per rank, where each rank ran and
     its capped host thread count, and says that no multi-GPU number has been measured."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--dist-backend", "gloo", "--device-index", "0",
-                        "--no-cpu-baseline", "--repeats", "1", "--config", str(config), "--no-per-view", "--warmup-seconds", "0.2",
+                        "--full", "--no-cpu-baseline", "--repeats", "1", "--config", str(config), "--no-per-view", "--warmup-seconds", "0.2",
                         "--workload", "synth-THuman-256", "--points", "6000", "--width", "160", "--height", "96", "--steps", "4",
                         "--warmup", "1"], capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
