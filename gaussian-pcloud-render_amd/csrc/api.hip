@@ -239,6 +239,36 @@ static int make_batch(const gsr_params* p, int V, void* geom, size_t geom_bytes,
     return GSR_OK;
 }
 
+// What the last forward on a geometry arena saved for the backward, kept on the host so that gsr_backward_batch_channels can refuse
+// a backward that does not match it without reading anything back from the device.  Keyed by the arena's address: every forward
+// and recolor on an arena rewrites its record.
+struct FrameRecord {
+    int kind;             // 0 colour forward, 1 channels forward, 2 recolor
+    int need_backward;
+    int nx, layout;       // channels forwards
+    int V, P, W, H;
+    const void* xstate;   // the extra-state block the channels forward saved into (NULL: none)
+    size_t xstate_bytes;
+};
+static std::mutex g_frames_mu;
+static std::map<const void*, FrameRecord> g_frames;
+static void note_frame(const void* geom, const FrameRecord& r)
+{
+    std::lock_guard<std::mutex> lk(g_frames_mu);
+    if (g_frames.size() > 4096 && !g_frames.count(geom)) g_frames.clear();   // (arenas come and go; records of freed ones are dropped)
+    g_frames[geom] = r;
+}
+static bool find_frame(const void* geom, FrameRecord& r)
+{
+    std::lock_guard<std::mutex> lk(g_frames_mu);
+    const auto it = g_frames.find(geom);
+    if (it == g_frames.end()) return false;
+    r = it->second;
+    return true;
+}
+// per-view bytes of the extra-channel state for a binning arena of capacity cap
+static size_t xstate_view_bytes(int W, int H, int64_t cap, int nx) { return align_up(xstate_view(nullptr, W, H, cap, nx).bytes, 256); }
+
 static int memset_views(hipStream_t s, void* base, size_t stride, size_t bytes, int V)
 {
     if (bytes == 0) return GSR_OK;
@@ -263,6 +293,29 @@ static int forward_impl(const gsr_params* p, int V, void* geom, size_t geom_byte
     if (int e = make_batch(p, V, geom, geom_bytes, image, image_bytes, mode == 2 ? nullptr : binning, binning_bytes,
                            p->need_backward != 0, B))
         return e;
+    // gsr_forward_batch_channels_train hands its extra-state block over as (state.accum = base, state.bytes = size): carved here
+    // for this binning arena's capacity (a resumed call carves it anew for the larger arena)
+    ExtraChannels Xs;
+    const void* xraw = X != nullptr ? (const void*)X->state.accum : nullptr;
+    if (X != nullptr && X->state.accum != nullptr) {
+        Xs = *X;
+        const size_t need = (size_t)V * xstate_view_bytes(p->W, p->H, B.b.cap, X->nx) + 256;
+        if (X->state.bytes < need)
+            return fail(GSR_ERR_CAPACITY, "[gsr] extra-state block too small (%zu < %zu: V * gsr_extra_state_bytes(W, H, n, nx) for a binning "
+                        "arena of V * gsr_binning_bytes(n))", X->state.bytes, need);
+        Xs.state = xstate_view(align256(const_cast<float*>(X->state.accum)), p->W, p->H, B.b.cap, X->nx);
+        Xs.state_stride = xstate_view_bytes(p->W, p->H, B.b.cap, X->nx);
+        if (!p->need_backward) Xs.state = XStateView{nullptr, nullptr, 0};
+        X = &Xs;
+    }
+    {
+        FrameRecord r{X ? 1 : 0, p->need_backward != 0, X ? X->nx : 0, 0, V, p->P, p->W, p->H, nullptr, 0};
+        if (X) {
+            r.layout = X->values_hi ? 2 : X->view_stride ? 1 : 0;
+            if (X->state.accum) { r.xstate = xraw; r.xstate_bytes = X->state.bytes; }
+        }
+        note_frame(geom, r);
+    }
     HostLanding* landp = nullptr;
     if (int e = landing(&landp)) return e;
     HostLanding& t_land = *landp;
@@ -506,20 +559,50 @@ int gsr_forward_batch(const gsr_params* p, int V, void* geom, size_t geom_bytes,
                         resume ? 1 : 0, (hipStream_t)stream);
 }
 
+static int extra_channels(const gsr_params* p, int nx, int extra_per_view, const float* extra, const float* extra_view_scale,
+                          const float* bg_extra, float* out_extra, ExtraChannels& X)
+{
+    if (!p) return fail(GSR_ERR_INVALID, "[gsr] params is NULL");
+    if (nx != 4 && nx != 8) return fail(GSR_ERR_INVALID, "[gsr] extra channels come in 4 or 8 (got %d): pad with zeros", nx);
+    if (!extra || !bg_extra || !out_extra) return fail(GSR_ERR_INVALID, "[gsr] an extra-channel pointer is NULL");
+    if (extra_per_view < 0 || extra_per_view > 2 || (extra_per_view == 2 && nx != 8))
+        return fail(GSR_ERR_INVALID, "[gsr] extra_per_view is 0, 1 or (with 8 channels) 2");
+    X = ExtraChannels{nx, extra, extra_view_scale, bg_extra, out_extra, extra_per_view == 1 ? (size_t)p->P * (size_t)nx : (size_t)0};
+    if (extra_per_view == 2) {   // [P][4] shared by the views, then [V][P][4]
+        X.values_hi = extra + (size_t)p->P * 4;
+        X.hi_view_stride = (size_t)p->P * 4;
+    }
+    return GSR_OK;
+}
+
 int gsr_forward_batch_channels(const gsr_params* p, int V, void* geom, size_t geom_bytes, void* image, size_t image_bytes,
                                void* binning, size_t binning_bytes, int* radii, float* out_color, int64_t* num_rendered, int resume,
                                int nx, int extra_per_view, const float* extra, const float* extra_view_scale, const float* bg_extra,
                                float* out_extra, gsr_stream_t stream)
 {
-    if (nx != 4 && nx != 8) return fail(GSR_ERR_INVALID, "[gsr] extra channels come in 4 or 8 (got %d): pad with zeros", nx);
-    if (!extra || !bg_extra || !out_extra) return fail(GSR_ERR_INVALID, "[gsr] an extra-channel pointer is NULL");
-    if (extra_per_view < 0 || extra_per_view > 2 || (extra_per_view == 2 && nx != 8))
-        return fail(GSR_ERR_INVALID, "[gsr] extra_per_view is 0, 1 or (with 8 channels) 2");
-    ExtraChannels X{nx, extra, extra_view_scale, bg_extra, out_extra, extra_per_view == 1 ? (size_t)p->P * (size_t)nx : (size_t)0};
-    if (extra_per_view == 2) {   // [P][4] shared by the views, then [V][P][4]
-        X.values_hi = extra + (size_t)p->P * 4;
-        X.hi_view_stride = (size_t)p->P * 4;
-    }
+    ExtraChannels X;
+    if (int e = extra_channels(p, nx, extra_per_view, extra, extra_view_scale, bg_extra, out_extra, X)) return e;
+    return forward_impl(p, V, geom, geom_bytes, image, image_bytes, binning, binning_bytes, radii, out_color, num_rendered,
+                        resume ? 1 : 0, (hipStream_t)stream, &X);
+}
+
+size_t gsr_extra_state_bytes(int W, int H, int64_t num_rendered, int nx)
+{
+    if (W <= 0 || H <= 0 || (nx != 4 && nx != 8)) return 0;
+    // the capacity a binning arena of V * gsr_binning_bytes(num_rendered) bytes is carved for (make_batch)
+    return xstate_view_bytes(W, H, bin_capacity_from_bytes(bin_view(nullptr, num_rendered).bytes), nx);
+}
+
+int gsr_forward_batch_channels_train(const gsr_params* p, int V, void* geom, size_t geom_bytes, void* image, size_t image_bytes,
+                                     void* binning, size_t binning_bytes, int* radii, float* out_color, int64_t* num_rendered,
+                                     int resume, int nx, int extra_per_view, const float* extra, const float* extra_view_scale,
+                                     const float* bg_extra, float* out_extra, void* extra_state, size_t extra_state_bytes,
+                                     gsr_stream_t stream)
+{
+    ExtraChannels X;
+    if (int e = extra_channels(p, nx, extra_per_view, extra, extra_view_scale, bg_extra, out_extra, X)) return e;
+    if (!extra_state) return fail(GSR_ERR_INVALID, "[gsr] extra_state is NULL");
+    X.state = XStateView{reinterpret_cast<float*>(extra_state), nullptr, extra_state_bytes};
     return forward_impl(p, V, geom, geom_bytes, image, image_bytes, binning, binning_bytes, radii, out_color, num_rendered,
                         resume ? 1 : 0, (hipStream_t)stream, &X);
 }
@@ -558,6 +641,7 @@ int gsr_forward_recolor(const gsr_params* p, int V, int colors_per_view, void* g
     if (!out_color || !p->bg || !binning) return fail(GSR_ERR_INVALID, "[gsr] recolor: NULL pointer");
     Batch B;
     if (int e = make_batch(p, V, geom, geom_bytes, image, image_bytes, const_cast<void*>(binning), binning_bytes, false, B)) return e;
+    note_frame(geom, FrameRecord{2, p->need_backward != 0, 0, 0, V, p->P, p->W, p->H, nullptr, 0});
     const Launch L{(hipStream_t)stream, p->debug};
     const int res = sorted_buffer(tile_count(p));
     {
@@ -601,6 +685,75 @@ int gsr_backward_batch(const gsr_params* p, int V, const int* radii, const void*
     {
         ProfScope ps("render_backward", L.stream);
         if (int e = launch_render_backward(L, *p, B, B.b.val[res], dL_dpix)) return e;
+    }
+    {
+        ProfScope ps("preprocess_backward", L.stream);
+        if (int e = launch_preprocess_backward(L, *p, B, radii, dL_dmean2D, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                                               dL_dscale, dL_drot))
+            return e;
+    }
+    return GSR_OK;
+}
+
+int gsr_backward_batch_channels(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
+                                size_t binning_bytes, const void* image, size_t image_bytes, const float* dL_dpix, float* dL_dmean2D,
+                                float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                                float* dL_dscale, float* dL_drot, int nx, int extra_per_view, const float* extra,
+                                const float* extra_view_scale, const float* bg_extra, const void* extra_state, size_t extra_state_bytes,
+                                const float* dL_dextra, float* dL_dextra_values, gsr_stream_t stream)
+{
+    ExtraChannels X;
+    if (int e = extra_channels(p, nx, extra_per_view, extra, extra_view_scale, bg_extra, dL_dextra_values, X)) return e;
+    if (!dL_dextra || !extra_state) return fail(GSR_ERR_INVALID, "[gsr] dL_dextra / extra_state is NULL");
+    if (int e = check_params(p, V)) return e;
+    if (p->P == 0) return GSR_OK;
+    // the forward this backward differentiates has to be a channels forward with need_backward = 1 into this extra-state block, with
+    // the same channels, layout and sizes
+    FrameRecord r;
+    if (!find_frame(geom, r))
+        return fail(GSR_ERR_INVALID, "[gsr] backward_channels: no forward on this geometry arena (run gsr_forward_batch_channels_train first)");
+    if (r.kind == 2)
+        return fail(GSR_ERR_INVALID, "[gsr] backward_channels after gsr_forward_recolor is not supported: the recolor replaced the saves "
+                    "of the channels forward (run gsr_forward_batch_channels_train again)");
+    if (r.kind != 1 || !r.need_backward || r.xstate == nullptr)
+        return fail(GSR_ERR_INVALID, "[gsr] backward_channels: the forward on this arena saved no extra channels (it needs "
+                    "gsr_forward_batch_channels_train with need_backward = 1)");
+    const int layout = extra_per_view;
+    if (r.nx != nx || r.layout != layout)
+        return fail(GSR_ERR_INVALID, "[gsr] backward_channels: nx = %d, extra_per_view = %d, but the forward had nx = %d, extra_per_view = %d",
+                    nx, layout, r.nx, r.layout);
+    if (r.V != V || r.P != p->P || r.W != p->W || r.H != p->H)
+        return fail(GSR_ERR_INVALID, "[gsr] backward_channels: views / sizes differ from the forward's");
+    if (r.xstate != extra_state || extra_state_bytes < r.xstate_bytes)
+        return fail(GSR_ERR_INVALID, "[gsr] backward_channels: extra_state is not the block the forward saved into");
+    if (!radii || !dL_dpix || !dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dcov3D)
+        return fail(GSR_ERR_INVALID, "[gsr] a required backward pointer is NULL");
+    if (p->shs && !dL_dsh) return fail(GSR_ERR_INVALID, "[gsr] dL_dsh is NULL");
+    if (p->scales && (!dL_dscale || !dL_drot)) return fail(GSR_ERR_INVALID, "[gsr] dL_dscale/dL_drot is NULL");
+    if (p->scales && ((uintptr_t)dL_drot & 15u)) return fail(GSR_ERR_INVALID, "[gsr] dL_drot must be 16-byte aligned (it is written one float4 per Gaussian)");
+    if (!binning) return fail(GSR_ERR_INVALID, "[gsr] binning arena is NULL");
+    Batch B;
+    if (int e = make_batch(p, V, const_cast<void*>(geom), geom_bytes, const_cast<void*>(image), image_bytes,
+                           const_cast<void*>(binning), binning_bytes, true, B))
+        return e;
+    X.state = xstate_view(align256(const_cast<void*>(extra_state)), p->W, p->H, B.b.cap, nx);
+    X.state_stride = xstate_view_bytes(p->W, p->H, B.b.cap, nx);
+    if (extra_state_bytes < (size_t)V * X.state_stride + 256)
+        return fail(GSR_ERR_CAPACITY, "[gsr] extra-state block too small for this binning arena");
+    // dL/d extra values are accumulated with atomics, views that share an array into the same rows: clear the output first
+    const size_t n_out = extra_per_view == 0 ? (size_t)p->P * nx : extra_per_view == 1 ? (size_t)V * p->P * nx : (size_t)(1 + V) * p->P * 4;
+    ExtraGrads XG{dL_dextra, dL_dextra_values, extra_per_view == 2 ? dL_dextra_values + (size_t)p->P * 4 : nullptr};
+    const Launch L{(hipStream_t)stream, p->debug};
+    const int res = sorted_buffer(tile_count(p));
+    {
+        ProfScope ps("bwd_items", L.stream);
+        if (hipMemsetAsync(dL_dextra_values, 0, n_out * sizeof(float), L.stream) != hipSuccess)
+            return fail(GSR_ERR_HIP, "[gsr] memset failed: %s", hipGetErrorString(hipGetLastError()));
+        if (int e = launch_bwd_items(L, B, tile_count(p), p->P)) return e;
+    }
+    {
+        ProfScope ps("render_backward", L.stream);
+        if (int e = launch_render_backward(L, *p, B, B.b.val[res], dL_dpix, &X, &XG)) return e;
     }
     {
         ProfScope ps("preprocess_backward", L.stream);

@@ -261,6 +261,28 @@ inline int64_t bin_capacity_from_bytes(size_t bytes)
     return lo;
 }
 
+// Extra-channel state of a forward the channels backward may follow (gsr_forward_batch_channels_train; caller-owned, one block per
+// view at a fixed stride, next to nothing else): what ckpt / accum are for the colour, for the NX extra channels.
+//   accum [NX][N]   the extra channels accumulated by the forward render, without the background term (quadrants that crossed a
+//                   slice boundary only, like ImageView::accum)
+//   ckpt  [((cap >> BWD_CHUNK_SHIFT_MIN) + 2) * (NX / 4) * 256] float4: the accumulated extras per pixel at the slice boundaries,
+//                   slot-major like BinView::ckpt, then quad of channels, then pixel (q * 64 + lane)
+struct XStateView {
+    float* accum;
+    float4* ckpt;
+    size_t bytes;
+};
+inline XStateView xstate_view(void* base, int W, int H, int64_t cap, int nx)
+{
+    XStateView x;
+    char* cur = reinterpret_cast<char*>(base);
+    const size_t N = (size_t)W * (size_t)H, r = (size_t)(cap > 0 ? cap : 1);
+    carve(cur, x.accum, (size_t)nx * (N ? N : 1));
+    carve(cur, x.ckpt, ((r >> BWD_CHUNK_SHIFT_MIN) + 2) * (size_t)(nx / 4) * 256);
+    x.bytes = (size_t)(cur - reinterpret_cast<char*>(base));
+    return x;
+}
+
 inline ImageView image_view(void* base, int W, int H)
 {
     ImageView v;
@@ -397,10 +419,21 @@ struct ExtraChannels {
     size_t view_stride;       // floats between consecutive views' value arrays (0: one array shared by the views)
     const float* values_hi = nullptr;   // nx = 8, split layout: channels 4..7 as [V][P][4], channels 0..3 in `values` as [P][4] shared
     size_t hi_view_stride = 0;
+    XStateView state{nullptr, nullptr, 0};   // view 0's extra-channel saves for the backward (forward with need_backward), or NULLs
+    size_t state_stride = 0;
+};
+// The channels backward: the forward's ExtraChannels plus dL/d out_extra and where dL/d values go.  Gradients are accumulated with
+// atomics straight into the caller's output (cleared by the host first), in the layout of `values` / `values_hi`: views that share
+// an array add into the same [P][...] rows.
+struct ExtraGrads {
+    const float* dL_dextra;   // [V][nx][H][W]
+    float* grad;              // like values: [P][nx] / [V][P][nx] (view_stride) / split: [P][4] ...
+    float* grad_hi;           // ... and [V][P][4] (hi_view_stride)
 };
 int launch_render_forward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, float* out_color,
                           bool with_ckpt, const ExtraChannels* X = nullptr);
-int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, const float* dL_dpix);
+int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, const float* dL_dpix,
+                           const ExtraChannels* X = nullptr, const ExtraGrads* XG = nullptr);
 int backward_subquadrant_moments(int set);   // render_bwd.hip: set >= 0 stores; 1 = moments about the sub-quadrant centres
 int forward_half_views(int set);   // render_fwd.hip: set >= 0 stores; returns the views per submission up to which the half-quadrant forward runs
 int selftest_mm(hipStream_t stream, float* d_scratch256);   // the matrix-core pixel contraction of the render backward

@@ -378,6 +378,22 @@ struct RenderBwdArgs {
     size_t g_stride, b_stride, iv_stride, gr_stride;
 };
 
+// The extra channels of a channels backward (k_render_backward<MODE, NX>): the forward's values and factors, its saves
+// (common.hpp XStateView), dL/d out_extra, and where dL/d values goes (same layout as the values; atomics into a cleared output).
+struct RenderBwdX {
+    const float* extra;        // [P][NX] (shared, vstride 0) or [V][P][NX]; split: channels 0..3 as [P][4]
+    const float* extra_hi;     // split layout: channels 4..7 as [V][P][4]; NULL otherwise
+    size_t extra_vstride, extra_hi_vstride;
+    const float* extra_scale;  // [V][NX] or NULL
+    const float* bg_extra;     // [NX]
+    const float4* xckpt;       // view 0's extra-channel state (x_stride bytes per view)
+    const float* xaccum;
+    size_t x_stride;
+    const float* dL_dextra;    // [V][NX][H][W]
+    float* grad;               // layout of `extra`
+    float* grad_hi;            // layout of `extra_hi`
+};
+
 // five waves per SIMD: 96 registers, the accumulators in VGPRs.  MODE 0 fits without scratch; in MODE 2 the cold sub-quadrant path
 // spills inside itself (and eight lane constants once per wave at kernel start, reloaded only there): the hot loops and the item
 // set-up are free of scratch accesses (checked in the assembly, profiles/r06_isa_mix.txt).  A fifth wave per SIMD is worth 2.6 %.
@@ -391,11 +407,23 @@ struct RenderBwdArgs {
 #define GSR_SUBQ_M 20.f
 #endif
 constexpr float SUBQ_M = GSR_SUBQ_M;
-template <int MODE>
-__attribute__((amdgpu_waves_per_eu(5, 5)))
-__global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a)
+// The kernel body, shared by the colour backward (NX = 0: k_render_backward<MODE>) and the channels backward (NX = 4 / 8:
+// k_render_backward<MODE, NX>; every NX-dependent line below is compiled out of the colour kernels).  With NX extra channels
+// e_k = extra_k * view_scale_k composited by the forward with the colour's alphas, a (pixel, entry) pair's d = c . dL_dpixel gains
+// e . dL_dextra (the per-pixel factors view_scale_k * dL_dextra_k are held in xd), the slice's start state and the background
+// term gain the extras' share, and dL/d extra_k = view_scale_k sum_pixels alpha T dL_dextra_k is one more contraction of the
+// batch's u rows (alpha T) on the matrix cores, against the basis rows xd instead of the dL_dpixel rows.
+__device__ __forceinline__ RenderBwdX bwd_x() { return RenderBwdX{}; }
+__device__ __forceinline__ RenderBwdX bwd_x(const RenderBwdX& x) { return x; }
+// (the colour kernels take no RenderBwdX argument at all -- XS is empty -- so their kernel arguments, and with them the offsets of the
+// implicit ones, are what they were before the channels backward existed: the same machine code)
+template <int MODE, int NX, typename... XS>
+__attribute__((amdgpu_waves_per_eu(NX > 0 ? 3 : 5, NX > 0 ? 3 : 5)))
+__global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... xs)
 {
+    const RenderBwdX x = bwd_x(xs...);
     constexpr bool SUBQ = MODE == 1;
+    static_assert(NX == 0 || NX == 4 || NX == 8, "extra channels come in quads");
     // Work items are (tile, chunk of BWD_CHUNK consumed list entries), one quadrant per wave; which ones a workgroup takes: see the
     // item loop.  XCD-aware either way: workgroup b runs on XCD b % 8 (each XCD has its own L2) and the four quadrant waves of an item
     // run on one XCD at about the same time, so the item's list slice and Splat records are fetched into that L2 once instead of
@@ -411,6 +439,13 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a)
     a.splat = at_view(a.splat, a.g_stride, view);
     a.grad_rec = at_view(a.grad_rec, a.gr_stride, view);
     a.dL_dpix += (size_t)view * 3u * (size_t)a.W * (size_t)a.H;
+    // extra channels: this view's values (x_lo: channels 0..3 or all NX; x_hi: 4..7), x_nx floats per Gaussian in each
+    const bool x_split = NX > 4 && x.extra_hi != nullptr;
+    const uint32_t x_nx = x_split ? 4u : (uint32_t)NX;
+    const float* const x_lo = NX > 0 ? x.extra + (size_t)view * x.extra_vstride : nullptr;
+    const float* const x_hi = NX > 0 ? (x_split ? x.extra_hi + (size_t)view * x.extra_hi_vstride : x_lo + 4) : nullptr;
+    float* const xg_lo = NX > 0 ? x.grad + (size_t)view * x.extra_vstride : nullptr;
+    float* const xg_hi = NX > 0 ? (x_split ? x.grad_hi + (size_t)view * x.extra_hi_vstride : xg_lo + 4) : nullptr;
     const uint32_t n_items = at_view(a.item_count, a.iv_stride, view)[0];
     // From here on this view's gradient records hold sums of THIS backward: a later backward on the same arenas has to clear
     // them first (k_bwd_items reads the flag; it has finished: stream order).  Raised before anything is accumulated, so a
@@ -419,10 +454,13 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a)
     // group 16 keeps the entries of a batch that is still open when its round ends (the next round restages groups 0..15)
     __shared__ __attribute__((aligned(16))) float stage[17 * QUAD_WORDS];
     __shared__ __attribute__((aligned(16))) float mrow[16 * MM_STRIDE];   // 8 entries x {q, u} rows x 64 pixels
+    // the staged entries' extra values: group g, channel c = the four entries' values at 4 (NX g + c)
+    __shared__ __attribute__((aligned(16))) float stage_x[NX > 0 ? 16 * 4 * NX : 4];
 #ifdef GSR_BWD_EMUL
     __shared__ float dpx_raster[3 * 64];
 #endif
     float am[16];                                                          // A operands of the 16 K steps (basis)
+    float amx[NX > 0 ? 16 : 1];                                            // the same for the extras' contraction (rows xd)
     mm_basis<SUBQ>(am, threadIdx.x);
     const uint32_t mm_p = mm_pos(threadIdx.x);                              // this lane's pixel in a row
     // what this lane does with its four accumulator values after a batch's contraction (see mm_basis): g < 3 on q columns,
@@ -507,8 +545,44 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a)
     bg_dot_dpixel += a.bg[0] * dpx0;
     bg_dot_dpixel += a.bg[1] * dpx1;
     bg_dot_dpixel += a.bg[2] * dpx2;
+    float xd[NX > 0 ? NX : 1];   // view_scale_k * dL_dextra_k of this pixel
+    float behind_x = 0.f;        // the extras' share of the slice's start state (see below)
+    if constexpr (NX > 0) {
+        const float* dxp = x.dL_dextra + (size_t)view * NX * N + pix;
+        float graw[NX];
+#pragma unroll
+        for (int k = 0; k < NX; k++) {
+            graw[k] = inside ? dxp[(size_t)k * N] : 0.f;
+            bg_dot_dpixel += x.bg_extra[k] * graw[k];
+            xd[k] = x.extra_scale != nullptr ? x.extra_scale[(size_t)view * NX + k] * graw[k] : graw[k];
+        }
+        if (!last_chunk && last_contributor > (uint32_t)hi0) {
+            const size_t slot = (size_t)(range.x >> a.chunk_shift) + (size_t)(hi0 >> a.chunk_shift);
+            const float4* xck = at_view(x.xckpt, x.x_stride, view) + slot * (NX / 4) * 256 + q * 64 + lane;
+            const float* xac = at_view(x.xaccum, x.x_stride, view) + pix;
+#pragma unroll
+            for (int j = 0; j < NX / 4; j++) {
+                const float4 c = xck[j * 256];
+                behind_x += (xac[(size_t)(4 * j) * N] - c.x) * graw[4 * j] + (xac[(size_t)(4 * j + 1) * N] - c.y) * graw[4 * j + 1] +
+                            (xac[(size_t)(4 * j + 2) * N] - c.z) * graw[4 * j + 2] + (xac[(size_t)(4 * j + 3) * N] - c.w) * graw[4 * j + 3];
+            }
+        }
+    }
     const float neg_tfb = -T_final * bg_dot_dpixel;   // the background term of dL_dalpha, times 1 / (1 - alpha) per entry
     mrow[mm_p] = dpx0; mrow[MM_STRIDE + mm_p] = dpx1; mrow[2 * MM_STRIDE + mm_p] = dpx2;
+    if constexpr (NX > 0) {
+        // rows 3 .. 3 + NX - 1: xd, the basis rows of the extras' contraction (lane row i < NX takes channel i; the others are 0)
+#pragma unroll
+        for (int k = 0; k < NX; k++) mrow[(3 + k) * MM_STRIDE + mm_p] = xd[k];
+        const uint32_t i = lane & 15u, kq = lane >> 4;
+        const f32x4* src = (const f32x4*)(mrow + (3u + (i < (uint32_t)NX ? i : 0u)) * MM_STRIDE + 4u * kq);
+#pragma unroll
+        for (int m = 0; m < 4; m++) {
+            const f32x4 t = src[4 * m];
+            amx[4 * m + 0] = i < (uint32_t)NX ? t.x : 0.f; amx[4 * m + 1] = i < (uint32_t)NX ? t.y : 0.f;
+            amx[4 * m + 2] = i < (uint32_t)NX ? t.z : 0.f; amx[4 * m + 3] = i < (uint32_t)NX ? t.w : 0.f;
+        }
+    }
     mm_basis_dpx(am, mrow, lane);
 #ifdef GSR_BWD_EMUL
     dpx_raster[lane] = dpx0; dpx_raster[64 + lane] = dpx1; dpx_raster[128 + lane] = dpx2;
@@ -524,6 +598,10 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a)
     // opacity is set to 0 every round, which is what keeps them from ever hitting)
 #pragma unroll
     for (int i = 0; i < 16 * QUAD_WORDS / 64; i++) stage[i * 64 + lane] = 0.f;
+    if constexpr (NX > 0) {
+#pragma unroll
+        for (int i = 0; i < NX; i++) stage_x[i * 64 + lane] = 0.f;
+    }
 
     // Per-pixel state at the back end of the slice.  A pixel whose last contributor lies inside (or before) the slice
     // starts from its final state exactly like the reference; a pixel that also consumed entries behind the slice
@@ -537,7 +615,8 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a)
         const size_t slot = (size_t)(range.x >> a.chunk_shift) + (size_t)(hi0 >> a.chunk_shift);
         const float4 ck = a.ckpt[slot * 256 + q * 64 + lane];
         T = ck.x;
-        const float behind = (a.accum[pix] - ck.y) * dpx0 + (a.accum[N + pix] - ck.z) * dpx1 + (a.accum[2 * N + pix] - ck.w) * dpx2;
+        float behind = (a.accum[pix] - ck.y) * dpx0 + (a.accum[N + pix] - ck.z) * dpx1 + (a.accum[2 * N + pix] - ck.w) * dpx2;
+        if constexpr (NX > 0) behind += behind_x;
         s_rec = behind / ck.x;
     }
 
@@ -546,6 +625,7 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a)
     // the ballot is the entry nearest the back.  Lanes whose f would fall before the slice re-read entry lo and are masked.
     f32x4 c0, c1, n0, n1;
     float c2b, n2b;  // blue
+    f32x4 cx0 = {0.f, 0.f, 0.f, 0.f}, cx1 = cx0, nx0 = cx0, nx1 = cx0;   // extra channels of the entry
     uint32_t id_cur, id_nxt, id_nn;
     {
         const int f0 = hi0 - 1 - (int)lane, f1 = hi0 - 65 - (int)lane;
@@ -556,7 +636,13 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a)
         bw_prefetch16(c0, &sp->q0);
         bw_prefetch16(c1, &sp->q1);
         bw_prefetch4f(c2b, &sp->q2);
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(c0), "+v"(c1), "+v"(c2b)::"memory");
+        if constexpr (NX > 0) {
+            bw_prefetch16(cx0, x_lo + (size_t)id_cur * x_nx);
+            if (NX > 4) bw_prefetch16(cx1, x_hi + (size_t)id_cur * x_nx);
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(c0), "+v"(c1), "+v"(c2b), "+v"(cx0), "+v"(cx1)::"memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(c0), "+v"(c1), "+v"(c2b)::"memory");
+        }
     }
 #ifdef GSR_STATS
     { BW_T(ti1); tw_setup += ti1 - ti0; }
@@ -573,6 +659,10 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a)
             bw_prefetch16(n0, &sp->q0);
             bw_prefetch16(n1, &sp->q1);
             bw_prefetch4f(n2b, &sp->q2);
+            if constexpr (NX > 0) {
+                bw_prefetch16(nx0, x_lo + (size_t)id_nxt * x_nx);
+                if (NX > 4) bw_prefetch16(nx1, x_hi + (size_t)id_nxt * x_nx);
+            }
             const int f2 = hi - 129 - (int)lane;
             bw_prefetch4(id_nn, plist + (f2 >= lo ? f2 : lo));
         }
@@ -604,6 +694,11 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a)
                     id_st |= mq > SUBQ_M ? 0x80000000u : 0u;
                 }
                 p[24] = c1.z; p[28] = c1.w; p[32] = c2b; p[36] = __builtin_bit_cast(float, id_st);
+                if constexpr (NX > 0) {
+                    float* px_ = stage_x + (slot >> 2) * (4 * NX) + (slot & 3u);
+                    px_[0] = cx0.x; px_[4] = cx0.y; px_[8] = cx0.z; px_[12] = cx0.w;
+                    if (NX > 4) { px_[16] = cx1.x; px_[20] = cx1.y; px_[24] = cx1.z; px_[28] = cx1.w; }
+                }
             }
         }
         BWD_STAT(0, 1);
@@ -632,6 +727,19 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a)
                     er[k] = R4[k]; eg[k] = G4[k]; eb[k] = Bl[k];
                 }
                 quad++;
+            }
+            // e . (view_scale * dL_dextra) of the group's four entries at this pixel
+            float xdot[NX > 0 ? BGRP : 1];
+            if constexpr (NX > 0) {
+                const f32x4* px_ = (const f32x4*)(stage_x + (quad - 1) * (4 * NX));
+#pragma unroll
+                for (int k = 0; k < BGRP; k++) xdot[k] = 0.f;
+#pragma unroll
+                for (int c = 0; c < NX; c++) {
+                    const f32x4 v = px_[c];
+#pragma unroll
+                    for (int k = 0; k < BGRP; k++) xdot[k] = __builtin_fmaf(v[k], xd[c], xdot[k]);
+                }
             }
 #pragma unroll
             for (int k = 0; k < BGRP; k++) {
@@ -714,7 +822,8 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a)
                 float dL_dalpha = (d - sn) * Tn;
                 dL_dalpha = dL_dalpha + (-T_final * rcp) * bg_dot_dpixel;
 #else
-                const float d = __builtin_fmaf(eb[k], dpx2, __builtin_fmaf(eg[k], dpx1, er[k] * dpx0));
+                float d = __builtin_fmaf(eb[k], dpx2, __builtin_fmaf(eg[k], dpx1, er[k] * dpx0));
+                if constexpr (NX > 0) d += xdot[k];
                 const float sn = __builtin_fmaf(last_alpha, last_d - s_rec, s_rec);  // la*last_d + (1-la)*s
                 float dL_dalpha = (d - sn) * Tn;
                 dL_dalpha = __builtin_fmaf(neg_tfb, rcp, dL_dalpha);   // (-T_final / (1 - alpha)) * bg . dL_dpixel
@@ -837,6 +946,17 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a)
             vB = dpp_mov<0x128, 0x8, 0x2>(vB, o3);         // row 3 bank 1: colour b of lane + 8
             if (mm_onA && vA != 0.f) atomicAdd(a.grad_rec + (size_t)idA * GRAD_REC_WORDS + mm_cA, vA);
             if (mm_onB && nb == 2u && vB != 0.f) atomicAdd(a.grad_rec + (size_t)idB * GRAD_REC_WORDS + mm_cB, vB);
+            if constexpr (NX > 0) {
+                // dL/d extra: D[i][j] = sum_p xd_i(p) u_j(p); lane (g, column j >= 8) holds channels 4 g .. 4 g + 3 of batch entry j - 8
+                const f32x4 accx = mm_contract(mrow, amx, lane, hit_blocks);
+                if (mm_j >= 8u && mm_g < (uint32_t)(NX / 4) && (mm_gb == 0u || nb == 2u)) {
+                    const uint32_t id = mm_gb ? idB : idA;
+                    float* dst = (mm_g == 0u ? xg_lo : xg_hi) + (size_t)id * x_nx;
+#pragma unroll
+                    for (int r = 0; r < 4; r++)
+                        if (accx[r] != 0.f) atomicAdd(dst + r, accx[r]);
+                }
+            }
             nb = 0;
           }
           if (!more) break;
@@ -850,11 +970,13 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a)
         BW_T(tr2);
         tw_eval += tr2 - tr1;
 #endif
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(n0), "+v"(n1), "+v"(n2b), "+v"(id_nn)::"memory");
+        if constexpr (NX > 0) asm volatile("s_waitcnt vmcnt(0)" : "+v"(n0), "+v"(n1), "+v"(n2b), "+v"(id_nn), "+v"(nx0), "+v"(nx1)::"memory");
+        else asm volatile("s_waitcnt vmcnt(0)" : "+v"(n0), "+v"(n1), "+v"(n2b), "+v"(id_nn)::"memory");
 #ifdef GSR_STATS
         { BW_T(tr3); tw_wait += tr3 - tr2; }
 #endif
         c0 = n0; c1 = n1; c2b = n2b;
+        if constexpr (NX > 0) { cx0 = nx0; cx1 = nx1; }
         id_cur = id_nxt;
         id_nxt = id_nn;
     }
@@ -868,6 +990,7 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a)
     }
 #endif
 }
+
 
 #ifdef GSR_STATS
 int debug_bwd_stats(unsigned long long* out8, int reset)
@@ -898,7 +1021,8 @@ int backward_subquadrant_moments(int set)
     return v;
 }
 
-int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, const float* dL_dpix)
+int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, const float* dL_dpix,
+                           const ExtraChannels* X, const ExtraGrads* XG)
 {
     RenderBwdArgs a;
     a.ranges = B.iv.ranges;
@@ -935,10 +1059,26 @@ int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B,
     if (a.dynamic) groups = div_up((int64_t)cus * 4 * 5 * 2, 32 * (int64_t)B.V);
     if (groups < 8) groups = 8;
     const dim3 grid((unsigned)(groups * B.V) * 32u);
+    if (X != nullptr && X->nx > 0) {
+        RenderBwdX x;
+        x.extra = X->values; x.extra_hi = X->values_hi; x.extra_vstride = X->view_stride; x.extra_hi_vstride = X->hi_view_stride;
+        x.extra_scale = X->view_scale; x.bg_extra = X->bg;
+        x.xckpt = X->state.ckpt; x.xaccum = X->state.accum; x.x_stride = X->state_stride;
+        x.dL_dextra = XG->dL_dextra; x.grad = XG->grad; x.grad_hi = XG->grad_hi;
+        const int mode = backward_subquadrant_moments(-1);
+#define GSR_LAUNCH_BWD_X(M_, NX_) hipLaunchKernelGGL((k_render_backward<M_, NX_, RenderBwdX>), grid, dim3(64), 0, L.stream, a, x)
+        if (X->nx == 4) {
+            if (mode == 1) GSR_LAUNCH_BWD_X(1, 4); else if (mode == 2) GSR_LAUNCH_BWD_X(2, 4); else GSR_LAUNCH_BWD_X(0, 4);
+        } else {
+            if (mode == 1) GSR_LAUNCH_BWD_X(1, 8); else if (mode == 2) GSR_LAUNCH_BWD_X(2, 8); else GSR_LAUNCH_BWD_X(0, 8);
+        }
+#undef GSR_LAUNCH_BWD_X
+        return check_launch(L, "render_backward_channels");
+    }
     switch (backward_subquadrant_moments(-1)) {
-    case 1: hipLaunchKernelGGL(k_render_backward<1>, grid, dim3(64), 0, L.stream, a); break;
-    case 2: hipLaunchKernelGGL(k_render_backward<2>, grid, dim3(64), 0, L.stream, a); break;
-    default: hipLaunchKernelGGL(k_render_backward<0>, grid, dim3(64), 0, L.stream, a); break;
+    case 1: hipLaunchKernelGGL((k_render_backward<1, 0>), grid, dim3(64), 0, L.stream, a); break;
+    case 2: hipLaunchKernelGGL((k_render_backward<2, 0>), grid, dim3(64), 0, L.stream, a); break;
+    default: hipLaunchKernelGGL((k_render_backward<0, 0>), grid, dim3(64), 0, L.stream, a); break;
     }
     return check_launch(L, "render_backward");
 }

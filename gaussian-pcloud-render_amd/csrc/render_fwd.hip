@@ -59,6 +59,11 @@ struct RenderArgs {
     const float* extra_scale;  // [V][NX] per-view factors applied to them (NULL: 1), e.g. the +-1 of view-dependent normals
     const float* bg_extra;     // [NX]
     float* out_extra;          // [V][NX][H][W]
+    // with ckpt (need_backward) and an extra-state block (gsr_forward_batch_channels_train): the extras' share of the backward's
+    // saves -- ckpt's companion and accum's (common.hpp XStateView), x_stride bytes between the views' blocks; else NULL
+    float4* xckpt;
+    float* xaccum;
+    size_t x_stride;
 };
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -252,6 +257,7 @@ __global__ __launch_bounds__(64) void k_render_forward(RenderArgs a)
     a.splat = at_view(a.splat, a.g_stride, view);
     a.out_color += (size_t)view * 3u * (size_t)a.W * (size_t)a.H;
     if (NX > 0) a.extra += (size_t)view * a.extra_vstride;
+    float4* const xckpt = NX > 0 && a.xckpt != nullptr ? at_view(a.xckpt, a.x_stride, view) : nullptr;
     // split layout: a Gaussian's first quad is extra[4 id], its second extra_hi[4 (view P + id)] (both 16-B records)
     const bool x_split = NX > 4 && a.extra_hi != nullptr;
     const float* const x_hi = x_split ? a.extra_hi + (size_t)view * a.extra_hi_vstride : a.extra + 4;
@@ -345,6 +351,11 @@ __global__ __launch_bounds__(64) void k_render_forward(RenderArgs a)
             if (a.ckpt != nullptr && base != 0 && (base & ((1 << a.chunk_shift) - 1)) == 0 && (base >> a.chunk_shift) < BWD_MAX_CHUNKS) {
                 const size_t slot = (size_t)(range.x >> a.chunk_shift) + (size_t)(base >> a.chunk_shift);
                 a.ckpt[slot * 256 + q * 64 + lane] = make_float4(T, C01.x, C01.y, C2);
+                if (NX > 0 && xckpt != nullptr) {
+#pragma unroll
+                    for (int j = 0; j < NX / 4; j++)
+                        xckpt[(slot * (NX / 4) + j) * 256 + q * 64 + lane] = make_float4(CX[2 * j].x, CX[2 * j].y, CX[2 * j + 1].x, CX[2 * j + 1].y);
+                }
                 crossed = true;
             }
 
@@ -537,6 +548,14 @@ __global__ __launch_bounds__(64) void k_render_forward(RenderArgs a)
             a.accum[pix] = C01.x;
             a.accum[N + pix] = C01.y;
             a.accum[2 * N + pix] = C2;
+            if (NX > 0 && xckpt != nullptr) {
+                float* xa = at_view(a.xaccum, a.x_stride, view) + pix;
+#pragma unroll
+                for (int j = 0; j < NX / 2; j++) {
+                    xa[(size_t)(2 * j) * N] = CX[j].x;
+                    xa[(size_t)(2 * j + 1) * N] = CX[j].y;
+                }
+            }
         }
     }
 }
@@ -863,10 +882,14 @@ int launch_render_forward(const Launch& L, const gsr_params& p, const Batch& B, 
     // tile_need was cleared at the start of the frame (k_preprocess; the host on a retry / re-render)
     a.extra = nullptr; a.extra_scale = nullptr; a.bg_extra = nullptr; a.out_extra = nullptr; a.extra_vstride = 0;
     a.extra_hi = nullptr; a.extra_hi_vstride = 0;
+    a.xckpt = nullptr; a.xaccum = nullptr; a.x_stride = 0;
     const dim3 grid((unsigned)div_up(T, 8) * 32u * (unsigned)B.V);
     if (X != nullptr && X->nx > 0) {
         a.extra = X->values; a.extra_scale = X->view_scale; a.bg_extra = X->bg; a.out_extra = X->out; a.extra_vstride = X->view_stride;
         a.extra_hi = X->values_hi; a.extra_hi_vstride = X->hi_view_stride;
+        if (with_ckpt && X->state.ckpt != nullptr) {
+            a.xckpt = X->state.ckpt; a.xaccum = X->state.accum; a.x_stride = X->state_stride;
+        }
         if (X->nx == 4) hipLaunchKernelGGL(k_render_forward<4>, grid, dim3(64), 0, L.stream, a);
         else hipLaunchKernelGGL(k_render_forward<8>, grid, dim3(64), 0, L.stream, a);
     } else if (B.V <= forward_half_views(-1)) {

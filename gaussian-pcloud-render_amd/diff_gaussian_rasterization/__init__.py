@@ -324,3 +324,104 @@ def rasterize_views(means3D, means2D, opacities, settings_list, shs=None, colors
         means3D, means2D, e if shs is None else shs, e if colors_precomp is None else colors_precomp, opacities,
         e if scales is None else scales, e if rotations is None else rotations, e if cov3D_precomp is None else cov3D_precomp,
         list(settings_list))
+
+
+class _RasterizeGaussiansViewsChannels(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, extra, extra_hi, bg_extra,
+                extra_view_scale, settings_list, nx_user):
+        rs = settings_list[0]
+        view, proj, cam = _stack_views(settings_list, means3D.device)
+        need_backward = any(ctx.needs_input_grad)
+        values = (extra, extra_hi) if extra_hi.numel() != 0 else extra
+        xs = None if extra_view_scale.numel() == 0 else extra_view_scale
+        counts, color, radii, geomBuffer, binningBuffer, imgBuffer, out_extra = _C.rasterize_gaussians_batch(
+            rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj,
+            rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree, cam, rs.prefiltered,
+            any(s.debug for s in settings_list), need_backward=need_backward, extra=(values, xs, bg_extra))
+        ctx.raster_settings = rs
+        ctx.opacity_shape = tuple(opacities.shape)
+        ctx.nx_user = nx_user
+        ctx.xstate = _C.extra_state(geomBuffer)
+        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
+                              imgBuffer, view, proj, cam, extra, extra_hi, bg_extra, extra_view_scale)
+        ctx.mark_non_differentiable(radii)
+        return color, radii, out_extra[:, :nx_user]
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _, grad_out_extra):
+        rs = ctx.raster_settings
+        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer, view, proj,
+         cam, extra, extra_hi, bg_extra, extra_view_scale) = ctx.saved_tensors
+        split = extra_hi.numel() != 0
+        nx = 8 if split else extra.shape[-1]
+        V = grad_out_color.shape[0]
+        if grad_out_extra.shape[1] != nx:   # (channels padded by rasterize_views_channels get no gradient to pass on)
+            grad_out_extra = torch.cat([grad_out_extra, grad_out_extra.new_zeros((V, nx - grad_out_extra.shape[1]) +
+                                                                                 tuple(grad_out_extra.shape[2:]))], 1)
+        values = (extra, extra_hi) if split else extra
+        xs = None if extra_view_scale.numel() == 0 else extra_view_scale
+        g = _C.rasterize_gaussians_backward_channels_batch(
+            rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj, rs.tanfovx,
+            rs.tanfovy, grad_out_color, sh, rs.sh_degree, cam, geomBuffer, binningBuffer, imgBuffer, rs.debug,
+            (values, xs, bg_extra), grad_out_extra, state=ctx.xstate)
+        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
+         grad_rotations, grad_x) = g
+        g_lo, g_hi = grad_x if split else (grad_x, None)
+
+        def fit(g, inp):
+            return g if inp.numel() != 0 else None
+
+        return (grad_means3D, grad_means2D, fit(grad_sh, sh), fit(grad_colors_precomp, colors_precomp),
+                grad_opacities.reshape(ctx.opacity_shape), fit(grad_scales, scales), fit(grad_rotations, rotations),
+                fit(grad_cov3Ds_precomp, cov3Ds_precomp), g_lo, g_hi, None, None, None, None)
+
+
+def rasterize_views_channels(means3D, means2D, opacities, settings_list, extra, bg_extra, extra_view_scale=None, shs=None,
+                             colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None):
+    """rasterize_views that also composites extra per-Gaussian channels with the colour's alphas, differentiably (C ABI
+    gsr_forward_batch_channels_train / gsr_backward_batch_channels).  Returns (colors [V,3,H,W], radii [V,P],
+    extra_images [V,nx,H,W]): extra_images[v][k] = sum_i extra[i][k] * extra_view_scale[v][k] * alpha_i T_i + T_final bg_extra[k],
+    what a rasterize_views call with those values as colors_precomp and bg_extra as background renders.
+    extra: [P,nx] shared by the views, [V,P,nx] one array per view, or the pair ([P,4], [V,P,4]) (channels 0..3 shared, 4..7 per
+    view); nx = 1..8 (padded to 4 / 8 with zero channels).  bg_extra [nx]; extra_view_scale [V,nx] or None.  Gradients flow to
+    `extra` as to every input rasterize_views differentiates; bg_extra and extra_view_scale get none (like the background)."""
+    if len(settings_list) == 0:
+        raise Exception("rasterize_views_channels: empty settings list")
+    if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
+        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or (
+            (scales is not None or rotations is not None) and cov3D_precomp is not None):
+        raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+    V, P = len(settings_list), means3D.shape[0]
+    e = _ABSENT
+    dev = means3D.device
+    if isinstance(extra, (tuple, list)):
+        lo, hi = extra
+        if tuple(lo.shape) != (P, 4) or tuple(hi.shape) != (V, P, 4):
+            raise Exception("rasterize_views_channels: split extra channels must have shapes (P, 4) and (V, P, 4)")
+        nx_user, nx = 8, 8
+    else:
+        lo, hi = extra, e
+        if lo.dim() not in (2, 3) or lo.shape[-2] != P or (lo.dim() == 3 and lo.shape[0] != V) or not 1 <= lo.shape[-1] <= 8:
+            raise Exception("rasterize_views_channels: extra must have shape (P, nx) or (V, P, nx) with nx in 1..8")
+        nx_user = int(lo.shape[-1])
+        nx = 4 if nx_user <= 4 else 8
+        if nx != nx_user:   # zero channels up to a quad (torch ops: the gradient is sliced back by autograd)
+            lo = torch.cat([lo, lo.new_zeros(tuple(lo.shape[:-1]) + (nx - nx_user,))], -1)
+    bg_extra = bg_extra.detach().reshape(-1).to(device=dev, dtype=torch.float32)
+    if bg_extra.numel() != nx_user:
+        raise Exception("rasterize_views_channels: bg_extra must have one value per extra channel")
+    if nx != nx_user:
+        bg_extra = torch.cat([bg_extra, bg_extra.new_zeros(nx - nx_user)])
+    if extra_view_scale is None:
+        xs = e
+    else:
+        xs = extra_view_scale.detach().to(device=dev, dtype=torch.float32).reshape(V, nx_user)
+        if nx != nx_user:
+            xs = torch.cat([xs, xs.new_ones((V, nx - nx_user))], 1)
+        xs = xs.contiguous()
+    return _RasterizeGaussiansViewsChannels.apply(
+        means3D, means2D, e if shs is None else shs, e if colors_precomp is None else colors_precomp, opacities,
+        e if scales is None else scales, e if rotations is None else rotations, e if cov3D_precomp is None else cov3D_precomp,
+        lo.contiguous(), hi if hi is e else hi.contiguous(), bg_extra.contiguous(), xs, list(settings_list), nx_user)

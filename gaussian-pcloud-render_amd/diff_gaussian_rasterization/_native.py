@@ -35,7 +35,8 @@ SYMBOLS = ("gsr_geom_bytes", "gsr_geom_bytes_inference", "gsr_image_bytes", "gsr
            "gsr_forward_stage2", "gsr_backward_batch", "gsr_backward", "gsr_mark_visible", "gsr_query", "gsr_set_profiling",
            "gsr_get_profile", "gsr_last_error", "gsr_version", "gsr_selftest", "gsr_forward_recolor", "gsr_forward_batch_channels", "gsr_d2h_count",
            "gsr_clock_probe_launch", "gsr_wall_clock_khz", "gsr_last_list_pairs", "gsr_set_forward_half_views",
-           "gsr_set_backward_moments", "gsr_set_sort_mode")
+           "gsr_set_backward_moments", "gsr_set_sort_mode", "gsr_extra_state_bytes", "gsr_forward_batch_channels_train",
+           "gsr_backward_batch_channels")
 
 GSR_RETRY = 1
 
@@ -63,6 +64,13 @@ def _load():
     lib.gsr_forward_batch_channels.restype = C.c_int
     lib.gsr_forward_batch_channels.argtypes = [C.POINTER(GsrParams), C.c_int, _fp, C.c_size_t, _fp, C.c_size_t, _fp, C.c_size_t,
                                                _fp, _fp, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]
+    lib.gsr_forward_batch_channels_train.restype = C.c_int
+    lib.gsr_forward_batch_channels_train.argtypes = lib.gsr_forward_batch_channels.argtypes[:-1] + [_fp, C.c_size_t, _fp]
+    lib.gsr_extra_state_bytes.restype = C.c_size_t
+    lib.gsr_extra_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int]
+    lib.gsr_backward_batch_channels.restype = C.c_int
+    lib.gsr_backward_batch_channels.argtypes = ([C.POINTER(GsrParams), C.c_int, _fp, _fp, C.c_size_t, _fp, C.c_size_t, _fp, C.c_size_t]
+                                                + [_fp] * 9 + [C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_size_t, _fp, _fp, _fp])
     lib.gsr_forward_stage1.restype = C.c_int
     lib.gsr_forward_stage1.argtypes = [C.POINTER(GsrParams), _fp, C.c_size_t, _fp, C.c_size_t, _fp,
                                        C.POINTER(C.c_int64), _fp]
@@ -414,7 +422,8 @@ def rasterize_gaussians_batch(background, means3D, colors, opacity, scales, rota
     extra = (values [P,nx] shared by the views or [V,P,nx] per view -- or the pair ([P,4] shared, [V,P,4] per view) for eight channels
     of which only the last four depend on the view --, view_scale [V,nx] or None, bg [nx]) with nx in (4, 8): the
     render also composites those channels with the colour's alphas (gsr_forward_batch_channels) and the result gains a 7th
-    element, out_extra [V,nx,H,W]."""
+    element, out_extra [V,nx,H,W].  With need_backward the call also saves what rasterize_gaussians_backward_channels_batch needs
+    (gsr_forward_batch_channels_train): a caller-owned extra-state block, kept with the geometry arena (extra_state(geomBuffer))."""
     if means3D.dim() != 2 or means3D.shape[1] != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     device = means3D.device
@@ -479,6 +488,7 @@ def rasterize_gaussians_batch(background, means3D, colors, opacity, scales, rota
         if capacity is None:
             hint = _CAP_HINT.get(key)
             capacity = None if hint is None else int(hint * CAP_SLACK) + 4096
+        xstate = [None]
         if capacity is None and V == 1 and not nx:
             # first frame of this configuration: count, then bind (one host round trip, like the reference)
             _check(lib.gsr_forward_stage1(C.byref(p), geom.data_ptr(), geom.numel(), img.data_ptr(), img.numel(),
@@ -490,6 +500,15 @@ def rasterize_gaussians_batch(background, means3D, colors, opacity, scales, rota
             if capacity is None:
                 capacity = 16 * P      # first batch of this configuration: a guess, corrected by the retry below
             def submit(binning, resume):
+                if nx and need_backward:
+                    # the extra-state block is sized with the binning arena (both grow on a retry)
+                    n = int(capacity) if not resume else need_pairs[0]
+                    xstate[0] = torch.empty((V * lib.gsr_extra_state_bytes(W, H, n, nx) + 256,), **byte)
+                    return lib.gsr_forward_batch_channels_train(
+                        C.byref(p), V, geom.data_ptr(), geom.numel(), img.data_ptr(), img.numel(), binning.data_ptr(),
+                        binning.numel(), radii.data_ptr(), out_color.data_ptr(), counts, resume, nx, x_per_view, xv.data_ptr(),
+                        None if xs is None else xs.data_ptr(), xb.data_ptr(), out_extra.data_ptr(), xstate[0].data_ptr(),
+                        xstate[0].numel(), stream)
                 if nx:
                     return lib.gsr_forward_batch_channels(
                         C.byref(p), V, geom.data_ptr(), geom.numel(), img.data_ptr(), img.numel(), binning.data_ptr(),
@@ -499,16 +518,19 @@ def rasterize_gaussians_batch(background, means3D, colors, opacity, scales, rota
                                              binning.data_ptr(), binning.numel(), radii.data_ptr(), out_color.data_ptr(), counts,
                                              resume, stream)
 
+            need_pairs = [0]
             binning = torch.empty((V * lib.gsr_binning_bytes(int(capacity)),), **byte)
             rc = submit(binning, 0)
             if rc == GSR_RETRY:
                 pairs = (C.c_int64 * V)()
                 _check(lib.gsr_last_list_pairs(pairs, V))
-                need = int(max(pairs) * CAP_SLACK) + 4096
+                need = need_pairs[0] = int(max(pairs) * CAP_SLACK) + 4096
                 binning = torch.empty((V * lib.gsr_binning_bytes(need),), **byte)
                 rc = submit(binning, 1)
             _check(rc)
-        ov.give(out_color, radii, geom, binning, img, out_extra)
+            if xstate[0] is not None:
+                geom._gsr_extra_state = (xstate[0], nx, x_per_view)
+        ov.give(out_color, radii, geom, binning, img, out_extra, xstate[0])
         pairs = (C.c_int64 * V)()
         _check(lib.gsr_last_list_pairs(pairs, V))   # (same host thread as the forward call: the count is kept per thread)
     del keep
@@ -715,6 +737,66 @@ def rasterize_gaussians_backward_batch(background, means3D, radii, colors, scale
                                           stream))
             del keep
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+
+
+def extra_state(geomBuffer):
+    """(extra-state block, nx, extra_per_view) a channels forward with need_backward kept with its geometry arena, or None."""
+    return getattr(geomBuffer, "_gsr_extra_state", None)
+
+
+def rasterize_gaussians_backward_channels_batch(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
+                                                viewmatrices, projmatrices, tan_fovx, tan_fovy, dL_dout_color, sh, degree, camposs,
+                                                geomBuffer, binningBuffer, imageBuffer, debug, extra, dL_dout_extra, state=None):
+    """Backward of rasterize_gaussians_batch(..., extra=(values, view_scale, bg), need_backward=True) (C ABI
+    gsr_backward_batch_channels): `extra` is the forward's triple, dL_dout_extra [V,nx,H,W].  Returns the 8-tuple of
+    rasterize_gaussians_backward_batch + dL/d values in the layout of the values ([P,nx], [V,P,nx], or the pair ([P,4], [V,P,4])).
+    state: the forward's extra_state(geomBuffer) (default: looked up on geomBuffer)."""
+    device = means3D.device
+    _require_hip(device)
+    P = means3D.shape[0]
+    V, H, W = int(dL_dout_color.shape[0]), int(dL_dout_color.shape[2]), int(dL_dout_color.shape[3])
+    M = int(sh.shape[1]) if sh.numel() != 0 and sh.shape[0] != 0 else 0
+    xv, xs, xb = extra
+    split = isinstance(xv, (tuple, list))
+    nx = 8 if split else int(xv.shape[-1])
+    x_per_view = 2 if split else int(xv.dim() == 3)
+    z = dict(dtype=torch.float32, device=device)
+    has_sr = scales.numel() != 0 and P != 0
+    e_or_z = torch.empty if P != 0 else torch.zeros
+    g = [e_or_z((P, 3), **z), e_or_z((P, 3), **z), e_or_z((P, 1), **z), e_or_z((P, 3), **z), e_or_z((P, 6), **z), e_or_z((P, M, 3), **z),
+         e_or_z((P, 3), **z) if has_sr else torch.zeros((P, 3), **z), e_or_z((P, 4), **z) if has_sr else torch.zeros((P, 4), **z)]
+    n_out = P * 4 * (1 + V) if split else P * nx * (V if x_per_view else 1)
+    gx = e_or_z((n_out,), **z)
+    if P != 0:
+        st = state if state is not None else extra_state(geomBuffer)
+        if st is None:
+            raise RuntimeError("backward_channels: the forward kept no extra-channel state (a channels forward with need_backward=True)")
+        with _on_device(device):
+            stream = _stream_handle(device)
+            p, keep = _params(background, means3D, colors, means3D, scales, rotations, scale_modifier,
+                              cov3D_precomp, viewmatrices, projmatrices, tan_fovx, tan_fovy, H, W, sh, degree, camposs, False,
+                              debug, True)
+            if split:
+                xv_c = torch.cat([_f32c(xv[0], device, "extra").reshape(-1), _f32c(xv[1], device, "extra").reshape(-1)])
+            else:
+                xv_c = _f32c(xv, device, "extra")
+            xb_c = _f32c(xb.reshape(-1), device, "bg_extra")
+            xs_c = None if xs is None else _f32c(xs, device, "extra_view_scale")
+            dpix = _f32c(dL_dout_color, device, "dL_dout_color")
+            dx = _f32c(dL_dout_extra, device, "dL_dout_extra")
+            radii_c = radii.contiguous()
+            _check(lib.gsr_backward_batch_channels(
+                C.byref(p), V, radii_c.data_ptr(), geomBuffer.data_ptr(), geomBuffer.numel(), binningBuffer.data_ptr(),
+                binningBuffer.numel(), imageBuffer.data_ptr(), imageBuffer.numel(), dpix.data_ptr(), g[0].data_ptr(), g[2].data_ptr(),
+                g[1].data_ptr(), g[3].data_ptr(), g[4].data_ptr(), _ptr(g[5]), g[6].data_ptr(), g[7].data_ptr(), nx, x_per_view,
+                xv_c.data_ptr(), None if xs_c is None else xs_c.data_ptr(), xb_c.data_ptr(), st[0].data_ptr(), st[0].numel(),
+                dx.data_ptr(), gx.data_ptr(), stream))
+            del keep
+    if split:
+        gx = (gx[:P * 4].reshape(P, 4), gx[P * 4:].reshape(V, P, 4))
+    else:
+        gx = gx.reshape((V, P, nx) if x_per_view else (P, nx))
+    return tuple(g) + (gx,)
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,

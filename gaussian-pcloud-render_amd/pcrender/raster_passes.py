@@ -11,6 +11,9 @@ bilinear down-filter when super_sample_rate > 1, permute to (b, q, h, w, 3).
 xyz, SH colour, hit map, normals; :387-524) or Simple_Render.render's (:740-820), pinned call by call -- every argument of every
 rasterizer call and the post-processed results -- by tests/golden/py_rasterize_calls.npz, the trace of the reference's own code.
 
+`train_passes` is render_passes with an autograd graph (diff_gaussian_rasterization.rasterize_views_channels): the same single
+render, differentiable to the cloud, its SH colours and the normals.
+
 `render_passes` produces the same four images per view but runs the geometry (preprocess, depth sort, pair
 emission, tile sort, ranges) ONCE per view -- all views in one submission (C ABI gsr_forward_batch) -- and re-renders the
 other colours on it with diff_gaussian_rasterization._native.recolor (C ABI gsr_forward_recolor), again all views per
@@ -24,6 +27,7 @@ import torch.nn.functional as F
 
 from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
 from diff_gaussian_rasterization import rasterize_views as _rasterize_views_call
+from diff_gaussian_rasterization import rasterize_views_channels as _rasterize_views_channels
 from diff_gaussian_rasterization import _native
 
 from . import camera as _camera
@@ -210,4 +214,43 @@ def render_passes(means3D, opacities, scales, rotations, shs, H_c2w, h, w, fov, 
 
         out = {"rgb": rgb, "xyz_w": again(means3D), "hitmap": again(torch.ones_like(means3D)),
                "normal": None if nv is None else again(nv.contiguous())}
+    return {k: (None if v is None else _finish(v, 1, num_q, h, w, super_sample_rate)) for k, v in out.items()}
+
+
+def train_passes(means3D, opacities, scales, rotations, shs, H_c2w, h, w, fov, bg, scale_factor, normals=None, sh_degree=1,
+                 super_sample_rate=2):
+    """render_passes for training: the same arguments, the same dict of (1, q, h, w, 3) tensors -- bit for bit -- but with an
+    autograd graph to means3D, opacities, scales, rotations, shs and normals, like the reference's four differentiable
+    GaussianRasterizer passes (simple_raw_render.py:410-524, whose losses weight the normal, hit-map and colour images).
+
+    One render for the four passes (diff_gaussian_rasterization.rasterize_views_channels): world xyz and the hit value are
+    extra channels shared by the views, the normals turned towards each view's camera (normals_per_view) one array per view.
+    The extra values are built with torch ops, so gradients reach means3D both as a position and as the xyz colour, and the
+    normals through the per-view sign flips, exactly as in literal_passes.
+    A background whose three values differ would give the hit map and the other extra passes backgrounds of their own per channel
+    of ONE channel set; that case falls back to literal_passes (four full differentiable passes).  The reference's training
+    configuration renders on black (white_back: false)."""
+    device = means3D.device
+    num_q = H_c2w.shape[0]
+    bg_d = torch.zeros(3, device=device) if bg is None else bg.to(device)
+    bg_cpu = bg if (bg is not None and bg.device.type == "cpu") else bg_d.cpu()
+    if not float(bg_cpu[0]) == float(bg_cpu[1]) == float(bg_cpu[2]):
+        return literal_passes(means3D, opacities, scales, rotations, shs, H_c2w, h, w, fov, bg_d, scale_factor, normals=normals,
+                              sh_degree=sh_degree, super_sample_rate=super_sample_rate)
+    radius = float(np.sqrt(3) / scale_factor * 6)
+    sts = settings_for_views(H_c2w, w, h, fov, device, sh_degree=sh_degree, bg=bg_d, super_sample_rate=super_sample_rate)
+    P = means3D.shape[0]
+    lo = torch.cat([means3D, torch.ones((P, 1), dtype=torch.float32, device=device)], dim=1)                # xyz, hit: shared
+    if normals is not None:
+        nv = normals_per_view(means3D, normals, H_c2w[:, :3, 3].detach().to(device=device, dtype=torch.float32))   # [q, P, 3]
+        extra = (lo, torch.cat([nv, torch.zeros((num_q, P, 1), dtype=torch.float32, device=device)], dim=2))
+        nx = 8
+    else:
+        extra, nx = lo, 4
+    means2D = torch.zeros_like(means3D, dtype=torch.float32, requires_grad=True, device=device) + 0
+    rgb, _, ex = _rasterize_views_channels(means3D, means2D, opacities, sts, extra, bg_d[0:1].expand(nx), shs=shs,
+                                           scales=scales * radius, rotations=rotations)
+    H, W = rgb.shape[-2], rgb.shape[-1]
+    out = {"rgb": rgb, "xyz_w": ex[:, 0:3], "hitmap": ex[:, 3:4].expand(num_q, 3, H, W),
+           "normal": None if normals is None else ex[:, 4:7]}
     return {k: (None if v is None else _finish(v, 1, num_q, h, w, super_sample_rate)) for k, v in out.items()}

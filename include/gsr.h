@@ -136,6 +136,21 @@ int gsr_forward_batch_channels(const gsr_params* p, int V, void* geom, size_t ge
                                int nx, int extra_per_view, const float* extra, const float* extra_view_scale, const float* bg_extra,
                                float* out_extra, gsr_stream_t stream);
 
+/* Training with the extra channels.  gsr_forward_batch_channels_train is gsr_forward_batch_channels that, with p->need_backward = 1,
+ * also saves into the caller-owned block `extra_state` what the channels backward needs beyond the colour's saves: the extra
+ * channels accumulated per pixel at the list-slice boundaries and at the end of the walk.  Outputs are bit-identical to
+ * gsr_forward_batch_channels.  The block holds at least V * gsr_extra_state_bytes(W, H, n, nx) + 256 bytes, n being the pair count
+ * the binning arena was sized for (V * gsr_binning_bytes(n) bytes; after a GSR_RETRY both grow together and the resumed call saves
+ * into the new block); gsr_geom_bytes / gsr_image_bytes / gsr_binning_bytes are unchanged.  With need_backward = 0 the block is
+ * not touched.  The library remembers, per geometry arena, what the last forward or recolor on it saved, so that the backward can
+ * refuse a mismatch without reading anything back from the device. */
+size_t gsr_extra_state_bytes(int W, int H, int64_t num_rendered, int nx);
+int gsr_forward_batch_channels_train(const gsr_params* p, int V, void* geom, size_t geom_bytes, void* image, size_t image_bytes,
+                                     void* binning, size_t binning_bytes, int* radii, float* out_color, int64_t* num_rendered,
+                                     int resume, int nx, int extra_per_view, const float* extra, const float* extra_view_scale,
+                                     const float* bg_extra, float* out_extra, void* extra_state, size_t extra_state_bytes,
+                                     gsr_stream_t stream);
+
 /* The reference's synchronous shape for one view.  Stage 1: preprocess, depth ordering, pair counting; returns
  * num_rendered through *num_rendered_out after a device->host read-back on `stream` (cf. rasterizer_impl.cu:281).
  * out_color is not touched. */
@@ -178,6 +193,22 @@ int gsr_backward_batch(const gsr_params* p, int V, const int* radii, const void*
                        size_t binning_bytes, const void* image, size_t image_bytes, const float* dL_dpix, float* dL_dmean2D,
                        float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
                        float* dL_dscale, float* dL_drot, gsr_stream_t stream);
+
+/* Backward of gsr_forward_batch_channels_train (need_backward = 1): gsr_backward_batch's arguments and outputs -- the mean2D, conic
+ * and opacity gradients now carry the extra channels' share of dL/d alpha (d = c . dL_dpix + e . dL_dextra with
+ * e_k = extra_k * view_scale_k; background term T_final (bg . dL_dpix + bg_extra . dL_dextra)) -- plus dL_dextra [V][nx][H][W]
+ * and dL_dextra_values, dL/d extra in the layout of `extra` (extra_per_view 0: [P][nx] summed over the views; 1: [V][P][nx];
+ * 2: [P][4] summed over the views, then [V][P][4]): view_scale_k * sum over pixels of alpha T dL_dextra_k.  nx, extra_per_view,
+ * extra, extra_view_scale, bg_extra and extra_state are the forward's.  Every element of dL_dextra_values is written (the library
+ * clears it and accumulates into it); bg_extra and extra_view_scale get no gradient.  GSR_ERR_INVALID with a message when the
+ * last forward on `geom` was not a channels forward with need_backward = 1 into this extra_state, when nx or the layout differ
+ * from that forward's, or after a gsr_forward_recolor on the arenas (not supported). */
+int gsr_backward_batch_channels(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
+                                size_t binning_bytes, const void* image, size_t image_bytes, const float* dL_dpix, float* dL_dmean2D,
+                                float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                                float* dL_dscale, float* dL_drot, int nx, int extra_per_view, const float* extra,
+                                const float* extra_view_scale, const float* bg_extra, const void* extra_state, size_t extra_state_bytes,
+                                const float* dL_dextra, float* dL_dextra_values, gsr_stream_t stream);
 
 /* One view, the reference's argument shape (num_rendered is not needed: the lists' extent lives in the arenas). */
 int gsr_backward(const gsr_params* p, const int* radii, int64_t num_rendered, const void* geom, size_t geom_bytes,
