@@ -239,9 +239,9 @@ static int make_batch(const gsr_params* p, int V, void* geom, size_t geom_bytes,
     return GSR_OK;
 }
 
-// What the last forward on a geometry arena saved for the backward, kept on the host so that gsr_backward_batch_channels can refuse
-// a backward that does not match it without reading anything back from the device.  Keyed by the arena's address: every forward
-// and recolor on an arena rewrites its record.
+// What the last forward on a geometry arena saved for the backward, kept on the host so that gsr_backward_batch and
+// gsr_backward_batch_channels can refuse a backward that does not match it without reading anything back from the device.  Keyed by
+// the arena's address: every forward and recolor on an arena rewrites its record.
 struct FrameRecord {
     int kind;             // 0 colour forward, 1 channels forward, 2 recolor
     int need_backward;
@@ -249,6 +249,8 @@ struct FrameRecord {
     int V, P, W, H;
     const void* xstate;   // the extra-state block the channels forward saved into (NULL: none)
     size_t xstate_bytes;
+    int fwd_need_backward;   // need_backward of the forward whose geometry and lists the arena holds (a recolor carries it on;
+                             // -1: unknown, a recolor on an arena without a record)
 };
 static std::mutex g_frames_mu;
 static std::map<const void*, FrameRecord> g_frames;
@@ -309,7 +311,7 @@ static int forward_impl(const gsr_params* p, int V, void* geom, size_t geom_byte
         X = &Xs;
     }
     {
-        FrameRecord r{X ? 1 : 0, p->need_backward != 0, X ? X->nx : 0, 0, V, p->P, p->W, p->H, nullptr, 0};
+        FrameRecord r{X ? 1 : 0, p->need_backward != 0, X ? X->nx : 0, 0, V, p->P, p->W, p->H, nullptr, 0, p->need_backward != 0};
         if (X) {
             r.layout = X->values_hi ? 2 : X->view_stride ? 1 : 0;
             if (X->state.accum) { r.xstate = xraw; r.xstate_bytes = X->state.bytes; }
@@ -641,7 +643,13 @@ int gsr_forward_recolor(const gsr_params* p, int V, int colors_per_view, void* g
     if (!out_color || !p->bg || !binning) return fail(GSR_ERR_INVALID, "[gsr] recolor: NULL pointer");
     Batch B;
     if (int e = make_batch(p, V, geom, geom_bytes, image, image_bytes, const_cast<void*>(binning), binning_bytes, false, B)) return e;
-    note_frame(geom, FrameRecord{2, p->need_backward != 0, 0, 0, V, p->P, p->W, p->H, nullptr, 0});
+    {
+        // a need_backward recolor rewrites the colour saves only: the gradient records and the SH clamp mask of the other Gaussians
+        // exist (and were cleared) only if the forward under it had need_backward too
+        FrameRecord prev;
+        const int fwd_nb = find_frame(geom, prev) ? prev.fwd_need_backward : -1;
+        note_frame(geom, FrameRecord{2, p->need_backward != 0, 0, 0, V, p->P, p->W, p->H, nullptr, 0, fwd_nb});
+    }
     const Launch L{(hipStream_t)stream, p->debug};
     const int res = sorted_buffer(tile_count(p));
     {
@@ -672,6 +680,21 @@ int gsr_backward_batch(const gsr_params* p, int V, const int* radii, const void*
     if (p->scales && (!dL_dscale || !dL_drot)) return fail(GSR_ERR_INVALID, "[gsr] dL_dscale/dL_drot is NULL");
     if (p->scales && ((uintptr_t)dL_drot & 15u)) return fail(GSR_ERR_INVALID, "[gsr] dL_drot must be 16-byte aligned (it is written one float4 per Gaussian)");
     if (!binning) return fail(GSR_ERR_INVALID, "[gsr] binning arena is NULL");
+    // the forward or recolor this backward differentiates has to have saved what it reads, for the same views and sizes.  Without a
+    // record (an arena whose forward ran before the record table was last dropped, at more than 4096 arenas) the call goes ahead as
+    // it always did: refusing it would break a valid backward, and the caller's contract (gsr.h) is unchanged.
+    FrameRecord r;
+    if (find_frame(geom, r)) {
+        if (!r.need_backward)
+            return fail(GSR_ERR_INVALID, "[gsr] backward: the last %s on this geometry arena had need_backward = 0 and saved nothing for "
+                        "it", r.kind == 2 ? "gsr_forward_recolor" : "forward");
+        if (r.fwd_need_backward == 0)
+            return fail(GSR_ERR_INVALID, "[gsr] backward: the recolor's forward on this geometry arena had need_backward = 0 (a "
+                        "need_backward recolor needs the arenas of a need_backward forward)");
+        if (r.V != V || r.P != p->P || r.W != p->W || r.H != p->H)
+            return fail(GSR_ERR_INVALID, "[gsr] backward: V = %d, P = %d, %d x %d, but the last forward or recolor on this geometry "
+                        "arena had V = %d, P = %d, %d x %d", V, p->P, p->W, p->H, r.V, r.P, r.W, r.H);
+    }
     Batch B;
     if (int e = make_batch(p, V, const_cast<void*>(geom), geom_bytes, const_cast<void*>(image), image_bytes,
                            const_cast<void*>(binning), binning_bytes, true, B))

@@ -669,10 +669,12 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
 
 
 def recolor(background, means3D, colors, sh, degree, campos, image_height, image_width, num_rendered, geomBuffer,
-            binningBuffer, imgBuffer, debug=False):
+            binningBuffer, imgBuffer, debug=False, need_backward=False):
     """Re-render a finished forward's view(s) with other per-Gaussian colours (exactly one of `colors` / `sh` [P,M,3]
     non-empty), reusing its geometry, sorted lists and ranges (gsr_forward_recolor).  campos [3] -> color [3,H,W];
-    campos [V,3] (a batch forward's arenas) -> [V,3,H,W], with `colors` [P,3] shared by the views or [V,P,3] per view."""
+    campos [V,3] (a batch forward's arenas) -> [V,3,H,W], with `colors` [P,3] shared by the views or [V,P,3] per view.
+    need_backward (arenas of a need_backward forward): also rewrite the saves, so that a backward afterwards -- with these
+    colours / SH and campos -- differentiates this render (include/gsr.h)."""
     device = means3D.device
     _require_hip(device)
     P, H, W = means3D.shape[0], int(image_height), int(image_width)
@@ -684,7 +686,7 @@ def recolor(background, means3D, colors, sh, degree, campos, image_height, image
             e = torch.empty(0)
             p, keep = _params(background, means3D, colors, torch.empty((1,), device=device), e, e, 1.0, e,
                               torch.empty((1,), device=device), torch.empty((1,), device=device), 1.0, 1.0, H, W, sh, degree,
-                              campos, False, debug, False)
+                              campos, False, debug, need_backward)
             per_view = int(colors.numel() != 0 and colors.dim() == 3)
             if per_view and tuple(colors.shape) != (V, P, 3):
                 raise RuntimeError("recolor: per-view colours must have shape (V, P, 3)")

@@ -171,7 +171,9 @@ int gsr_forward_stage2(const gsr_params* p, void* geom, size_t geom_bytes, void*
  * arenas stay valid for further recolor calls.  With p->need_backward = 1 (and arenas of a need_backward forward) the
  * saves the backward reads are rewritten too (per-pixel state at the list-slice boundaries, accumulated colour, SH clamp
  * mask), so a backward afterwards -- called with the SAME colour inputs -- differentiates the LAST colours rendered; with
- * need_backward = 0 a backward after the recolor is not supported. */
+ * need_backward = 0 a backward after the recolor is not supported (gsr_backward_batch refuses it).  A backward after a
+ * colors_per_view recolor is called with colors_precomp = the [V,P,3] colours and returns dL_dcolor [P,3] SUMMED over the views
+ * (like every per-Gaussian gradient); the per-view shares are not separated. */
 int gsr_forward_recolor(const gsr_params* p, int V, int colors_per_view, void* geom, size_t geom_bytes, const void* binning,
                         size_t binning_bytes, void* image, size_t image_bytes, float* out_color, gsr_stream_t stream);
 
@@ -183,7 +185,12 @@ int gsr_forward_recolor(const gsr_params* p, int V, int colors_per_view, void* g
  * to be cleared by the caller -- the reference zero-fills nine tensors per call (rasterize_points.cu:151-159) -- except
  * dL_dscale / dL_drot, which are not touched when cov3D_precomp is given.  The reference's internal dL_dconic accumulator
  * lives in the geometry arena.  Valid after a forward with need_backward = 1 on the same arenas, any number of times: every
- * call returns the gradients of ITS dL_dpix (a repeated call first clears what the previous one accumulated).
+ * call returns the gradients of ITS dL_dpix (a repeated call first clears what the previous one accumulated).  GSR_ERR_INVALID with
+ * a message when the library's record of the last forward or recolor on `geom` shows that it saved nothing (need_backward = 0),
+ * that it was a need_backward recolor on the arenas of a need_backward = 0 forward, or that V, P, W or H differ from this call's
+ * (arenas without a record -- the record table is dropped once it holds more than 4096 arenas -- are not checked).  After
+ * gsr_forward_batch_channels_train with need_backward = 1 this call is valid and differentiates the COLOUR image alone (the
+ * extra channels' dL_dextra taken as zero): the channels forward writes the colour's saves exactly as the colour forward does.
  * shapes: radii[V,P] dL_dmean2D[P,3] dL_dopacity[P,1] dL_dcolor[P,3] dL_dmean3D[P,3] dL_dcov3D[P,6] dL_dsh[P,M,3]
  * dL_dscale[P,3] dL_drot[P,4].
  * Alignment: dL_drot must be 16-byte aligned (GSR_ERR_INVALID otherwise); the other gradient outputs should be -- every

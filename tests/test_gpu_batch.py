@@ -55,19 +55,33 @@ def test_batch_forward_backward_vs_oracle(oracle, gpu_device):
     names = ("dL_dmean2D", "dL_dcolor", "dL_dopacity", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot")
     gp = {n: x.cpu().numpy() for n, x in zip(names, grads)}
     total = None
-    flips = False
+    flips = 0
+    scenes = []
     for v, view in enumerate(views):
         s = util.scene_from(g, view, W, H, bg=(1, 1, 1))
+        scenes.append(s)
         o, go = oracle.forward_backward(s, dL[v])
         assert counts[v] == o["R"]
         np.testing.assert_array_equal(radii[v].cpu().numpy(), o["radii"])
         err = np.abs(color[v].cpu().numpy() - o["out_color"]).max(axis=0)
         assert (err > 1e-4).mean() <= 2e-3
-        flips = flips or bool((err > 1e-4).any())
+        flips += int((err > 1e-4).sum())
         go["dL_dopacity"] = go["dL_dopacity"].reshape(-1, 1)
         total = go if total is None else {k: total[k] + go[k] for k in total}
+    print("batch of %d views: %d pixels differ from the oracle by more than 1e-4" % (V, flips))
     if not flips:
         check_grads(gp, total, "batch of %d views vs summed oracle gradients" % V)
+    else:
+        # a threshold flip between glibc's and ocml's expf: the oracle's backward replays other decisions than the product's.  The
+        # gradients are held to the sum of the reference build's per-view backwards instead (its expf is the product's)
+        ref = util.reference_build()
+        tr = None
+        for v, s in enumerate(scenes):
+            _, gr = ref.forward_backward(s, dL[v])
+            gr = dict(gr)
+            gr["dL_dopacity"] = gr["dL_dopacity"].reshape(-1, 1)
+            tr = gr if tr is None else {k: tr[k] + gr[k] for k in tr}
+        check_grads(gp, tr, "batch of %d views vs summed reference-build gradients (after %d expf flips)" % (V, flips))
 
 
 def test_batch_equals_single_view_calls_bit_for_bit(gpu_device):
