@@ -84,8 +84,6 @@ struct PreArgs {
     uint32_t* tiles_touched;
     uint8_t* clamped;
     uint32_t* dkey;
-    uint32_t* pre_minmax;                 // [2][n_pre] per view: smallest / largest depth key of a visible Gaussian per workgroup
-    int n_pre;
     float* grad_rec;
     uint64_t* counters;
     char* g_zero;                         // per-frame cleared regions of the geometry / image arenas
@@ -99,7 +97,6 @@ struct PreArgs {
 // reused for every view of the batch -- re-reading them per view pulled the 156-B-stride SH rows from HBM five times over)
 // (135 registers at degree 1 = three waves per SIMD; forcing four -- amdgpu_waves_per_eu(4, 4), 128 registers -- spills: 0.029 ->
 // 0.031 ms per view at 12 views per call, 0.067 -> 0.187 at one)
-constexpr int MAX_VIEWS_PER_THREAD = 256;   // (= api.hip MAX_VIEWS)
 template <int DEG>
 __global__ __launch_bounds__(256) void k_preprocess(PreArgs a)
 {
@@ -121,12 +118,10 @@ __global__ __launch_bounds__(256) void k_preprocess(PreArgs a)
             zero_region(a.iv_zero + a.iv_stride * vw, a.iv_zero_bytes, gtid, nthr);
         }
     }
-    // Threads past the end of the cloud stay (the workgroup meets at a barrier below): they recompute the last Gaussian and
-    // store nothing.
+    // Threads past the end of the cloud stay: they recompute the last Gaussian and store nothing.
     const bool valid = idx_raw < a.P;
     const int idx = valid ? idx_raw : a.P - 1;
     __shared__ float4 xpose[4][256];   // per wave: 64 Splat lines on their way to coalesced stores
-    __shared__ uint32_t s_mm[MAX_VIEWS_PER_THREAD][4][2];   // per view of this thread and wave: depth-key extremes
 
     const V3 p_orig = v3(a.means3D[3 * idx], a.means3D[3 * idx + 1], a.means3D[3 * idx + 2]);
     float cov6[6];
@@ -232,18 +227,6 @@ __global__ __launch_bounds__(256) void k_preprocess(PreArgs a)
             at_view(a.tiles_touched, a.g_stride, vw)[idx] = tiles;
             at_view(a.dkey, a.g_stride, vw)[idx] = key;
         }
-        {
-            // smallest / largest key of a Gaussian that emits pairs, per wave (the depth sort's histogram kernel reduces the
-            // workgroups' records to the key bits the frame's sort has to look at, sort.hip)
-            uint32_t kmin = (valid && key != CULLED_KEY) ? key : 0xFFFFFFFFu, kmax = (valid && key != CULLED_KEY) ? key : 0u;
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                const uint32_t x = __shfl_xor(kmin, d, 64), y = __shfl_xor(kmax, d, 64);
-                kmin = x < kmin ? x : kmin;
-                kmax = y > kmax ? y : kmax;
-            }
-            if ((threadIdx.x & 63) == 0) { s_mm[vw - v_first][threadIdx.x >> 6][0] = kmin; s_mm[vw - v_first][threadIdx.x >> 6][1] = kmax; }
-        }
         // q3: what the pair emission needs per Gaussian (tile rectangle, tile count), so that it gathers ONE line per
         // Gaussian; the whole 64-B line is written here
         // what the emission needs (binning.hip emit_info): (first tile, last tile + 1, pairs emitted, pairs of the reference's
@@ -288,15 +271,6 @@ __global__ __launch_bounds__(256) void k_preprocess(PreArgs a)
             }
         }
     }
-    __syncthreads();
-    if ((int)threadIdx.x < v_last - v_first) {
-        const uint32_t* m = &s_mm[threadIdx.x][0][0];
-        const uint32_t lo01 = m[0] < m[2] ? m[0] : m[2], lo23 = m[4] < m[6] ? m[4] : m[6];
-        const uint32_t hi01 = m[1] > m[3] ? m[1] : m[3], hi23 = m[5] > m[7] ? m[5] : m[7];
-        uint32_t* mm = at_view(a.pre_minmax, a.g_stride, (uint32_t)(v_first + (int)threadIdx.x));
-        mm[blockIdx.x] = lo01 < lo23 ? lo01 : lo23;
-        mm[a.n_pre + blockIdx.x] = hi01 > hi23 ? hi01 : hi23;
-    }
 }
 
 int launch_preprocess(const Launch& L, const gsr_params& p, const Batch& B, int* radii)
@@ -317,7 +291,6 @@ int launch_preprocess(const Launch& L, const gsr_params& p, const Batch& B, int*
     a.scales = p.scales; a.rotations = p.rotations; a.cov3D_precomp = p.cov3D_precomp;
     a.view = p.viewmatrix; a.proj = p.projmatrix; a.campos = p.campos;
     a.splat = g.splat; a.tiles_touched = g.tiles_touched; a.clamped = g.clamped;
-    a.pre_minmax = g.pre_minmax; a.n_pre = (int)div_up(p.P, PRE_THREADS);
     a.dkey = g.dkey[0]; a.radii = radii; a.counters = g.counters; a.grad_rec = B.grad_rec; a.gr_stride = B.gr_stride;
     a.g_zero = g.zero_begin; a.g_zero_bytes = g.zero_bytes; a.g_stride = B.g_stride;
     a.iv_zero = B.iv.zero_begin; a.iv_zero_bytes = B.iv.zero_bytes; a.iv_stride = B.iv_stride;
