@@ -238,6 +238,8 @@ struct FrameRecord {
     size_t xstate_bytes;
     int fwd_need_backward;   // need_backward of the forward whose geometry and lists the arena holds (a recolor carries it on;
                              // -1: unknown, a recolor on an arena without a record)
+    int64_t list_pairs = -1; // largest per-view pair count of that forward's lists (a recolor carries it on; -1: unknown): what the
+                             // scratch of a deterministic backward has to hold slots for
 };
 static std::mutex g_frames_mu;
 static std::map<const void*, FrameRecord> g_frames;
@@ -401,6 +403,14 @@ static int forward_impl(const gsr_params* p, int V, void* geom, size_t geom_byte
         t_list_pairs[(size_t)v] = (int64_t)Lp;
         if (mode != 2 && (int64_t)Lp > B.b.cap) retry = true;
     }
+    {
+        // the lists' extent joins the arena's record (host data of the one read-back above: gsr_backward_batch_det sizes by it)
+        FrameRecord r;
+        if (find_frame(geom, r)) {
+            r.list_pairs = *std::max_element(t_list_pairs.begin(), t_list_pairs.end());
+            note_frame(geom, r);
+        }
+    }
     if (retry) {
         fail(GSR_RETRY, "[gsr] binning arena holds %lld pairs per view, the frame needs more (num_rendered is enough; gsr_last_list_pairs is exact): repeat with resume = 1",
              (long long)B.b.cap);
@@ -513,8 +523,9 @@ int gsr_forward_recolor(const gsr_params* p, int V, int colors_per_view, void* g
         // a need_backward recolor rewrites the colour saves only: the gradient records and the SH clamp mask of the other Gaussians
         // exist (and were cleared) only if the forward under it had need_backward too
         FrameRecord prev;
-        const int fwd_nb = find_frame(geom, prev) ? prev.fwd_need_backward : -1;
-        note_frame(geom, FrameRecord{2, p->need_backward != 0, 0, 0, V, p->P, p->W, p->H, nullptr, 0, fwd_nb});
+        const bool had = find_frame(geom, prev);
+        const int fwd_nb = had ? prev.fwd_need_backward : -1;
+        note_frame(geom, FrameRecord{2, p->need_backward != 0, 0, 0, V, p->P, p->W, p->H, nullptr, 0, fwd_nb, had ? prev.list_pairs : -1});
     }
     const Launch L{(hipStream_t)stream, p->debug};
     const int res = sorted_buffer(tile_count(p));
@@ -533,10 +544,26 @@ int gsr_forward_recolor(const gsr_params* p, int V, int colors_per_view, void* g
     return GSR_OK;
 }
 
-int gsr_backward_batch(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
-                       size_t binning_bytes, const void* image, size_t image_bytes, const float* dL_dpix, float* dL_dmean2D,
-                       float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
-                       float* dL_drot, gsr_stream_t stream)
+// per-view bytes of the deterministic backward's scratch for lists of `pairs` pairs
+static size_t det_view_bytes(int W, int H, int64_t pairs)
+{
+    const int T = ((W + TILE_X - 1) / TILE_X) * ((H + TILE_Y - 1) / TILE_Y);
+    return align_up(det_view(nullptr, T, pairs).bytes, 256);
+}
+
+size_t gsr_backward_det_bytes(int V, int P, int W, int H, int64_t pairs)
+{
+    (void)P;   // (the sort's key bits follow P, its work space does not)
+    if (V < 1 || W <= 0 || H <= 0) return 0;
+    if (pairs > 0xFFFFFFFFll) pairs = 0xFFFFFFFFll;
+    return (size_t)V * det_view_bytes(W, H, pairs) + 256;
+}
+
+// gsr_backward_batch (deterministic = false: det_scratch is not looked at) and gsr_backward_batch_det
+static int backward_impl(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
+                         size_t binning_bytes, const void* image, size_t image_bytes, const float* dL_dpix, float* dL_dmean2D,
+                         float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
+                         float* dL_drot, bool deterministic, void* det_scratch, size_t det_scratch_bytes, gsr_stream_t stream)
 {
     if (int e = check_params(p, V)) return e;
     if (p->P == 0) return GSR_OK;
@@ -550,7 +577,9 @@ int gsr_backward_batch(const gsr_params* p, int V, const int* radii, const void*
     // record (an arena whose forward ran before the record table was last dropped, at more than 4096 arenas) the call goes ahead as
     // it always did: refusing it would break a valid backward, and the caller's contract (gsr.h) is unchanged.
     FrameRecord r;
+    int64_t list_pairs = -1;
     if (find_frame(geom, r)) {
+        list_pairs = r.list_pairs;
         if (!r.need_backward)
             return fail(GSR_ERR_INVALID, "[gsr] backward: the last %s on this geometry arena had need_backward = 0 and saved nothing for "
                         "it", r.kind == 2 ? "gsr_forward_recolor" : "forward");
@@ -567,13 +596,45 @@ int gsr_backward_batch(const gsr_params* p, int V, const int* radii, const void*
         return e;
     const Launch L{(hipStream_t)stream, p->debug};
     const int res = sorted_buffer(tile_count(p));
+    // deterministic: one slot per (consumed list entry, quadrant) in the caller's scratch block.  The block has to hold the
+    // forward's lists: their largest per-view pair count from the arena's record, or -- no record -- the binning arena's capacity
+    DetView D{};
+    size_t d_stride = 0;
+    if (deterministic) {
+        int64_t n = list_pairs >= 0 ? list_pairs : B.b.cap;
+        if (n > B.b.cap) n = B.b.cap;
+        if (n < 1) n = 1;
+        const size_t need = gsr_backward_det_bytes(V, p->P, p->W, p->H, n);
+        if (!det_scratch || det_scratch_bytes < need)
+            return fail(GSR_ERR_CAPACITY, "[gsr] backward_det: scratch block too small (%zu < %zu = gsr_backward_det_bytes(%d, %d, %d, %d, %lld): "
+                        "the forward's lists hold up to %lld pairs per view)", det_scratch_bytes, need, V, p->P, p->W, p->H, (long long)n,
+                        (long long)n);
+        D = det_view(align256(det_scratch), tile_count(p), n);
+        d_stride = det_view_bytes(p->W, p->H, n);
+    }
     {
         ProfScope ps("bwd_items", L.stream);
         if (int e = launch_bwd_items(L, B, tile_count(p), p->P)) return e;
     }
+    int dres = 0;
+    if (deterministic) {
+        {
+            ProfScope ps("det_prepare", L.stream);
+            if (int e = launch_det_prepare(L, B, D, d_stride, B.b.val[res], tile_count(p))) return e;
+        }
+        {
+            ProfScope ps("det_sort", L.stream);
+            if (int e = launch_det_sort(L, B, D, d_stride, p->P, &dres)) return e;
+        }
+    }
     {
         ProfScope ps("render_backward", L.stream);
-        if (int e = launch_render_backward(L, *p, B, B.b.val[res], dL_dpix)) return e;
+        const RenderBwdDet d{D.part, D.flags, D.slot_base, d_stride, (uint32_t)D.cap};
+        if (int e = launch_render_backward(L, *p, B, B.b.val[res], dL_dpix, nullptr, nullptr, deterministic ? &d : nullptr)) return e;
+    }
+    if (deterministic) {
+        ProfScope ps("det_reduce", L.stream);
+        if (int e = launch_det_reduce(L, B, D, d_stride, dres)) return e;
     }
     {
         ProfScope ps("preprocess_backward", L.stream);
@@ -582,6 +643,24 @@ int gsr_backward_batch(const gsr_params* p, int V, const int* radii, const void*
             return e;
     }
     return GSR_OK;
+}
+
+int gsr_backward_batch(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
+                       size_t binning_bytes, const void* image, size_t image_bytes, const float* dL_dpix, float* dL_dmean2D,
+                       float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
+                       float* dL_drot, gsr_stream_t stream)
+{
+    return backward_impl(p, V, radii, geom, geom_bytes, binning, binning_bytes, image, image_bytes, dL_dpix, dL_dmean2D, dL_dopacity,
+                         dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, false, nullptr, 0, stream);
+}
+
+int gsr_backward_batch_det(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
+                           size_t binning_bytes, const void* image, size_t image_bytes, const float* dL_dpix, float* dL_dmean2D,
+                           float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
+                           float* dL_drot, void* det_scratch, size_t det_scratch_bytes, gsr_stream_t stream)
+{
+    return backward_impl(p, V, radii, geom, geom_bytes, binning, binning_bytes, image, image_bytes, dL_dpix, dL_dmean2D, dL_dopacity,
+                         dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, true, det_scratch, det_scratch_bytes, stream);
 }
 
 int gsr_backward_batch_channels(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
@@ -790,6 +869,8 @@ int gsr_selftest(gsr_stream_t stream)
     const int rm = selftest_mm(s, d);
     (void)hipFree(d);
     if (rm != 0) return fail(GSR_ERR_HIP, "[gsr] selftest: matrix-core pixel contraction wrong at check %d", rm);
+    const int rd = selftest_det_reduce(s);
+    if (rd != 0) return fail(GSR_ERR_HIP, "[gsr] selftest: ordered reduction of the deterministic backward differs from the host sum at check %d", rd);
 
     const int64_t n = 100003;
     std::vector<uint32_t> hk(n), hv(n), order(n);

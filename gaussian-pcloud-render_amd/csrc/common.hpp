@@ -282,6 +282,55 @@ inline uint32_t higher_msb(uint32_t n)
     return msb;
 }
 
+// ---- deterministic backward (det_backward.hip) ---------------------------
+// Caller-owned scratch of gsr_backward_batch_det, one block per view at a fixed stride.  The consumed prefixes of a view's tile
+// lists (tile_need[t] entries of tile t) are numbered tile after tile: consumed position = slot_base[tile] + position in the list.
+//   part   [cap][4][DET_SLOT_WORDS]  the nine partial sums of (consumed position, quadrant), laid out like a grad_rec record
+//                                    (words 9..15 zero): 256 B per list entry, one 64-B line per quadrant
+//   flags  [cap]                     byte q of word i != 0: quadrant q of consumed position i was stored by THIS backward
+//   key / val / hist / totals        the (Gaussian id, consumed position) pairs and the radix sort's work space (sort.hip)
+//   slot_base [T + 1]                exclusive prefix sum of tile_need;  count [2]: consumed positions of the view (<= cap)
+constexpr int DET_SLOT_WORDS = 16;
+struct DetView {
+    uint32_t* key[2];
+    uint32_t* val[2];
+    uint32_t* hist;
+    uint32_t* totals;
+    uint32_t* slot_base;
+    uint64_t* count;
+    uint32_t* flags;
+    float* part;
+    int64_t cap;
+    size_t bytes;
+};
+inline DetView det_view(void* base, int T, int64_t cap)
+{
+    DetView d;
+    char* cur = reinterpret_cast<char*>(base);
+    const size_t r = (size_t)(cap > 0 ? cap : 1);
+    carve(cur, d.key[0], r);
+    carve(cur, d.key[1], r);
+    carve(cur, d.val[0], r);
+    carve(cur, d.val[1], r);
+    carve(cur, d.hist, (size_t)RADIX * (size_t)sort_hist_stride((int64_t)r));
+    carve(cur, d.totals, (size_t)RADIX);
+    carve(cur, d.slot_base, (size_t)(T > 0 ? T : 1) + 1);
+    carve(cur, d.count, (size_t)2);
+    carve(cur, d.flags, r);
+    carve(cur, d.part, r * 4 * DET_SLOT_WORDS);
+    d.cap = (int64_t)r;
+    d.bytes = (size_t)(cur - reinterpret_cast<char*>(base));
+    return d;
+}
+// what k_render_backward's storing instantiations (render_bwd.hip) need of it: view 0's arrays and the stride to the next view's
+struct RenderBwdDet {
+    float* part;
+    uint32_t* flags;
+    const uint32_t* slot_base;
+    size_t stride;
+    uint32_t cap;
+};
+
 // ---- launch-side helpers defined in the .hip files ---------------------------------------------
 struct Launch {
     hipStream_t stream;
@@ -377,11 +426,17 @@ struct ExtraGrads {
 };
 int launch_render_forward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, float* out_color,
                           bool with_ckpt, const ExtraChannels* X = nullptr);
+// D != NULL (colour backward only): the storing instantiations -- partial sums go to D's slots instead of into the gradient records
 int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, const float* dL_dpix,
-                           const ExtraChannels* X = nullptr, const ExtraGrads* XG = nullptr);
+                           const ExtraChannels* X = nullptr, const ExtraGrads* XG = nullptr, const RenderBwdDet* D = nullptr);
 int backward_subquadrant_moments(int set);   // render_bwd.hip: set >= 0 stores; 1 = moments about the sub-quadrant centres
 int forward_half_views(int set);   // render_fwd.hip: set >= 0 stores; returns the views per submission up to which the half-quadrant forward runs
 int selftest_mm(hipStream_t stream, float* d_scratch256);   // the matrix-core pixel contraction of the render backward
+// det_backward.hip: the steps of the deterministic backward around the storing render backward (D: view 0's scratch, d_stride apart)
+int launch_det_prepare(const Launch& L, const Batch& B, const DetView& D, size_t d_stride, const uint32_t* point_list, int T);
+int launch_det_sort(const Launch& L, const Batch& B, const DetView& D, size_t d_stride, int P, int* result_buffer);
+int launch_det_reduce(const Launch& L, const Batch& B, const DetView& D, size_t d_stride, int sorted_buffer);
+int selftest_det_reduce(hipStream_t stream);   // the ordered reduction against a host sum in the same order, bit for bit
 #ifdef GSR_STATS
 int debug_bwd_stats(unsigned long long* out8, int reset);   // instrumentation build only
 int debug_dup_times(unsigned long long* out8, int reset);

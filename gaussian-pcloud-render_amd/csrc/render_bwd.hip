@@ -415,13 +415,29 @@ constexpr float SUBQ_M = GSR_SUBQ_M;
 // batch's u rows (alpha T) on the matrix cores, against the basis rows xd instead of the dL_dpixel rows.
 __device__ __forceinline__ RenderBwdX bwd_x() { return RenderBwdX{}; }
 __device__ __forceinline__ RenderBwdX bwd_x(const RenderBwdX& x) { return x; }
+// The STORING colour kernels of the deterministic backward, k_render_backward<MODE, 0, RenderBwdDet>: the same
+// walk and the same contraction, but the flush stores a (quadrant, entry)'s nine sums into a slot of its own -- a pure function of
+// (view, tile, position of the entry in the tile's list, quadrant), so exactly one wave ever writes it -- instead of adding them
+// into the Gaussian's record; k_det_reduce (det_backward.hip) adds the slots of a Gaussian in a fixed order afterwards.  Like the
+// channels argument, the switch is the TYPE of the trailing kernel argument: the atomic instantiations keep their names,
+// arguments and machine code.
+__device__ __forceinline__ RenderBwdX bwd_x(const RenderBwdDet&) { return RenderBwdX{}; }
+__device__ __forceinline__ RenderBwdDet bwd_det() { return RenderBwdDet{}; }
+__device__ __forceinline__ RenderBwdDet bwd_det(const RenderBwdX&) { return RenderBwdDet{}; }
+__device__ __forceinline__ RenderBwdDet bwd_det(const RenderBwdDet& d) { return d; }
 // (the colour kernels take no RenderBwdX argument at all -- XS is empty -- so their kernel arguments, and with them the offsets of the
 // implicit ones, are what they were before the channels backward existed: the same machine code)
+// (the storing kernels carry the slot addressing on top of the colour kernel's 96 registers: four waves per SIMD instead of spills)
+template <typename... XS> constexpr bool bwd_is_det = (std::is_same<XS, RenderBwdDet>::value || ...);
 template <int MODE, int NX, typename... XS>
-__attribute__((amdgpu_waves_per_eu(NX > 0 ? 3 : 5, NX > 0 ? 3 : 5)))
+__attribute__((amdgpu_waves_per_eu(NX > 0 ? 3 : bwd_is_det<XS...> ? 4 : 5, NX > 0 ? 3 : bwd_is_det<XS...> ? 4 : 5)))
 __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... xs)
 {
     const RenderBwdX x = bwd_x(xs...);
+    constexpr bool DET = bwd_is_det<XS...>;
+    static_assert(!DET || NX == 0, "the storing flush exists for the colour backward only");
+    RenderBwdDet det{};
+    if constexpr (DET) det = bwd_det(xs...);
     constexpr bool SUBQ = MODE == 1;
     static_assert(NX == 0 || NX == 4 || NX == 8, "extra channels come in quads");
     // Work items are (tile, chunk of BWD_CHUNK consumed list entries), one quadrant per wave; which ones a workgroup takes: see the
@@ -446,6 +462,18 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
     const float* const x_hi = NX > 0 ? (x_split ? x.extra_hi + (size_t)view * x.extra_hi_vstride : x_lo + 4) : nullptr;
     float* const xg_lo = NX > 0 ? x.grad + (size_t)view * x.extra_vstride : nullptr;
     float* const xg_hi = NX > 0 ? (x_split ? x.grad_hi + (size_t)view * x.extra_hi_vstride : xg_lo + 4) : nullptr;
+    // storing flush: this view's slots, and which words of a slot the lanes WITHOUT a value of entries 0..3 (A) / 4..7 (B) fill
+    // with zeros, so that a slot leaves the wave as one whole 64-B line (28 idle lanes = 4 entries x the 7 unused words 9..15)
+    float* det_part = nullptr;
+    uint8_t* det_flag = nullptr;
+    const uint32_t* det_base = nullptr;
+    uint32_t det_pad = 0;
+    if constexpr (DET) {
+        det_part = at_view(det.part, det.stride, view);
+        det_flag = reinterpret_cast<uint8_t*>(at_view(det.flags, det.stride, view));
+        det_base = at_view(det.slot_base, det.stride, view);
+        det_pad = (threadIdx.x >> 4) < 3u ? 9u + 2u * (threadIdx.x >> 4) + ((threadIdx.x >> 2) & 1u) : 15u;
+    }
     const uint32_t n_items = at_view(a.item_count, a.iv_stride, view)[0];
     // From here on this view's gradient records hold sums of THIS backward: a later backward on the same arenas has to clear
     // them first (k_bwd_items reads the flag; it has finished: stream order).  Raised before anything is accumulated, so a
@@ -534,6 +562,12 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
     const int hi0 = last_chunk ? total : lo + (1 << a.chunk_shift);
 
     const uint2 range = a.ranges[tile];
+    // storing flush: the tile's first consumed position and how many it has (list positions beyond them own no slot)
+    uint32_t det_lo = 0, det_n = 0;
+    if constexpr (DET) {
+        det_lo = det_base[tile];
+        det_n = det_base[tile + 1] - det_lo;
+    }
     const float T_final = inside ? a.final_T[pix] : 0.f;
     float dpx0 = 0.f, dpx1 = 0.f, dpx2 = 0.f;
     if (inside) {
@@ -684,6 +718,9 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
             const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
             const uint32_t nsurv = (uint32_t)__popcll(mask);
             if (lane < 4) stage[((nsurv - 1) >> 2) * QUAD_WORDS + 20 + lane] = 0.f;  // opacity row of the last group
+            // storing flush: the entry's list position rides in the first spare row of its staged record (words 40..43 of a group);
+            // unused places of the round's last group own no slot
+            if constexpr (DET) { if (lane < 4) stage[((nsurv - 1) >> 2) * QUAD_WORDS + 40 + lane] = __builtin_bit_cast(float, 0xFFFFFFFFu); }
             if (touch) {
                 float* p = stage + (slot >> 2) * QUAD_WORDS + (slot & 3u);
                 p[0] = c0.x; p[4] = c0.y; p[8] = c0.z; p[12] = c0.w; p[16] = c1.x; p[20] = c1.y;
@@ -694,6 +731,7 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
                     id_st |= mq > SUBQ_M ? 0x80000000u : 0u;
                 }
                 p[24] = c1.z; p[28] = c1.w; p[32] = c2b; p[36] = __builtin_bit_cast(float, id_st);
+                if constexpr (DET) p[40] = __builtin_bit_cast(float, (uint32_t)f_lane);
                 if constexpr (NX > 0) {
                     float* px_ = stage_x + (slot >> 2) * (4 * NX) + (slot & 3u);
                     px_[0] = cx0.x; px_[4] = cx0.y; px_[8] = cx0.z; px_[12] = cx0.w;
@@ -867,6 +905,11 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
             const float eX = e[0], eY = e[4], cP = e[mm_offP], cQ = e[mm_offQ], cO = e[20];
             uint32_t idA = __builtin_bit_cast(uint32_t, stage[gq0 * QUAD_WORDS + 36u + mm_k4]);
             uint32_t idB = __builtin_bit_cast(uint32_t, stage[gq1 * QUAD_WORDS + 36u + mm_k4]);
+            uint32_t posA = 0, posB = 0;   // storing flush: list positions of this lane's entries (0xFFFFFFFF: no entry)
+            if constexpr (DET) {
+                posA = __builtin_bit_cast(uint32_t, stage[gq0 * QUAD_WORDS + 40u + mm_k4]);
+                posB = __builtin_bit_cast(uint32_t, stage[gq1 * QUAD_WORDS + 40u + mm_k4]);
+            }
             bool subq_batch = SUBQ;
             if constexpr (MODE == 2) {   // (wave-uniform: every lane sees the same eight staged ids between them)
                 subq_batch = __builtin_amdgcn_ballot_w64(((idA | (nb == 2u ? idB : 0u)) >> 31) != 0u) != 0ull;
@@ -944,8 +987,22 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
             vA = dpp_mov<0x128, 0x8, 0x1>(vA, o3);         // row_ror:8, row 3 bank 0: colour b of lane + 8
             float vB = dpp_mov<0x104, 0xf, 0x5>(o1, o2);   // row_shl:4 -> banks 0, 2: o2 of the lane four above
             vB = dpp_mov<0x128, 0x8, 0x2>(vB, o3);         // row 3 bank 1: colour b of lane + 8
+            if constexpr (DET) {
+                // every lane stores: the nine values of an entry, zeros in words 9..15 -- one instruction writes the four whole
+                // lines of entries 0..3 (then 4..7) -- and the lane holding the opacity sum marks the slot as written
+                const size_t cA = (size_t)det_lo + posA, cB = (size_t)det_lo + posB;
+                if (posA < det_n && cA < (size_t)det.cap) {
+                    det_part[(cA * 4u + q) * DET_SLOT_WORDS + (mm_onA ? mm_cA : det_pad)] = mm_onA ? vA : 0.f;
+                    if (mm_onA && mm_cA == 8u) det_flag[cA * 4u + q] = 1;
+                }
+                if (nb == 2u && posB < det_n && cB < (size_t)det.cap) {
+                    det_part[(cB * 4u + q) * DET_SLOT_WORDS + (mm_onB ? mm_cB : det_pad)] = mm_onB ? vB : 0.f;
+                    if (mm_onB && mm_cB == 8u) det_flag[cB * 4u + q] = 1;
+                }
+            } else {
             if (mm_onA && vA != 0.f) atomicAdd(a.grad_rec + (size_t)idA * GRAD_REC_WORDS + mm_cA, vA);
             if (mm_onB && nb == 2u && vB != 0.f) atomicAdd(a.grad_rec + (size_t)idB * GRAD_REC_WORDS + mm_cB, vB);
+            }
             if constexpr (NX > 0) {
                 // dL/d extra: D[i][j] = sum_p xd_i(p) u_j(p); lane (g, column j >= 8) holds channels 4 g .. 4 g + 3 of batch entry j - 8
                 const f32x4 accx = mm_contract(mrow, amx, lane, hit_blocks);
@@ -1022,7 +1079,7 @@ int backward_subquadrant_moments(int set)
 }
 
 int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, const float* dL_dpix,
-                           const ExtraChannels* X, const ExtraGrads* XG)
+                           const ExtraChannels* X, const ExtraGrads* XG, const RenderBwdDet* D)
 {
     RenderBwdArgs a;
     a.ranges = B.iv.ranges;
@@ -1074,6 +1131,15 @@ int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B,
         }
 #undef GSR_LAUNCH_BWD_X
         return check_launch(L, "render_backward_channels");
+    }
+    if (D != nullptr) {
+        const RenderBwdDet d = *D;
+        switch (backward_subquadrant_moments(-1)) {
+        case 1: hipLaunchKernelGGL((k_render_backward<1, 0, RenderBwdDet>), grid, dim3(64), 0, L.stream, a, d); break;
+        case 2: hipLaunchKernelGGL((k_render_backward<2, 0, RenderBwdDet>), grid, dim3(64), 0, L.stream, a, d); break;
+        default: hipLaunchKernelGGL((k_render_backward<0, 0, RenderBwdDet>), grid, dim3(64), 0, L.stream, a, d); break;
+        }
+        return check_launch(L, "render_backward_det");
     }
     switch (backward_subquadrant_moments(-1)) {
     case 1: hipLaunchKernelGGL((k_render_backward<1, 0>), grid, dim3(64), 0, L.stream, a); break;

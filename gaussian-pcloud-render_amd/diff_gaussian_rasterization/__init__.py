@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as _C
+from ._native import get_deterministic, set_deterministic  # noqa: F401  (the deterministic-backward switch)
 
 
 def cpu_deep_copy_tuple(input_tuple):
@@ -66,6 +67,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             if fast is not None:
                 num_rendered, color, radii, arenas, layout = fast
                 ctx.raster_settings, ctx.num_rendered, ctx.opacity_shape, ctx.layout = rs, num_rendered, tuple(opacities.shape), layout
+                ctx.det_pairs = _C.last_list_pairs(1) if need_backward and _C.deterministic_active() else None
                 if need_backward:
                     ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, arenas)
                 ctx.mark_non_differentiable(radii)
@@ -79,6 +81,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             _C.rasterize_gaussians, args, rs.debug, "snapshot_fw.dump",
             "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.", need_backward=any(ctx.needs_input_grad))
         ctx.raster_settings, ctx.num_rendered, ctx.opacity_shape = rs, num_rendered, tuple(opacities.shape)
+        ctx.det_pairs = _C.last_list_pairs(1) if means3D.shape[0] != 0 and _C.deterministic_active() else None
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
                               imgBuffer)
         ctx.mark_non_differentiable(radii)
@@ -90,7 +93,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         if ctx.layout is not None:
             colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, arenas = ctx.saved_tensors
             (g_means2D, g_colors, g_opacities, g_means3D, g_cov3D, g_sh, g_scales, g_rotations) = _C.backward_view(
-                rs, means3D, radii, colors_precomp, scales, rotations, cov3Ds_precomp, grad_out_color, sh, arenas, ctx.layout)
+                rs, means3D, radii, colors_precomp, scales, rotations, cov3Ds_precomp, grad_out_color, sh, arenas, ctx.layout,
+                deterministic=_C.deterministic_active(), pairs=ctx.det_pairs)
             return (g_means3D, g_means2D, _or_none(g_sh, sh), _or_none(g_colors, colors_precomp), g_opacities.reshape(ctx.opacity_shape),
                     _or_none(g_scales, scales), _or_none(g_rotations, rotations), _or_none(g_cov3D, cov3Ds_precomp), None)
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
@@ -101,7 +105,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                 binningBuffer, imgBuffer, rs.debug)
         (g_means2D, g_colors, g_opacities, g_means3D, g_cov3D, g_sh, g_scales, g_rotations) = _native_call(
             _C.rasterize_gaussians_backward, args, rs.debug, "snapshot_bw.dump",
-            "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+            "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n", deterministic=_C.deterministic_active(),
+            pairs=ctx.det_pairs)
         # gradients in the order of forward's inputs; the settings get none
         return (g_means3D, g_means2D, _or_none(g_sh, sh), _or_none(g_colors, colors_precomp), g_opacities.reshape(ctx.opacity_shape),
                 _or_none(g_scales, scales), _or_none(g_rotations, rotations), _or_none(g_cov3D, cov3Ds_precomp), None)
@@ -285,6 +290,7 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
         ctx.raster_settings = rs
         ctx.num_rendered = counts
         ctx.opacity_shape = tuple(opacities.shape)
+        ctx.det_pairs = _C.last_list_pairs(len(counts)) if means3D.shape[0] != 0 and _C.deterministic_active() else None
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
                               imgBuffer, view, proj, cam)
         ctx.mark_non_differentiable(radii)
@@ -298,7 +304,8 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
          grad_rotations) = _C.rasterize_gaussians_backward_batch(
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj, rs.tanfovx,
-            rs.tanfovy, grad_out_color, sh, rs.sh_degree, cam, geomBuffer, binningBuffer, imgBuffer, rs.debug)
+            rs.tanfovy, grad_out_color, sh, rs.sh_degree, cam, geomBuffer, binningBuffer, imgBuffer, rs.debug,
+            deterministic=_C.deterministic_active(), pairs=ctx.det_pairs)
 
         def fit(g, inp):
             return g if inp.numel() != 0 else None
@@ -388,6 +395,17 @@ def rasterize_views_channels(means3D, means2D, opacities, settings_list, extra, 
     `extra` as to every input rasterize_views differentiates; bg_extra and extra_view_scale get none (like the background)."""
     if len(settings_list) == 0:
         raise Exception("rasterize_views_channels: empty settings list")
+    # the channels backward adds dL/d extra with float atomics of its own and has no deterministic counterpart (include/gsr.h)
+    _why = ("rasterize_views_channels has no deterministic backward (the extra channels' gradients are accumulated with float "
+            "atomics); render the channels as colours through rasterize_views, or switch the deterministic path off")
+    if get_deterministic() is True:
+        raise RuntimeError(_why + ": diff_gaussian_rasterization.set_deterministic(False / None)")
+    if get_deterministic() is None and torch.are_deterministic_algorithms_enabled():
+        if torch.is_deterministic_algorithms_warn_only_enabled():
+            import warnings
+            warnings.warn(_why, UserWarning)
+        else:
+            raise RuntimeError(_why + ": torch.use_deterministic_algorithms(True, warn_only=True) or set_deterministic(False)")
     if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
         raise Exception('Please provide excatly one of either SHs or precomputed colors!')
     if ((scales is None or rotations is None) and cov3D_precomp is None) or (

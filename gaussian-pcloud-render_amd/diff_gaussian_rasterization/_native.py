@@ -36,7 +36,7 @@ SYMBOLS = ("gsr_geom_bytes", "gsr_geom_bytes_inference", "gsr_image_bytes", "gsr
            "gsr_get_profile", "gsr_last_error", "gsr_version", "gsr_selftest", "gsr_forward_recolor", "gsr_forward_batch_channels", "gsr_d2h_count",
            "gsr_clock_probe_launch", "gsr_wall_clock_khz", "gsr_last_list_pairs", "gsr_set_forward_half_views",
            "gsr_set_backward_moments", "gsr_extra_state_bytes", "gsr_forward_batch_channels_train",
-           "gsr_backward_batch_channels")
+           "gsr_backward_batch_channels", "gsr_backward_batch_det", "gsr_backward_det_bytes")
 
 GSR_RETRY = 1
 
@@ -83,6 +83,10 @@ def _load():
     lib.gsr_backward_batch.restype = C.c_int
     lib.gsr_backward_batch.argtypes = [C.POINTER(GsrParams), C.c_int, _fp, _fp, C.c_size_t, _fp, C.c_size_t, _fp,
                                        C.c_size_t] + [_fp] * 9 + [_fp]
+    lib.gsr_backward_batch_det.restype = C.c_int
+    lib.gsr_backward_batch_det.argtypes = lib.gsr_backward_batch.argtypes[:-1] + [_fp, C.c_size_t, _fp]
+    lib.gsr_backward_det_bytes.restype = C.c_size_t
+    lib.gsr_backward_det_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64]
     lib.gsr_backward.restype = C.c_int
     lib.gsr_backward.argtypes = [C.POINTER(GsrParams), _fp, C.c_int64, _fp, C.c_size_t, _fp, C.c_size_t, _fp,
                                  C.c_size_t] + [_fp] * 9 + [_fp]
@@ -218,6 +222,45 @@ def set_reference_lists(on):
     else:
         _TLS.reference_lists = bool(on)
     return old
+
+
+# ---- deterministic backward (include/gsr.h gsr_backward_batch_det) ---------------------------------------------------------
+# None (default): follow torch.are_deterministic_algorithms_enabled(); True / False force the path on / off.  GSR_DETERMINISTIC
+# (0 / 1) in the environment sets the initial value.  With the path on, the colour backwards go through gsr_backward_batch_det:
+# bit-identical gradients from call to call and from process to process for the same inputs and call shape (not across different
+# numbers of views per call), for a scratch block per backward and the time of a sort and an ordered reduction.
+_DETERMINISTIC = [{"0": False, "1": True}.get(os.environ.get("GSR_DETERMINISTIC", "").strip())]
+CALLS = dict(backward=0, backward_det=0)     # colour backwards issued through each entry (tests)
+
+
+def set_deterministic(flag):
+    """True / False: force the deterministic colour backward on / off; None: follow torch's deterministic-algorithms switch."""
+    _DETERMINISTIC[0] = None if flag is None else bool(flag)
+
+
+def get_deterministic():
+    """The value set_deterministic was last given (None, True or False)."""
+    return _DETERMINISTIC[0]
+
+
+def deterministic_active():
+    f = _DETERMINISTIC[0]
+    return bool(torch.are_deterministic_algorithms_enabled()) if f is None else f
+
+
+def last_list_pairs(V):
+    """largest per-view pair count of the lists of the calling thread's last forward (gsr_last_list_pairs)"""
+    pairs = (C.c_int64 * V)()
+    _check(lib.gsr_last_list_pairs(pairs, V))
+    return int(max(pairs))
+
+
+def det_scratch(V, P, W, H, pairs, binning_bytes, device):
+    """the scratch block of one deterministic backward.  pairs None: the lists' extent is not known here; (bytes of a view's
+    binning arena) / 16 is an upper bound of what the arena holds (the library checks the size against the lists it remembers)"""
+    if pairs is None:
+        pairs = max(1, int(binning_bytes) // max(1, V) // 16)
+    return torch.empty((int(lib.gsr_backward_det_bytes(V, P, W, H, int(pairs))),), dtype=torch.uint8, device=device)
 
 
 # ---- binning-arena capacity -----------------------------------------------------------------------------------------
@@ -617,8 +660,10 @@ def forward_view(rs, means3D, sh, colors, opacity, scales, rotations, cov3D_prec
     return int(counts[0]), color, radii, arenas, (g, i, b)
 
 
-def backward_view(rs, means3D, radii, colors, scales, rotations, cov3D_precomp, grad_color, sh, arenas, layout):
-    """Backward of forward_view (gsr_backward_batch, V = 1): the reference's 8-tuple."""
+def backward_view(rs, means3D, radii, colors, scales, rotations, cov3D_precomp, grad_color, sh, arenas, layout, deterministic=False,
+                  pairs=None):
+    """Backward of forward_view (gsr_backward_batch, V = 1): the reference's 8-tuple.  deterministic: gsr_backward_batch_det with a
+    scratch block for lists of `pairs` pairs (None: bounded from the binning arena's size)."""
     device = means3D.device
     P = means3D.shape[0]
     H, W = int(grad_color.shape[-2]), int(grad_color.shape[-1])
@@ -647,9 +692,18 @@ def backward_view(rs, means3D, radii, colors, scales, rotations, cov3D_precomp, 
     base = arenas.data_ptr()
     with _on_device(device):
         stream = _raw_stream(device.index) if _raw_stream is not None and device.index is not None else torch.cuda.current_stream(device).cuda_stream
-        rc = lib.gsr_backward_batch(C.byref(p), 1, radii.data_ptr(), base, g, base + g + i, b, base + g, i, grad_color.data_ptr(),
-                                    g_means2D.data_ptr(), g_opacity.data_ptr(), g_colors.data_ptr(), g_means3D.data_ptr(),
-                                    g_cov3D.data_ptr(), g_sh.data_ptr() if M else None, g_scales.data_ptr(), g_rot.data_ptr(), stream)
+        if deterministic:
+            CALLS["backward_det"] += 1
+            scratch = det_scratch(1, P, W, H, pairs, b, device)
+            rc = lib.gsr_backward_batch_det(C.byref(p), 1, radii.data_ptr(), base, g, base + g + i, b, base + g, i, grad_color.data_ptr(),
+                                            g_means2D.data_ptr(), g_opacity.data_ptr(), g_colors.data_ptr(), g_means3D.data_ptr(),
+                                            g_cov3D.data_ptr(), g_sh.data_ptr() if M else None, g_scales.data_ptr(), g_rot.data_ptr(),
+                                            scratch.data_ptr(), scratch.numel(), stream)
+        else:
+            CALLS["backward"] += 1
+            rc = lib.gsr_backward_batch(C.byref(p), 1, radii.data_ptr(), base, g, base + g + i, b, base + g, i, grad_color.data_ptr(),
+                                        g_means2D.data_ptr(), g_opacity.data_ptr(), g_colors.data_ptr(), g_means3D.data_ptr(),
+                                        g_cov3D.data_ptr(), g_sh.data_ptr() if M else None, g_scales.data_ptr(), g_rot.data_ptr(), stream)
     if rc != 0:
         raise RuntimeError(lib.gsr_last_error().decode("utf-8", "replace"))
     return g_means2D, g_colors, g_opacity, g_means3D, g_cov3D, g_sh, g_scales, g_rot
@@ -697,8 +751,10 @@ def recolor(background, means3D, colors, sh, degree, campos, image_height, image
 
 def rasterize_gaussians_backward_batch(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                        viewmatrices, projmatrices, tan_fovx, tan_fovy, dL_dout_color, sh, degree, camposs,
-                                       geomBuffer, binningBuffer, imageBuffer, debug, _alloc=None):
+                                       geomBuffer, binningBuffer, imageBuffer, debug, _alloc=None, deterministic=None, pairs=None):
     """Backward of rasterize_gaussians_batch: dL_dout_color [V,3,H,W], radii [V,P]; gradients summed over the views.
+    deterministic (None: the package switch, deterministic_active()): through gsr_backward_batch_det (bit-identical from call to
+    call), with a scratch block for lists of `pairs` pairs per view (None: bounded from the binning arena's size).
     Returns the reference's 8-tuple (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
     dL_drotations).  _alloc(shape, dtype=, device=): allocator of the outputs (tests hand over float-aligned views to
     exercise the C ABI's alignment fallback; default torch.empty)."""
@@ -720,6 +776,8 @@ def rasterize_gaussians_backward_batch(background, means3D, radii, colors, scale
     dL_dsh = e_or_z((P, M, 3), **z)
     dL_dscales = e_or_z((P, 3), **z) if has_sr else torch.zeros((P, 3), **z)
     dL_drotations = e_or_z((P, 4), **z) if has_sr else torch.zeros((P, 4), **z)
+    if deterministic is None:
+        deterministic = deterministic_active()
     if P != 0:
         with _on_device(device):
             stream = _stream_handle(device)
@@ -729,12 +787,17 @@ def rasterize_gaussians_backward_batch(background, means3D, radii, colors, scale
                               debug, True)
             dpix = _f32c(dL_dout_color, device, "dL_dout_color")
             radii_c = radii.contiguous()
-            _check(lib.gsr_backward_batch(C.byref(p), V, radii_c.data_ptr(), geomBuffer.data_ptr(), geomBuffer.numel(),
-                                          binningBuffer.data_ptr(), binningBuffer.numel(), imageBuffer.data_ptr(),
-                                          imageBuffer.numel(), dpix.data_ptr(), dL_dmeans2D.data_ptr(),
-                                          dL_dopacity.data_ptr(), dL_dcolors.data_ptr(), dL_dmeans3D.data_ptr(),
-                                          dL_dcov3D.data_ptr(), _ptr(dL_dsh), dL_dscales.data_ptr(), dL_drotations.data_ptr(),
-                                          stream))
+            common = (C.byref(p), V, radii_c.data_ptr(), geomBuffer.data_ptr(), geomBuffer.numel(), binningBuffer.data_ptr(),
+                      binningBuffer.numel(), imageBuffer.data_ptr(), imageBuffer.numel(), dpix.data_ptr(), dL_dmeans2D.data_ptr(),
+                      dL_dopacity.data_ptr(), dL_dcolors.data_ptr(), dL_dmeans3D.data_ptr(), dL_dcov3D.data_ptr(), _ptr(dL_dsh),
+                      dL_dscales.data_ptr(), dL_drotations.data_ptr())
+            if deterministic:
+                CALLS["backward_det"] += 1
+                scratch = det_scratch(V, P, W, H, pairs, binningBuffer.numel(), device)
+                _check(lib.gsr_backward_batch_det(*common, scratch.data_ptr(), scratch.numel(), stream))
+            else:
+                CALLS["backward"] += 1
+                _check(lib.gsr_backward_batch(*common, stream))
             del keep
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
 
@@ -801,13 +864,13 @@ def rasterize_gaussians_backward_channels_batch(background, means3D, radii, colo
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
-                                 geomBuffer, R, binningBuffer, imageBuffer, debug):
+                                 geomBuffer, R, binningBuffer, imageBuffer, debug, deterministic=None, pairs=None):
     """Counterpart of RasterizeGaussiansBackwardCUDA (rasterize_points.cu:117-196); same argument order,
     same 8-tuple (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)."""
     return rasterize_gaussians_backward_batch(
         background, means3D, radii.reshape(1, -1), colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
         projmatrix, tan_fovx, tan_fovy, dL_dout_color.reshape((1,) + tuple(dL_dout_color.shape[-3:])), sh, degree, campos,
-        geomBuffer, binningBuffer, imageBuffer, debug)
+        geomBuffer, binningBuffer, imageBuffer, debug, deterministic=deterministic, pairs=pairs)
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):

@@ -201,6 +201,33 @@ int gsr_backward_batch(const gsr_params* p, int V, const int* radii, const void*
                        float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
                        float* dL_dscale, float* dL_drot, gsr_stream_t stream);
 
+/* Deterministic colour backward (opt-in; replaces rasterize_points.cu:117-196 like gsr_backward_batch, and with it the reference's own
+ * float atomics, backward.cu:523-554, whose order of arrival makes its gradients differ in their last bits from run to run; the
+ * reference has no repeatable path).  gsr_backward_batch's arguments, outputs and refusals, plus a caller-owned scratch block.
+ * For the same inputs, the same call shape (V, image size, moments mode, reference_lists), the same library build and the same
+ * device model, every gradient is BIT-IDENTICAL from call to call and from process to process: whichever workgroup takes which work
+ * unit, whatever runs beside it.  It is NOT promised across different V (the list slices and their start states differ), builds or
+ * device models.  The values are those of gsr_backward_batch up to the order of float additions: the same partial sums per (list
+ * entry, 8 x 8 quadrant), stored into slots of their own instead of added with atomics, then added per Gaussian in a fixed order --
+ * tile, then depth inside the tile, then quadrant.  Valid after gsr_forward_batch, after gsr_forward_recolor
+ * with need_backward = 1 and after gsr_forward_batch_channels_train (it then differentiates the colour image alone), any number of
+ * times over one forward, in all three moments modes.  No device->host read-back; the library allocates nothing on the device.
+ *
+ * gsr_backward_det_bytes(V, P, W, H, pairs) is the size of the scratch block, a pure host function: `pairs` is the largest per-view
+ * pair count of the forward's lists -- max_v gsr_last_list_pairs after the forward (exact), or anything larger such as the count the
+ * binning arena was sized for.  A block smaller than the forward's lists need returns GSR_ERR_CAPACITY with the needed size in the
+ * message (the library remembers the lists' extent with the geometry arena's record).  The block is large: about 276 bytes per pair
+ * and view (a 64-B slot per quadrant, the sort's ping-pong buffers and a flag word), i.e. 2.0 GB per view for lists of 7.3 M pairs
+ * and 24 GB for 12 such views, of which only the entries the forward consumed (about 1.1 M per view there) are ever touched.
+ *
+ * gsr_backward_batch_channels has no deterministic counterpart (dL/d extra is accumulated with float atomics of its own): a
+ * channels backward stays non-deterministic. */
+size_t gsr_backward_det_bytes(int V, int P, int W, int H, int64_t pairs);
+int gsr_backward_batch_det(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
+                           size_t binning_bytes, const void* image, size_t image_bytes, const float* dL_dpix, float* dL_dmean2D,
+                           float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                           float* dL_dscale, float* dL_drot, void* det_scratch, size_t det_scratch_bytes, gsr_stream_t stream);
+
 /* Backward of gsr_forward_batch_channels_train (need_backward = 1): gsr_backward_batch's arguments and outputs -- the mean2D, conic
  * and opacity gradients now carry the extra channels' share of dL/d alpha (d = c . dL_dpix + e . dL_dextra with
  * e_k = extra_k * view_scale_k; background term T_final (bg . dL_dpix + bg_extra . dL_dextra)) -- plus dL_dextra [V][nx][H][W]
@@ -267,7 +294,8 @@ int gsr_get_profile(const char** names, float* ms, int cap);
 int gsr_clock_probe_launch(void* dst16, int iters, gsr_stream_t stream);
 int gsr_wall_clock_khz(void);
 
-/* Device self-test of internal primitives (the matrix-core pixel contraction of the render backward, stable radix sort vs std::stable_sort).
+/* Device self-test of internal primitives (the matrix-core pixel contraction of the render backward, the ordered reduction of the
+ * deterministic backward against a host sum in the same order, stable radix sort vs std::stable_sort).
  * Allocates its own small buffers; not part of the hot path.  0 = pass. */
 int gsr_selftest(gsr_stream_t stream);
 
