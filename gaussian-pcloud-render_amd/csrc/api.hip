@@ -230,16 +230,18 @@ static int make_batch(const gsr_params* p, int V, void* geom, size_t geom_bytes,
 // gsr_backward_batch_channels can refuse a backward that does not match it without reading anything back from the device.  Keyed by
 // the arena's address: every forward and recolor on an arena rewrites its record.
 struct FrameRecord {
-    int kind;             // 0 colour forward, 1 channels forward, 2 recolor
-    int need_backward;
-    int nx, layout;       // channels forwards
-    int V, P, W, H;
-    const void* xstate;   // the extra-state block the channels forward saved into (NULL: none)
-    size_t xstate_bytes;
-    int fwd_need_backward;   // need_backward of the forward whose geometry and lists the arena holds (a recolor carries it on;
-                             // -1: unknown, a recolor on an arena without a record)
-    int64_t list_pairs = -1; // largest per-view pair count of that forward's lists (a recolor carries it on; -1: unknown): what the
-                             // scratch of a deterministic backward has to hold slots for
+    int kind = 0;             // 0 colour forward, 1 channels forward, 2 recolor
+    int need_backward = 0;
+    int nx = 0, layout = 0;   // channels forwards
+    int V = 0, P = 0, W = 0, H = 0;
+    const void* xstate = nullptr;   // the extra-state block the channels forward saved into (NULL: none)
+    size_t xstate_bytes = 0;
+    int fwd_need_backward = -1;  // need_backward of the forward whose geometry and lists the arena holds (a recolor carries it on;
+                                 // -1: unknown, a recolor on an arena without a record)
+    int64_t list_pairs = -1;     // largest per-view pair count of that forward's lists (a recolor carries it on; -1: unknown): what the
+                                 // scratch of a deterministic backward has to hold slots for
+    FrameRecord() = default;
+    FrameRecord(int kind_, const gsr_params* p, int V_) : kind(kind_), need_backward(p->need_backward != 0), V(V_), P(p->P), W(p->W), H(p->H) {}
 };
 static std::mutex g_frames_mu;
 static std::map<const void*, FrameRecord> g_frames;
@@ -300,8 +302,10 @@ static int forward_impl(const gsr_params* p, int V, void* geom, size_t geom_byte
         X = &Xs;
     }
     {
-        FrameRecord r{X ? 1 : 0, p->need_backward != 0, X ? X->nx : 0, 0, V, p->P, p->W, p->H, nullptr, 0, p->need_backward != 0};
+        FrameRecord r(X ? 1 : 0, p, V);
+        r.fwd_need_backward = r.need_backward;
         if (X) {
+            r.nx = X->nx;
             r.layout = X->values_hi ? 2 : X->view_stride ? 1 : 0;
             if (X->state.accum) { r.xstate = xraw; r.xstate_bytes = X->state.bytes; }
         }
@@ -522,10 +526,12 @@ int gsr_forward_recolor(const gsr_params* p, int V, int colors_per_view, void* g
     {
         // a need_backward recolor rewrites the colour saves only: the gradient records and the SH clamp mask of the other Gaussians
         // exist (and were cleared) only if the forward under it had need_backward too
-        FrameRecord prev;
-        const bool had = find_frame(geom, prev);
-        const int fwd_nb = had ? prev.fwd_need_backward : -1;
-        note_frame(geom, FrameRecord{2, p->need_backward != 0, 0, 0, V, p->P, p->W, p->H, nullptr, 0, fwd_nb, had ? prev.list_pairs : -1});
+        FrameRecord prev, r(2, p, V);
+        if (find_frame(geom, prev)) {   // (no record: both stay -1, unknown)
+            r.fwd_need_backward = prev.fwd_need_backward;
+            r.list_pairs = prev.list_pairs;
+        }
+        note_frame(geom, r);
     }
     const Launch L{(hipStream_t)stream, p->debug};
     const int res = sorted_buffer(tile_count(p));
@@ -559,68 +565,130 @@ size_t gsr_backward_det_bytes(int V, int P, int W, int H, int64_t pairs)
     return (size_t)V * det_view_bytes(W, H, pairs) + 256;
 }
 
-// gsr_backward_batch (deterministic = false: det_scratch is not looked at) and gsr_backward_batch_det
-static int backward_impl(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
-                         size_t binning_bytes, const void* image, size_t image_bytes, const float* dL_dpix, float* dL_dmean2D,
-                         float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
-                         float* dL_drot, bool deterministic, void* det_scratch, size_t det_scratch_bytes, gsr_stream_t stream)
+// ---- the backward: one sequence behind gsr_backward, gsr_backward_batch, gsr_backward_batch_det and gsr_backward_batch_channels ----
+struct BwdGrads {   // dL/d image in, the eight gradient outputs (include/gsr.h)
+    const float* dL_dpix;
+    float *dL_dmean2D, *dL_dopacity, *dL_dcolor, *dL_dmean3D, *dL_dcov3D, *dL_dsh, *dL_dscale, *dL_drot;
+};
+struct BwdDet { void* scratch; size_t bytes; };   // optional part: the deterministic backward's scratch block
+struct BwdExtra {   // optional part: the extra channels (X.state is carved by backward_impl), their gradients and state block
+    ExtraChannels X;
+    ExtraGrads XG;
+    int layout;     // extra_per_view
+    const void* state;
+    size_t state_bytes;
+};
+
+static int check_bwd_pointers(const gsr_params* p, const int* radii, const void* binning, const BwdGrads& G)
 {
+    if (!radii || !G.dL_dpix || !G.dL_dmean2D || !G.dL_dopacity || !G.dL_dcolor || !G.dL_dmean3D || !G.dL_dcov3D)
+        return fail(GSR_ERR_INVALID, "[gsr] a required backward pointer is NULL");
+    if (p->shs && !G.dL_dsh) return fail(GSR_ERR_INVALID, "[gsr] dL_dsh is NULL");
+    if (p->scales && (!G.dL_dscale || !G.dL_drot)) return fail(GSR_ERR_INVALID, "[gsr] dL_dscale/dL_drot is NULL");
+    if (p->scales && ((uintptr_t)G.dL_drot & 15u)) return fail(GSR_ERR_INVALID, "[gsr] dL_drot must be 16-byte aligned (it is written one float4 per Gaussian)");
+    if (!binning) return fail(GSR_ERR_INVALID, "[gsr] binning arena is NULL");
+    return GSR_OK;
+}
+
+// The forward or recolor a backward differentiates has to have saved what it reads, for the same views and sizes.
+// Colour backward (x == NULL): without a record (an arena whose forward ran before the record table was last dropped, at more than
+// 4096 arenas) the call goes ahead as it always did: refusing it would break a valid backward, and the caller's contract (gsr.h) is
+// unchanged.  Channels backward: the record has to be that of a channels forward with need_backward = 1 into this extra-state
+// block, with the same channels, layout and sizes.  list_pairs: the record's (-1: none).
+static int check_bwd_frame(const void* geom, const gsr_params* p, int V, const BwdExtra* x, int64_t* list_pairs)
+{
+    FrameRecord r;
+    *list_pairs = -1;
+    if (!find_frame(geom, r))
+        return x ? fail(GSR_ERR_INVALID, "[gsr] backward_channels: no forward on this geometry arena (run gsr_forward_batch_channels_train first)")
+                 : GSR_OK;
+    *list_pairs = r.list_pairs;
+    const bool same = r.V == V && r.P == p->P && r.W == p->W && r.H == p->H;
+    if (x) {
+        if (r.kind == 2)
+            return fail(GSR_ERR_INVALID, "[gsr] backward_channels after gsr_forward_recolor is not supported: the recolor replaced the saves "
+                        "of the channels forward (run gsr_forward_batch_channels_train again)");
+        if (r.kind != 1 || !r.need_backward || r.xstate == nullptr)
+            return fail(GSR_ERR_INVALID, "[gsr] backward_channels: the forward on this arena saved no extra channels (it needs "
+                        "gsr_forward_batch_channels_train with need_backward = 1)");
+        if (r.nx != x->X.nx || r.layout != x->layout)
+            return fail(GSR_ERR_INVALID, "[gsr] backward_channels: nx = %d, extra_per_view = %d, but the forward had nx = %d, extra_per_view = %d",
+                        x->X.nx, x->layout, r.nx, r.layout);
+        if (!same) return fail(GSR_ERR_INVALID, "[gsr] backward_channels: views / sizes differ from the forward's");
+        if (r.xstate != x->state || x->state_bytes < r.xstate_bytes)
+            return fail(GSR_ERR_INVALID, "[gsr] backward_channels: extra_state is not the block the forward saved into");
+        return GSR_OK;
+    }
+    if (!r.need_backward)
+        return fail(GSR_ERR_INVALID, "[gsr] backward: the last %s on this geometry arena had need_backward = 0 and saved nothing for "
+                    "it", r.kind == 2 ? "gsr_forward_recolor" : "forward");
+    if (r.fwd_need_backward == 0)
+        return fail(GSR_ERR_INVALID, "[gsr] backward: the recolor's forward on this geometry arena had need_backward = 0 (a "
+                    "need_backward recolor needs the arenas of a need_backward forward)");
+    if (!same)
+        return fail(GSR_ERR_INVALID, "[gsr] backward: V = %d, P = %d, %d x %d, but the last forward or recolor on this geometry "
+                    "arena had V = %d, P = %d, %d x %d", V, p->P, p->W, p->H, r.V, r.P, r.W, r.H);
+    return GSR_OK;
+}
+
+// det / x: at most one of the two optional parts (there is no deterministic channels backward).
+static int backward_impl(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
+                         size_t binning_bytes, const void* image, size_t image_bytes, const BwdGrads& G, const BwdDet* det, BwdExtra* x,
+                         gsr_stream_t stream)
+{
+    if (det && x) return fail(GSR_ERR_INVALID, "[gsr] backward: no deterministic backward of the extra channels");
     if (int e = check_params(p, V)) return e;
     if (p->P == 0) return GSR_OK;
-    if (!radii || !dL_dpix || !dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dcov3D)
-        return fail(GSR_ERR_INVALID, "[gsr] a required backward pointer is NULL");
-    if (p->shs && !dL_dsh) return fail(GSR_ERR_INVALID, "[gsr] dL_dsh is NULL");
-    if (p->scales && (!dL_dscale || !dL_drot)) return fail(GSR_ERR_INVALID, "[gsr] dL_dscale/dL_drot is NULL");
-    if (p->scales && ((uintptr_t)dL_drot & 15u)) return fail(GSR_ERR_INVALID, "[gsr] dL_drot must be 16-byte aligned (it is written one float4 per Gaussian)");
-    if (!binning) return fail(GSR_ERR_INVALID, "[gsr] binning arena is NULL");
-    // the forward or recolor this backward differentiates has to have saved what it reads, for the same views and sizes.  Without a
-    // record (an arena whose forward ran before the record table was last dropped, at more than 4096 arenas) the call goes ahead as
-    // it always did: refusing it would break a valid backward, and the caller's contract (gsr.h) is unchanged.
-    FrameRecord r;
+    // which fault a call with several reports is part of each entry's contract: the colour entries look at the pointers first, the
+    // channels entry at the arena's record
     int64_t list_pairs = -1;
-    if (find_frame(geom, r)) {
-        list_pairs = r.list_pairs;
-        if (!r.need_backward)
-            return fail(GSR_ERR_INVALID, "[gsr] backward: the last %s on this geometry arena had need_backward = 0 and saved nothing for "
-                        "it", r.kind == 2 ? "gsr_forward_recolor" : "forward");
-        if (r.fwd_need_backward == 0)
-            return fail(GSR_ERR_INVALID, "[gsr] backward: the recolor's forward on this geometry arena had need_backward = 0 (a "
-                        "need_backward recolor needs the arenas of a need_backward forward)");
-        if (r.V != V || r.P != p->P || r.W != p->W || r.H != p->H)
-            return fail(GSR_ERR_INVALID, "[gsr] backward: V = %d, P = %d, %d x %d, but the last forward or recolor on this geometry "
-                        "arena had V = %d, P = %d, %d x %d", V, p->P, p->W, p->H, r.V, r.P, r.W, r.H);
-    }
+    if (!x)
+        if (int e = check_bwd_pointers(p, radii, binning, G)) return e;
+    if (int e = check_bwd_frame(geom, p, V, x, &list_pairs)) return e;
+    if (x)
+        if (int e = check_bwd_pointers(p, radii, binning, G)) return e;
     Batch B;
     if (int e = make_batch(p, V, const_cast<void*>(geom), geom_bytes, const_cast<void*>(image), image_bytes,
                            const_cast<void*>(binning), binning_bytes, true, B))
         return e;
     const Launch L{(hipStream_t)stream, p->debug};
-    const int res = sorted_buffer(tile_count(p));
+    const int T = tile_count(p), res = sorted_buffer(T);
     // deterministic: one slot per (consumed list entry, quadrant) in the caller's scratch block.  The block has to hold the
     // forward's lists: their largest per-view pair count from the arena's record, or -- no record -- the binning arena's capacity
     DetView D{};
     size_t d_stride = 0;
-    if (deterministic) {
+    if (det) {
         int64_t n = list_pairs >= 0 ? list_pairs : B.b.cap;
         if (n > B.b.cap) n = B.b.cap;
         if (n < 1) n = 1;
         const size_t need = gsr_backward_det_bytes(V, p->P, p->W, p->H, n);
-        if (!det_scratch || det_scratch_bytes < need)
+        if (!det->scratch || det->bytes < need)
             return fail(GSR_ERR_CAPACITY, "[gsr] backward_det: scratch block too small (%zu < %zu = gsr_backward_det_bytes(%d, %d, %d, %d, %lld): "
-                        "the forward's lists hold up to %lld pairs per view)", det_scratch_bytes, need, V, p->P, p->W, p->H, (long long)n,
+                        "the forward's lists hold up to %lld pairs per view)", det->bytes, need, V, p->P, p->W, p->H, (long long)n,
                         (long long)n);
-        D = det_view(align256(det_scratch), tile_count(p), n);
+        D = det_view(align256(det->scratch), T, n);
         d_stride = det_view_bytes(p->W, p->H, n);
+    }
+    if (x) {
+        const int nx = x->X.nx;
+        x->X.state = xstate_view(align256(const_cast<void*>(x->state)), p->W, p->H, B.b.cap, nx);
+        x->X.state_stride = xstate_view_bytes(p->W, p->H, B.b.cap, nx);
+        if (x->state_bytes < (size_t)V * x->X.state_stride + 256)
+            return fail(GSR_ERR_CAPACITY, "[gsr] extra-state block too small for this binning arena");
     }
     {
         ProfScope ps("bwd_items", L.stream);
-        if (int e = launch_bwd_items(L, B, tile_count(p), p->P)) return e;
+        // dL/d extra values are accumulated with atomics, views that share an array into the same rows: clear the output first
+        const size_t n_out = !x ? 0 : (size_t)p->P * (x->layout == 0 ? x->X.nx : x->layout == 1 ? V * x->X.nx : (1 + V) * 4);
+        if (x && hipMemsetAsync(x->XG.grad, 0, n_out * sizeof(float), L.stream) != hipSuccess)
+            return fail(GSR_ERR_HIP, "[gsr] memset failed: %s", hipGetErrorString(hipGetLastError()));
+        if (int e = launch_bwd_items(L, B, T, p->P)) return e;
     }
     int dres = 0;
-    if (deterministic) {
+    if (det) {
         {
             ProfScope ps("det_prepare", L.stream);
-            if (int e = launch_det_prepare(L, B, D, d_stride, B.b.val[res], tile_count(p))) return e;
+            if (int e = launch_det_prepare(L, B, D, d_stride, B.b.val[res], T)) return e;
         }
         {
             ProfScope ps("det_sort", L.stream);
@@ -630,16 +698,17 @@ static int backward_impl(const gsr_params* p, int V, const int* radii, const voi
     {
         ProfScope ps("render_backward", L.stream);
         const RenderBwdDet d{D.part, D.flags, D.slot_base, d_stride, (uint32_t)D.cap};
-        if (int e = launch_render_backward(L, *p, B, B.b.val[res], dL_dpix, nullptr, nullptr, deterministic ? &d : nullptr)) return e;
+        if (int e = launch_render_backward(L, *p, B, B.b.val[res], G.dL_dpix, x ? &x->X : nullptr, x ? &x->XG : nullptr, det ? &d : nullptr))
+            return e;
     }
-    if (deterministic) {
+    if (det) {
         ProfScope ps("det_reduce", L.stream);
         if (int e = launch_det_reduce(L, B, D, d_stride, dres)) return e;
     }
     {
         ProfScope ps("preprocess_backward", L.stream);
-        if (int e = launch_preprocess_backward(L, *p, B, radii, dL_dmean2D, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                               dL_dscale, dL_drot))
+        if (int e = launch_preprocess_backward(L, *p, B, radii, G.dL_dmean2D, G.dL_dopacity, G.dL_dcolor, G.dL_dmean3D, G.dL_dcov3D,
+                                               G.dL_dsh, G.dL_dscale, G.dL_drot))
             return e;
     }
     return GSR_OK;
@@ -650,8 +719,8 @@ int gsr_backward_batch(const gsr_params* p, int V, const int* radii, const void*
                        float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
                        float* dL_drot, gsr_stream_t stream)
 {
-    return backward_impl(p, V, radii, geom, geom_bytes, binning, binning_bytes, image, image_bytes, dL_dpix, dL_dmean2D, dL_dopacity,
-                         dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, false, nullptr, 0, stream);
+    const BwdGrads G{dL_dpix, dL_dmean2D, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot};
+    return backward_impl(p, V, radii, geom, geom_bytes, binning, binning_bytes, image, image_bytes, G, nullptr, nullptr, stream);
 }
 
 int gsr_backward_batch_det(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
@@ -659,8 +728,9 @@ int gsr_backward_batch_det(const gsr_params* p, int V, const int* radii, const v
                            float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
                            float* dL_drot, void* det_scratch, size_t det_scratch_bytes, gsr_stream_t stream)
 {
-    return backward_impl(p, V, radii, geom, geom_bytes, binning, binning_bytes, image, image_bytes, dL_dpix, dL_dmean2D, dL_dopacity,
-                         dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, true, det_scratch, det_scratch_bytes, stream);
+    const BwdGrads G{dL_dpix, dL_dmean2D, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot};
+    const BwdDet det{det_scratch, det_scratch_bytes};
+    return backward_impl(p, V, radii, geom, geom_bytes, binning, binning_bytes, image, image_bytes, G, &det, nullptr, stream);
 }
 
 int gsr_backward_batch_channels(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
@@ -670,66 +740,12 @@ int gsr_backward_batch_channels(const gsr_params* p, int V, const int* radii, co
                                 const float* extra_view_scale, const float* bg_extra, const void* extra_state, size_t extra_state_bytes,
                                 const float* dL_dextra, float* dL_dextra_values, gsr_stream_t stream)
 {
-    ExtraChannels X;
-    if (int e = extra_channels(p, nx, extra_per_view, extra, extra_view_scale, bg_extra, dL_dextra_values, X)) return e;
+    BwdExtra x{{}, {}, extra_per_view, extra_state, extra_state_bytes};
+    if (int e = extra_channels(p, nx, extra_per_view, extra, extra_view_scale, bg_extra, dL_dextra_values, x.X)) return e;
     if (!dL_dextra || !extra_state) return fail(GSR_ERR_INVALID, "[gsr] dL_dextra / extra_state is NULL");
-    if (int e = check_params(p, V)) return e;
-    if (p->P == 0) return GSR_OK;
-    // the forward this backward differentiates has to be a channels forward with need_backward = 1 into this extra-state block, with
-    // the same channels, layout and sizes
-    FrameRecord r;
-    if (!find_frame(geom, r))
-        return fail(GSR_ERR_INVALID, "[gsr] backward_channels: no forward on this geometry arena (run gsr_forward_batch_channels_train first)");
-    if (r.kind == 2)
-        return fail(GSR_ERR_INVALID, "[gsr] backward_channels after gsr_forward_recolor is not supported: the recolor replaced the saves "
-                    "of the channels forward (run gsr_forward_batch_channels_train again)");
-    if (r.kind != 1 || !r.need_backward || r.xstate == nullptr)
-        return fail(GSR_ERR_INVALID, "[gsr] backward_channels: the forward on this arena saved no extra channels (it needs "
-                    "gsr_forward_batch_channels_train with need_backward = 1)");
-    const int layout = extra_per_view;
-    if (r.nx != nx || r.layout != layout)
-        return fail(GSR_ERR_INVALID, "[gsr] backward_channels: nx = %d, extra_per_view = %d, but the forward had nx = %d, extra_per_view = %d",
-                    nx, layout, r.nx, r.layout);
-    if (r.V != V || r.P != p->P || r.W != p->W || r.H != p->H)
-        return fail(GSR_ERR_INVALID, "[gsr] backward_channels: views / sizes differ from the forward's");
-    if (r.xstate != extra_state || extra_state_bytes < r.xstate_bytes)
-        return fail(GSR_ERR_INVALID, "[gsr] backward_channels: extra_state is not the block the forward saved into");
-    if (!radii || !dL_dpix || !dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dcov3D)
-        return fail(GSR_ERR_INVALID, "[gsr] a required backward pointer is NULL");
-    if (p->shs && !dL_dsh) return fail(GSR_ERR_INVALID, "[gsr] dL_dsh is NULL");
-    if (p->scales && (!dL_dscale || !dL_drot)) return fail(GSR_ERR_INVALID, "[gsr] dL_dscale/dL_drot is NULL");
-    if (p->scales && ((uintptr_t)dL_drot & 15u)) return fail(GSR_ERR_INVALID, "[gsr] dL_drot must be 16-byte aligned (it is written one float4 per Gaussian)");
-    if (!binning) return fail(GSR_ERR_INVALID, "[gsr] binning arena is NULL");
-    Batch B;
-    if (int e = make_batch(p, V, const_cast<void*>(geom), geom_bytes, const_cast<void*>(image), image_bytes,
-                           const_cast<void*>(binning), binning_bytes, true, B))
-        return e;
-    X.state = xstate_view(align256(const_cast<void*>(extra_state)), p->W, p->H, B.b.cap, nx);
-    X.state_stride = xstate_view_bytes(p->W, p->H, B.b.cap, nx);
-    if (extra_state_bytes < (size_t)V * X.state_stride + 256)
-        return fail(GSR_ERR_CAPACITY, "[gsr] extra-state block too small for this binning arena");
-    // dL/d extra values are accumulated with atomics, views that share an array into the same rows: clear the output first
-    const size_t n_out = extra_per_view == 0 ? (size_t)p->P * nx : extra_per_view == 1 ? (size_t)V * p->P * nx : (size_t)(1 + V) * p->P * 4;
-    ExtraGrads XG{dL_dextra, dL_dextra_values, extra_per_view == 2 ? dL_dextra_values + (size_t)p->P * 4 : nullptr};
-    const Launch L{(hipStream_t)stream, p->debug};
-    const int res = sorted_buffer(tile_count(p));
-    {
-        ProfScope ps("bwd_items", L.stream);
-        if (hipMemsetAsync(dL_dextra_values, 0, n_out * sizeof(float), L.stream) != hipSuccess)
-            return fail(GSR_ERR_HIP, "[gsr] memset failed: %s", hipGetErrorString(hipGetLastError()));
-        if (int e = launch_bwd_items(L, B, tile_count(p), p->P)) return e;
-    }
-    {
-        ProfScope ps("render_backward", L.stream);
-        if (int e = launch_render_backward(L, *p, B, B.b.val[res], dL_dpix, &X, &XG)) return e;
-    }
-    {
-        ProfScope ps("preprocess_backward", L.stream);
-        if (int e = launch_preprocess_backward(L, *p, B, radii, dL_dmean2D, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                               dL_dscale, dL_drot))
-            return e;
-    }
-    return GSR_OK;
+    x.XG = ExtraGrads{dL_dextra, dL_dextra_values, extra_per_view == 2 ? dL_dextra_values + (size_t)p->P * 4 : nullptr};
+    const BwdGrads G{dL_dpix, dL_dmean2D, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot};
+    return backward_impl(p, V, radii, geom, geom_bytes, binning, binning_bytes, image, image_bytes, G, nullptr, &x, stream);
 }
 
 int gsr_backward(const gsr_params* p, const int* radii, int64_t R, const void* geom, size_t geom_bytes, const void* binning,

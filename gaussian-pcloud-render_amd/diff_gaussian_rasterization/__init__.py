@@ -53,6 +53,32 @@ def _or_none(grad, inp):
     return grad if inp.numel() != 0 else None
 
 
+def _input_grads(grads, ctx, sh, colors_precomp, scales, rotations, cov3Ds_precomp, *rest):
+    """The native backward's 8-tuple as the gradients of (means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+    cov3Ds_precomp), the order of forward's inputs, followed by `rest` (the settings get None)."""
+    g_means2D, g_colors, g_opacities, g_means3D, g_cov3D, g_sh, g_scales, g_rotations = grads
+    return (g_means3D, g_means2D, _or_none(g_sh, sh), _or_none(g_colors, colors_precomp), g_opacities.reshape(ctx.opacity_shape),
+            _or_none(g_scales, scales), _or_none(g_rotations, rotations), _or_none(g_cov3D, cov3Ds_precomp)) + rest
+
+
+_ABSENT = torch.Tensor([])
+
+
+def _check_sources(shs, colors_precomp, scales, rotations, cov3D_precomp):
+    """exactly one colour source and exactly one covariance source (reference __init__.py:190-195: the same exception texts)"""
+    if (shs is None) == (colors_precomp is None):
+        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+    pair_given, pair_complete = scales is not None or rotations is not None, scales is not None and rotations is not None
+    if (cov3D_precomp is None and not pair_complete) or (cov3D_precomp is not None and pair_given):
+        raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+
+
+def _absent_as_empty(*optionals):
+    """absent optionals travel as empty CPU tensors, like the reference's torch.Tensor([]) (:197-206); one shared empty tensor
+    instead of a fresh one per call (GaussianRasterizer.forward runs while the GPU waits for the call's first kernel)"""
+    return [_ABSENT if t is None else t for t in optionals]
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """The per-view call: 9 inputs in the reference's order, (color, radii) out, gradients back in input order (reference
     __init__.py:44-155)."""
@@ -92,24 +118,20 @@ class _RasterizeGaussians(torch.autograd.Function):
         rs = ctx.raster_settings
         if ctx.layout is not None:
             colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, arenas = ctx.saved_tensors
-            (g_means2D, g_colors, g_opacities, g_means3D, g_cov3D, g_sh, g_scales, g_rotations) = _C.backward_view(
-                rs, means3D, radii, colors_precomp, scales, rotations, cov3Ds_precomp, grad_out_color, sh, arenas, ctx.layout,
-                deterministic=_C.deterministic_active(), pairs=ctx.det_pairs)
-            return (g_means3D, g_means2D, _or_none(g_sh, sh), _or_none(g_colors, colors_precomp), g_opacities.reshape(ctx.opacity_shape),
-                    _or_none(g_scales, scales), _or_none(g_rotations, rotations), _or_none(g_cov3D, cov3Ds_precomp), None)
+            grads = _C.backward_view(rs, means3D, radii, colors_precomp, scales, rotations, cov3Ds_precomp, grad_out_color, sh, arenas,
+                                     ctx.layout, deterministic=_C.deterministic_active(), pairs=ctx.det_pairs)
+            return _input_grads(grads, ctx, sh, colors_precomp, scales, rotations, cov3Ds_precomp, None)
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
          imgBuffer) = ctx.saved_tensors
         # the native call's argument order = reference __init__.py:109-129
         args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
                 rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos, geomBuffer, ctx.num_rendered,
                 binningBuffer, imgBuffer, rs.debug)
-        (g_means2D, g_colors, g_opacities, g_means3D, g_cov3D, g_sh, g_scales, g_rotations) = _native_call(
+        grads = _native_call(
             _C.rasterize_gaussians_backward, args, rs.debug, "snapshot_bw.dump",
             "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n", deterministic=_C.deterministic_active(),
             pairs=ctx.det_pairs)
-        # gradients in the order of forward's inputs; the settings get none
-        return (g_means3D, g_means2D, _or_none(g_sh, sh), _or_none(g_colors, colors_precomp), g_opacities.reshape(ctx.opacity_shape),
-                _or_none(g_scales, scales), _or_none(g_rotations, rotations), _or_none(g_cov3D, cov3Ds_precomp), None)
+        return _input_grads(grads, ctx, sh, colors_precomp, scales, rotations, cov3Ds_precomp, None)
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -125,9 +147,6 @@ class GaussianRasterizationSettings(NamedTuple):
     campos: torch.Tensor
     prefiltered: bool
     debug: bool
-
-
-_ABSENT = torch.Tensor([])
 
 
 class GaussianRasterizer(nn.Module):
@@ -166,17 +185,8 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None):
-        # exactly one colour source and exactly one covariance source (reference __init__.py:190-195: the same exception texts)
-        if (shs is None) == (colors_precomp is None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        pair_given, pair_complete = scales is not None or rotations is not None, scales is not None and rotations is not None
-        if (cov3D_precomp is None and not pair_complete) or (cov3D_precomp is not None and pair_given):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-        # absent optionals travel as empty CPU tensors, like the reference's torch.Tensor([]) (:197-206); one shared empty tensor
-        # instead of a fresh one per call (this method runs while the GPU waits for the call's first kernel)
-        absent = _ABSENT
-        shs, colors_precomp, scales, rotations, cov3D_precomp = (absent if t is None else t
-                                                                 for t in (shs, colors_precomp, scales, rotations, cov3D_precomp))
+        _check_sources(shs, colors_precomp, scales, rotations, cov3D_precomp)
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales, rotations, cov3D_precomp)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                    self.raster_settings)
 
@@ -301,18 +311,11 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
         rs = ctx.raster_settings
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer, view, proj,
          cam) = ctx.saved_tensors
-        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = _C.rasterize_gaussians_backward_batch(
+        grads = _C.rasterize_gaussians_backward_batch(
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj, rs.tanfovx,
             rs.tanfovy, grad_out_color, sh, rs.sh_degree, cam, geomBuffer, binningBuffer, imgBuffer, rs.debug,
             deterministic=_C.deterministic_active(), pairs=ctx.det_pairs)
-
-        def fit(g, inp):
-            return g if inp.numel() != 0 else None
-
-        return (grad_means3D, grad_means2D, fit(grad_sh, sh), fit(grad_colors_precomp, colors_precomp),
-                grad_opacities.reshape(ctx.opacity_shape), fit(grad_scales, scales), fit(grad_rotations, rotations),
-                fit(grad_cov3Ds_precomp, cov3Ds_precomp), None)
+        return _input_grads(grads, ctx, sh, colors_precomp, scales, rotations, cov3Ds_precomp, None)
 
 
 def rasterize_views(means3D, means2D, opacities, settings_list, shs=None, colors_precomp=None, scales=None, rotations=None,
@@ -321,16 +324,10 @@ def rasterize_views(means3D, means2D, opacities, settings_list, shs=None, colors
     Returns (colors [V,3,H,W], radii [V,P]); gradients of the shared inputs are the sums over the views."""
     if len(settings_list) == 0:
         raise Exception("rasterize_views: empty settings list")
-    if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
-        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-    if ((scales is None or rotations is None) and cov3D_precomp is None) or (
-            (scales is not None or rotations is not None) and cov3D_precomp is not None):
-        raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-    e = _ABSENT
-    return _RasterizeGaussiansViews.apply(
-        means3D, means2D, e if shs is None else shs, e if colors_precomp is None else colors_precomp, opacities,
-        e if scales is None else scales, e if rotations is None else rotations, e if cov3D_precomp is None else cov3D_precomp,
-        list(settings_list))
+    _check_sources(shs, colors_precomp, scales, rotations, cov3D_precomp)
+    shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales, rotations, cov3D_precomp)
+    return _RasterizeGaussiansViews.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                                          list(settings_list))
 
 
 class _RasterizeGaussiansViewsChannels(torch.autograd.Function):
@@ -372,16 +369,8 @@ class _RasterizeGaussiansViewsChannels(torch.autograd.Function):
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj, rs.tanfovx,
             rs.tanfovy, grad_out_color, sh, rs.sh_degree, cam, geomBuffer, binningBuffer, imgBuffer, rs.debug,
             (values, xs, bg_extra), grad_out_extra, state=ctx.xstate)
-        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations, grad_x) = g
-        g_lo, g_hi = grad_x if split else (grad_x, None)
-
-        def fit(g, inp):
-            return g if inp.numel() != 0 else None
-
-        return (grad_means3D, grad_means2D, fit(grad_sh, sh), fit(grad_colors_precomp, colors_precomp),
-                grad_opacities.reshape(ctx.opacity_shape), fit(grad_scales, scales), fit(grad_rotations, rotations),
-                fit(grad_cov3Ds_precomp, cov3Ds_precomp), g_lo, g_hi, None, None, None, None)
+        g_lo, g_hi = g[8] if split else (g[8], None)
+        return _input_grads(g[:8], ctx, sh, colors_precomp, scales, rotations, cov3Ds_precomp, g_lo, g_hi, None, None, None, None)
 
 
 def rasterize_views_channels(means3D, means2D, opacities, settings_list, extra, bg_extra, extra_view_scale=None, shs=None,
@@ -406,11 +395,8 @@ def rasterize_views_channels(means3D, means2D, opacities, settings_list, extra, 
             warnings.warn(_why, UserWarning)
         else:
             raise RuntimeError(_why + ": torch.use_deterministic_algorithms(True, warn_only=True) or set_deterministic(False)")
-    if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
-        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-    if ((scales is None or rotations is None) and cov3D_precomp is None) or (
-            (scales is not None or rotations is not None) and cov3D_precomp is not None):
-        raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+    _check_sources(shs, colors_precomp, scales, rotations, cov3D_precomp)
+    shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales, rotations, cov3D_precomp)
     V, P = len(settings_list), means3D.shape[0]
     e = _ABSENT
     dev = means3D.device
@@ -440,6 +426,5 @@ def rasterize_views_channels(means3D, means2D, opacities, settings_list, extra, 
             xs = torch.cat([xs, xs.new_ones((V, nx - nx_user))], 1)
         xs = xs.contiguous()
     return _RasterizeGaussiansViewsChannels.apply(
-        means3D, means2D, e if shs is None else shs, e if colors_precomp is None else colors_precomp, opacities,
-        e if scales is None else scales, e if rotations is None else rotations, e if cov3D_precomp is None else cov3D_precomp,
-        lo.contiguous(), hi if hi is e else hi.contiguous(), bg_extra.contiguous(), xs, list(settings_list), nx_user)
+        means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, lo.contiguous(),
+        hi if hi is e else hi.contiguous(), bg_extra.contiguous(), xs, list(settings_list), nx_user)

@@ -10,6 +10,7 @@ call raises.
 import ctypes as C
 import os
 import threading
+import weakref as _weakref
 
 import torch
 
@@ -30,18 +31,51 @@ class GsrParams(C.Structure):
     ]
 
 
-# every symbol include/gsr.h declares (tests check the library exports all of them)
-SYMBOLS = ("gsr_geom_bytes", "gsr_geom_bytes_inference", "gsr_image_bytes", "gsr_binning_bytes", "gsr_forward_batch", "gsr_forward_stage1",
-           "gsr_forward_stage2", "gsr_backward_batch", "gsr_backward", "gsr_mark_visible", "gsr_query", "gsr_set_profiling",
-           "gsr_get_profile", "gsr_last_error", "gsr_version", "gsr_selftest", "gsr_forward_recolor", "gsr_forward_batch_channels", "gsr_d2h_count",
-           "gsr_clock_probe_launch", "gsr_wall_clock_khz", "gsr_last_list_pairs", "gsr_set_forward_half_views",
-           "gsr_set_backward_moments", "gsr_extra_state_bytes", "gsr_forward_batch_channels_train",
-           "gsr_backward_batch_channels", "gsr_backward_batch_det", "gsr_backward_det_bytes")
-
 GSR_RETRY = 1
 
 Q = dict(DEPTHS=1, MEANS2D=2, CONIC_OPACITY=3, RGB=4, TILES_TOUCHED=5, POINT_LIST=6, POINT_LIST_KEYS=7, RANGES=8,
          FINAL_T=9, N_CONTRIB=10, CLAMPED=11, TILE_NEED=12, DEPTH_SORT=13, LIST_PAIRS=14)
+
+_int, _i64, _size, _pp = C.c_int, C.c_int64, C.c_size_t, C.POINTER(GsrParams)
+_ARENAS = [_fp, _size, _fp, _size, _fp, _size]
+# the 12 leading arguments of the batch forwards: params, V, three arenas, radii, out_color, num_rendered, resume
+_FWD = [_pp, _int] + _ARENAS + [_fp, _fp, C.POINTER(_i64), _int]
+_FWD_X = _FWD + [_int, _int, _fp, _fp, _fp, _fp]          # + nx, extra_per_view, extra, extra_view_scale, bg_extra, out_extra
+# the 18 leading arguments of the batch backwards: params, V, radii, three arenas, dL_dpix and the eight gradient outputs
+_BWD = [_pp, _int, _fp] + _ARENAS + [_fp] * 9
+# symbol -> (restype, argtypes) of everything include/gsr.h declares with arguments
+_DECL = {
+    "gsr_geom_bytes": (_size, [_int]),
+    "gsr_geom_bytes_inference": (_size, [_int]),
+    "gsr_image_bytes": (_size, [_int, _int]),
+    "gsr_binning_bytes": (_size, [_i64]),
+    "gsr_extra_state_bytes": (_size, [_int, _int, _i64, _int]),
+    "gsr_backward_det_bytes": (_size, [_int, _int, _int, _int, _i64]),
+    "gsr_forward_batch": (_int, _FWD + [_fp]),
+    "gsr_forward_batch_channels": (_int, _FWD_X + [_fp]),
+    "gsr_forward_batch_channels_train": (_int, _FWD_X + [_fp, _size, _fp]),
+    "gsr_forward_stage1": (_int, [_pp, _fp, _size, _fp, _size, _fp, C.POINTER(_i64), _fp]),
+    "gsr_forward_stage2": (_int, [_pp] + _ARENAS + [_i64, _fp, _fp]),
+    "gsr_forward_recolor": (_int, [_pp, _int, _int] + _ARENAS + [_fp, _fp]),
+    "gsr_backward_batch": (_int, _BWD + [_fp]),
+    "gsr_backward_batch_det": (_int, _BWD + [_fp, _size, _fp]),
+    "gsr_backward_batch_channels": (_int, _BWD + [_int, _int, _fp, _fp, _fp, _fp, _size, _fp, _fp, _fp]),
+    "gsr_backward": (_int, [_pp, _fp, _i64] + _ARENAS + [_fp] * 9 + [_fp]),
+    "gsr_mark_visible": (_int, [_int, _fp, _fp, _fp, _fp, _fp]),
+    "gsr_query": (_int, [_pp, _int, _fp, _fp, _size, _fp, _i64, _fp, _size, _fp]),
+    "gsr_set_profiling": (None, [_int]),
+    "gsr_set_forward_half_views": (_int, [_int]),
+    "gsr_set_backward_moments": (_int, [_int]),
+    "gsr_get_profile": (_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _int]),
+    "gsr_selftest": (_int, [_fp]),
+    "gsr_d2h_count": (C.c_longlong, []),
+    "gsr_clock_probe_launch": (_int, [_fp, _int, _fp]),
+    "gsr_wall_clock_khz": (_int, []),
+    "gsr_last_list_pairs": (_int, [C.POINTER(_i64), _int]),
+}
+_RESTYPE_ONLY = {"gsr_last_error": C.c_char_p, "gsr_version": C.c_char_p}
+# every symbol include/gsr.h declares (tests check the library exports all of them)
+SYMBOLS = tuple(_DECL) + tuple(_RESTYPE_ONLY)
 
 
 def _load():
@@ -50,70 +84,10 @@ def _load():
             "diff_gaussian_rasterization: %s not found - build it with "
             "`python gaussian-pcloud-render_amd/build.py` (hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    lib.gsr_geom_bytes.restype = C.c_size_t
-    lib.gsr_geom_bytes.argtypes = [C.c_int]
-    lib.gsr_geom_bytes_inference.restype = C.c_size_t
-    lib.gsr_geom_bytes_inference.argtypes = [C.c_int]
-    lib.gsr_image_bytes.restype = C.c_size_t
-    lib.gsr_image_bytes.argtypes = [C.c_int, C.c_int]
-    lib.gsr_binning_bytes.restype = C.c_size_t
-    lib.gsr_binning_bytes.argtypes = [C.c_int64]
-    lib.gsr_forward_batch.restype = C.c_int
-    lib.gsr_forward_batch.argtypes = [C.POINTER(GsrParams), C.c_int, _fp, C.c_size_t, _fp, C.c_size_t, _fp, C.c_size_t, _fp, _fp,
-                                      C.POINTER(C.c_int64), C.c_int, _fp]
-    lib.gsr_forward_batch_channels.restype = C.c_int
-    lib.gsr_forward_batch_channels.argtypes = [C.POINTER(GsrParams), C.c_int, _fp, C.c_size_t, _fp, C.c_size_t, _fp, C.c_size_t,
-                                               _fp, _fp, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]
-    lib.gsr_forward_batch_channels_train.restype = C.c_int
-    lib.gsr_forward_batch_channels_train.argtypes = lib.gsr_forward_batch_channels.argtypes[:-1] + [_fp, C.c_size_t, _fp]
-    lib.gsr_extra_state_bytes.restype = C.c_size_t
-    lib.gsr_extra_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int]
-    lib.gsr_backward_batch_channels.restype = C.c_int
-    lib.gsr_backward_batch_channels.argtypes = ([C.POINTER(GsrParams), C.c_int, _fp, _fp, C.c_size_t, _fp, C.c_size_t, _fp, C.c_size_t]
-                                                + [_fp] * 9 + [C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_size_t, _fp, _fp, _fp])
-    lib.gsr_forward_stage1.restype = C.c_int
-    lib.gsr_forward_stage1.argtypes = [C.POINTER(GsrParams), _fp, C.c_size_t, _fp, C.c_size_t, _fp,
-                                       C.POINTER(C.c_int64), _fp]
-    lib.gsr_forward_stage2.restype = C.c_int
-    lib.gsr_forward_stage2.argtypes = [C.POINTER(GsrParams), _fp, C.c_size_t, _fp, C.c_size_t, _fp, C.c_size_t,
-                                       C.c_int64, _fp, _fp]
-    lib.gsr_forward_recolor.restype = C.c_int
-    lib.gsr_forward_recolor.argtypes = [C.POINTER(GsrParams), C.c_int, C.c_int, _fp, C.c_size_t, _fp, C.c_size_t, _fp, C.c_size_t, _fp,
-                                        _fp]
-    lib.gsr_backward_batch.restype = C.c_int
-    lib.gsr_backward_batch.argtypes = [C.POINTER(GsrParams), C.c_int, _fp, _fp, C.c_size_t, _fp, C.c_size_t, _fp,
-                                       C.c_size_t] + [_fp] * 9 + [_fp]
-    lib.gsr_backward_batch_det.restype = C.c_int
-    lib.gsr_backward_batch_det.argtypes = lib.gsr_backward_batch.argtypes[:-1] + [_fp, C.c_size_t, _fp]
-    lib.gsr_backward_det_bytes.restype = C.c_size_t
-    lib.gsr_backward_det_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64]
-    lib.gsr_backward.restype = C.c_int
-    lib.gsr_backward.argtypes = [C.POINTER(GsrParams), _fp, C.c_int64, _fp, C.c_size_t, _fp, C.c_size_t, _fp,
-                                 C.c_size_t] + [_fp] * 9 + [_fp]
-    lib.gsr_mark_visible.restype = C.c_int
-    lib.gsr_mark_visible.argtypes = [C.c_int, _fp, _fp, _fp, _fp, _fp]
-    lib.gsr_query.restype = C.c_int
-    lib.gsr_query.argtypes = [C.POINTER(GsrParams), C.c_int, _fp, _fp, C.c_size_t, _fp, C.c_int64, _fp, C.c_size_t, _fp]
-    lib.gsr_set_profiling.restype = None
-    lib.gsr_set_profiling.argtypes = [C.c_int]
-    lib.gsr_set_forward_half_views.restype = C.c_int
-    lib.gsr_set_forward_half_views.argtypes = [C.c_int]
-    lib.gsr_set_backward_moments.restype = C.c_int
-    lib.gsr_set_backward_moments.argtypes = [C.c_int]
-    lib.gsr_get_profile.restype = C.c_int
-    lib.gsr_get_profile.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
-    lib.gsr_selftest.restype = C.c_int
-    lib.gsr_selftest.argtypes = [_fp]
-    lib.gsr_d2h_count.restype = C.c_longlong
-    lib.gsr_d2h_count.argtypes = []
-    lib.gsr_clock_probe_launch.restype = C.c_int
-    lib.gsr_clock_probe_launch.argtypes = [_fp, C.c_int, _fp]
-    lib.gsr_wall_clock_khz.restype = C.c_int
-    lib.gsr_wall_clock_khz.argtypes = []
-    lib.gsr_last_list_pairs.restype = C.c_int
-    lib.gsr_last_list_pairs.argtypes = [C.POINTER(C.c_int64), C.c_int]
-    lib.gsr_last_error.restype = C.c_char_p
-    lib.gsr_version.restype = C.c_char_p
+    for name, (restype, argtypes) in _DECL.items():
+        getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
+    for name, restype in _RESTYPE_ONLY.items():
+        getattr(lib, name).restype = restype
     return lib
 
 
@@ -329,8 +303,6 @@ def _image_bytes(W, H):
 # either: autograd's own in-place checks have the same blind spot (a swapped storage, `t.data = other`, IS seen: the record
 # holds data_ptr / offset / shape / strides).  Off by default (below); when on, set_overlap(False) restores plain in-stream execution.  All outputs and arenas are allocated on the side stream and handed to the caller's stream with
 # record_stream, so torch's caching allocator never recycles them under a kernel that still runs.
-import weakref as _weakref
-
 # OPT-IN since round 5 (GSR_OVERLAP=1 or set_overlap(True)): what the overlap is worth depends on which hardware queues the runtime
 # binds the side streams to at their first launch -- 1 250-1 360 frames/s in most processes, 1 010-1 160 in some, in-order 985 --
 # which a process can neither see nor choose, and the reference's literal caller (fresh settings tensors per call,
@@ -454,6 +426,80 @@ class _OnSideStream:
         return False
 
 
+def _extra_layout(extra, P, V, device):
+    """The `extra` triple (values, view_scale or None, bg) of a channels forward or backward, checked against P points and V views:
+    (nx, extra_per_view of gsr.h, values -- the split pair as one flat tensor --, view_scale, bg)."""
+    xv, xs, xb = extra
+    if isinstance(xv, (tuple, list)):
+        # split layout (gsr.h extra_per_view = 2): channels 0..3 shared by the views [P,4], channels 4..7 per view [V,P,4]
+        lo, hi = xv
+        if tuple(lo.shape) != (P, 4) or tuple(hi.shape) != (V, P, 4):
+            raise RuntimeError("split extra channels must have shapes (num_points, 4) and (num_views, num_points, 4)")
+        xv = torch.cat([_f32c(lo, device, "extra").reshape(-1), _f32c(hi, device, "extra").reshape(-1)])
+        x_per_view, nx = 2, 8
+    else:
+        x_per_view = int(xv.dim() == 3)
+        nx = int(xv.shape[-1]) if xv.dim() in (2, 3) else -1
+        if nx not in (4, 8) or xv.shape[-2] != P or (x_per_view and xv.shape[0] != V):
+            raise RuntimeError("extra channels must have shape (num_points, 4 or 8) or (num_views, num_points, 4 or 8)")
+    if xb.numel() != nx or (xs is not None and tuple(xs.shape) != (V, nx)):
+        raise RuntimeError("bg_extra must have nx entries and view_scale shape (V, nx)")
+    return nx, x_per_view, xv, xs, xb
+
+
+def _extra_f32(xv, xs, xb, device):
+    return (_f32c(xv, device, "extra"), None if xs is None else _f32c(xs, device, "extra_view_scale"),
+            _f32c(xb.reshape(-1), device, "bg_extra"))
+
+
+def _grad_tensors(P, M, device, has_sr, alloc=None):
+    """The eight outputs of a backward in the reference's order (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh,
+    dL_dscales, dL_drotations).  Nothing is cleared: the per-Gaussian backward kernel writes every output for every Gaussian (the
+    reference zero-fills nine tensors, rasterize_points.cu:151-159), and the accumulation records live in the geometry arena --
+    except where no kernel writes: P = 0, and scales / rotations that were not given.  alloc: see rasterize_gaussians_backward_batch."""
+    new = (alloc or torch.empty) if P != 0 else torch.zeros
+    sr = new if has_sr else torch.zeros
+    return (new((P, 3), dtype=_F32, device=device), new((P, 3), dtype=_F32, device=device), new((P, 1), dtype=_F32, device=device),
+            new((P, 3), dtype=_F32, device=device), new((P, 6), dtype=_F32, device=device), new((P, M, 3), dtype=_F32, device=device),
+            sr((P, 3), dtype=_F32, device=device), sr((P, 4), dtype=_F32, device=device))
+
+
+def _arena_args(geom, binning, image):
+    return (geom.data_ptr(), geom.numel(), binning.data_ptr(), binning.numel(), image.data_ptr(), image.numel())
+
+
+def _bwd_inputs(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices,
+                tan_fovx, tan_fovy, dL_dout_color, sh, degree, camposs, debug):
+    """(params, tensors to keep, radii, dL_dout_color) of a general-path backward, converted"""
+    H, W = int(dL_dout_color.shape[2]), int(dL_dout_color.shape[3])
+    # (opacity lives in the geom arena; the pointer only has to be non-NULL: means3D stands in)
+    p, keep = _params(background, means3D, colors, means3D, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
+                      projmatrices, tan_fovx, tan_fovy, H, W, sh, degree, camposs, False, debug, True)
+    return p, keep, radii.contiguous(), _f32c(dL_dout_color, means3D.device, "dL_dout_color")
+
+
+def _bwd_head(p, V, radii, arenas, dpix, g):
+    """The 18 leading arguments of the three batch backwards.  arenas: (geom, bytes, binning, bytes, image, bytes); g: _grad_tensors
+    (the C ABI takes opacity before colour)."""
+    return (C.byref(p), V, radii.data_ptr()) + arenas + (
+        dpix.data_ptr(), g[0].data_ptr(), g[2].data_ptr(), g[1].data_ptr(), g[3].data_ptr(), g[4].data_ptr(), _ptr(g[5]), g[6].data_ptr(),
+        g[7].data_ptr())
+
+
+def _colour_backward(p, V, radii, arenas, dpix, grads, W, H, device, deterministic, pairs):
+    """One colour backward into `grads`, through gsr_backward_batch or (deterministic) gsr_backward_batch_det with a scratch block
+    for lists of `pairs` pairs per view."""
+    head = _bwd_head(p, V, radii, arenas, dpix, grads)
+    stream = _stream_handle(device)
+    if deterministic:
+        CALLS["backward_det"] += 1
+        scratch = det_scratch(V, p.P, W, H, pairs, arenas[3], device)
+        _check(lib.gsr_backward_batch_det(*head, scratch.data_ptr(), scratch.numel(), stream))
+    else:
+        CALLS["backward"] += 1
+        _check(lib.gsr_backward_batch(*head, stream))
+
+
 def rasterize_gaussians_batch(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                               viewmatrices, projmatrices, tan_fovx, tan_fovy, image_height, image_width, sh, degree,
                               camposs, prefiltered, debug, need_backward=True, capacity=None, extra=None):
@@ -474,24 +520,7 @@ def rasterize_gaussians_batch(background, means3D, colors, opacity, scales, rota
         raise RuntimeError("viewmatrices, projmatrices and camposs must describe the same number of views (>= 1)")
     P, H, W = means3D.shape[0], int(image_height), int(image_width)
     byte = dict(dtype=torch.uint8, device=device)
-    nx = 0
-    xv = xs = xb = None
-    if extra is not None:
-        xv, xs, xb = extra
-        if isinstance(xv, (tuple, list)):
-            # split layout (gsr.h extra_per_view = 2): channels 0..3 shared by the views [P,4], channels 4..7 per view [V,P,4]
-            lo, hi = xv
-            if tuple(lo.shape) != (P, 4) or tuple(hi.shape) != (V, P, 4):
-                raise RuntimeError("split extra channels must have shapes (num_points, 4) and (num_views, num_points, 4)")
-            xv = torch.cat([_f32c(lo, device, "extra").reshape(-1), _f32c(hi, device, "extra").reshape(-1)])
-            x_per_view, nx = 2, 8
-        else:
-            x_per_view = int(xv.dim() == 3)
-            nx = int(xv.shape[-1]) if xv.dim() in (2, 3) else -1
-            if nx not in (4, 8) or xv.shape[-2] != P or (x_per_view and xv.shape[0] != V):
-                raise RuntimeError("extra channels must have shape (num_points, 4 or 8) or (num_views, num_points, 4 or 8)")
-        if xb.numel() != nx or (xs is not None and tuple(xs.shape) != (V, nx)):
-            raise RuntimeError("bg_extra must have nx entries and view_scale shape (V, nx)")
+    nx, x_per_view, xv, xs, xb = (0, 0, None, None, None) if extra is None else _extra_layout(extra, P, V, device)
     if P == 0:  # rasterize_points.cu:81: the zero image (not the background) is returned
         e = torch.empty((0,), **byte)
         r0 = ([0] * V, torch.zeros((V, 3, H, W), dtype=torch.float32, device=device),
@@ -509,9 +538,7 @@ def rasterize_gaussians_batch(background, means3D, colors, opacity, scales, rota
         ov = _NO_CONTEXT
     with _on_device(device), ov:
         if nx:
-            xv = _f32c(xv, device, "extra")
-            xb = _f32c(xb.reshape(-1), device, "bg_extra")
-            xs = None if xs is None else _f32c(xs, device, "extra_view_scale")
+            xv, xs, xb = _extra_f32(xv, xs, xb, device)
         f32 = dict(dtype=torch.float32, device=device)
         out_extra = torch.empty((V, nx, H, W), **f32) if nx else None
         # every pixel and every radius is written by the kernels (the reference fills both with zeros first)
@@ -541,42 +568,33 @@ def rasterize_gaussians_batch(background, means3D, colors, opacity, scales, rota
             if capacity is None:
                 capacity = 16 * P      # first batch of this configuration: a guess, corrected by the retry below
             def submit(binning, resume):
-                if nx and need_backward:
-                    # the extra-state block is sized with the binning arena (both grow on a retry)
-                    n = int(capacity) if not resume else need_pairs[0]
-                    xstate[0] = torch.empty((V * lib.gsr_extra_state_bytes(W, H, n, nx) + 256,), **byte)
-                    return lib.gsr_forward_batch_channels_train(
-                        C.byref(p), V, geom.data_ptr(), geom.numel(), img.data_ptr(), img.numel(), binning.data_ptr(),
-                        binning.numel(), radii.data_ptr(), out_color.data_ptr(), counts, resume, nx, x_per_view, xv.data_ptr(),
-                        None if xs is None else xs.data_ptr(), xb.data_ptr(), out_extra.data_ptr(), xstate[0].data_ptr(),
-                        xstate[0].numel(), stream)
-                if nx:
-                    return lib.gsr_forward_batch_channels(
-                        C.byref(p), V, geom.data_ptr(), geom.numel(), img.data_ptr(), img.numel(), binning.data_ptr(),
-                        binning.numel(), radii.data_ptr(), out_color.data_ptr(), counts, resume, nx, x_per_view, xv.data_ptr(),
-                        None if xs is None else xs.data_ptr(), xb.data_ptr(), out_extra.data_ptr(), stream)
-                return lib.gsr_forward_batch(C.byref(p), V, geom.data_ptr(), geom.numel(), img.data_ptr(), img.numel(),
-                                             binning.data_ptr(), binning.numel(), radii.data_ptr(), out_color.data_ptr(), counts,
-                                             resume, stream)
+                head = (C.byref(p), V, geom.data_ptr(), geom.numel(), img.data_ptr(), img.numel(), binning.data_ptr(), binning.numel(),
+                        radii.data_ptr(), out_color.data_ptr(), counts, resume)
+                if not nx:
+                    return lib.gsr_forward_batch(*head, stream)
+                x = (nx, x_per_view, xv.data_ptr(), _ptr(xs), xb.data_ptr(), out_extra.data_ptr())
+                if not need_backward:
+                    return lib.gsr_forward_batch_channels(*head, *x, stream)
+                # the extra-state block is sized with the binning arena (both grow on a retry)
+                n = int(capacity) if not resume else need_pairs[0]
+                xstate[0] = torch.empty((V * lib.gsr_extra_state_bytes(W, H, n, nx) + 256,), **byte)
+                return lib.gsr_forward_batch_channels_train(*head, *x, xstate[0].data_ptr(), xstate[0].numel(), stream)
 
             need_pairs = [0]
             binning = torch.empty((V * lib.gsr_binning_bytes(int(capacity)),), **byte)
             rc = submit(binning, 0)
             if rc == GSR_RETRY:
-                pairs = (C.c_int64 * V)()
-                _check(lib.gsr_last_list_pairs(pairs, V))
-                need = need_pairs[0] = int(max(pairs) * CAP_SLACK) + 4096
+                need = need_pairs[0] = int(last_list_pairs(V) * CAP_SLACK) + 4096
                 binning = torch.empty((V * lib.gsr_binning_bytes(need),), **byte)
                 rc = submit(binning, 1)
             _check(rc)
             if xstate[0] is not None:
                 geom._gsr_extra_state = (xstate[0], nx, x_per_view)
         ov.give(out_color, radii, geom, binning, img, out_extra, xstate[0])
-        pairs = (C.c_int64 * V)()
-        _check(lib.gsr_last_list_pairs(pairs, V))   # (same host thread as the forward call: the count is kept per thread)
+        pairs = last_list_pairs(V)   # (same host thread as the forward call: the count is kept per thread)
     del keep
     counts = [int(c) for c in counts]
-    _note_counts(key, [int(c) for c in pairs])      # the arena holds the lists: sized by their pairs, not by num_rendered
+    _note_counts(key, (pairs,))      # the arena holds the lists: sized by their pairs, not by num_rendered
     if nx:
         return counts, out_color, radii, geom, binning, img, out_extra
     return counts, out_color, radii, geom, binning, img
@@ -606,21 +624,14 @@ def _slab_layout(P, W, H, need_backward, capacity):
     return g, i, b
 
 
-def forward_view(rs, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, need_backward):
-    """One view through gsr_forward_batch.  Returns (num_rendered, color [3,H,W], radii [P], arenas, layout) -- arenas: ONE uint8
-    tensor holding the geometry, image and binning arenas at the byte offsets 0, layout[0], layout[0] + layout[1] -- or None when
-    the call has to take the general path."""
-    device = means3D.device
-    P = means3D.shape[0]
-    if _OVERLAP_ON or device.type != "cuda" or means3D.dim() != 2 or P == 0:
-        return None
-    H, W = int(rs.image_height), int(rs.image_width)
-    hint = _CAP_HINT.get((device.index, P, W, H))
-    if hint is None or device.index is None or device.index != torch.cuda.current_device():
-        return None
+def _view_params(rs, tensors, W, H, prefiltered, need_backward):
+    """GsrParams of one view from the eleven input tensors in the order of its pointer fields (bg ... campos), as they come: only
+    a tensor that is not float32, on the device and contiguous is converted.  Returns (params, M, the converted tensors -- to be kept
+    until the call has been enqueued)."""
+    device = tensors[1].device
     keep = []
     ptrs = []
-    for t in (rs.bg, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, rs.viewmatrix, rs.projmatrix, rs.campos):
+    for t in tensors:
         if t.numel() == 0:
             ptrs.append(None)
             continue
@@ -628,9 +639,26 @@ def forward_view(rs, means3D, sh, colors, opacity, scales, rotations, cov3D_prec
             t = _f32c(t, device, "an input")
             keep.append(t)
         ptrs.append(t.data_ptr())
-    M = int(sh.shape[1]) if ptrs[2] is not None else 0
-    p = GsrParams(P, int(rs.sh_degree), M, W, H, float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier),
-                  int(bool(rs.prefiltered)), 0, int(need_backward), int(reference_lists()), *ptrs)
+    M = int(tensors[2].shape[1]) if ptrs[2] is not None else 0
+    p = GsrParams(tensors[1].shape[0], int(rs.sh_degree), M, W, H, float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier),
+                  prefiltered, 0, need_backward, int(reference_lists()), *ptrs)
+    return p, M, keep
+
+
+def forward_view(rs, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, need_backward):
+    """One view through gsr_forward_batch.  Returns (num_rendered, color [3,H,W], radii [P], arenas, layout) -- arenas: ONE uint8
+    tensor holding the geometry, image and binning arenas at the byte offsets 0, layout[0], layout[0] + layout[1] -- or None when
+    the call has to take the general path."""
+    device = means3D.device
+    P = means3D.shape[0]
+    if _OVERLAP_ON or device.type != "cuda" or means3D.dim() != 2 or means3D.shape[1] != 3 or P == 0:
+        return None
+    H, W = int(rs.image_height), int(rs.image_width)
+    hint = _CAP_HINT.get((device.index, P, W, H))
+    if hint is None or device.index is None or device.index != torch.cuda.current_device():
+        return None
+    p, _, keep = _view_params(rs, (rs.bg, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, rs.viewmatrix, rs.projmatrix,
+                                   rs.campos), W, H, int(bool(rs.prefiltered)), int(need_backward))
     capacity = (int(hint * CAP_SLACK) + 4096 + _CAP_QUANTUM - 1) // _CAP_QUANTUM * _CAP_QUANTUM
     g, i, b = _slab_layout(P, W, H, need_backward, capacity)
     arenas = torch.empty((g + i + b,), dtype=torch.uint8, device=device)
@@ -641,7 +669,7 @@ def forward_view(rs, means3D, sh, colors, opacity, scales, rotations, cov3D_prec
         counts = _TLS_FAST.counts = (C.c_int64 * 1)()
         _TLS_FAST.pairs = (C.c_int64 * 1)()
     base = arenas.data_ptr()
-    stream = _raw_stream(device.index) if _raw_stream is not None else torch.cuda.current_stream(device).cuda_stream
+    stream = _stream_handle(device)
     rc = lib.gsr_forward_batch(C.byref(p), 1, base, g, base + g, i, base + g + i, b, radii.data_ptr(), color.data_ptr(), counts, 0, stream)
     pairs = _TLS_FAST.pairs
     if rc == GSR_RETRY:
@@ -653,8 +681,7 @@ def forward_view(rs, means3D, sh, colors, opacity, scales, rotations, cov3D_prec
         grown[:g + i].copy_(arenas[:g + i])
         arenas, b, base = grown, b2, grown.data_ptr()
         rc = lib.gsr_forward_batch(C.byref(p), 1, base, g, base + g, i, base + g + i, b, radii.data_ptr(), color.data_ptr(), counts, 1, stream)
-    if rc != 0:
-        raise RuntimeError(lib.gsr_last_error().decode("utf-8", "replace"))
+    _check(rc)
     _check(lib.gsr_last_list_pairs(pairs, 1))
     _note_counts((device.index, P, W, H), (int(pairs[0]),))
     return int(counts[0]), color, radii, arenas, (g, i, b)
@@ -665,48 +692,18 @@ def backward_view(rs, means3D, radii, colors, scales, rotations, cov3D_precomp, 
     """Backward of forward_view (gsr_backward_batch, V = 1): the reference's 8-tuple.  deterministic: gsr_backward_batch_det with a
     scratch block for lists of `pairs` pairs (None: bounded from the binning arena's size)."""
     device = means3D.device
-    P = means3D.shape[0]
     H, W = int(grad_color.shape[-2]), int(grad_color.shape[-1])
-    keep = []
-    ptrs = []
-    for t in (rs.bg, means3D, sh, colors, means3D, scales, rotations, cov3D_precomp, rs.viewmatrix, rs.projmatrix, rs.campos):
-        if t.numel() == 0:       # (opacity lives in the geometry arena; the pointer only has to be non-NULL: means3D stands in)
-            ptrs.append(None)
-            continue
-        if t.dtype is not _F32 or t.device != device or not t.is_contiguous():
-            t = _f32c(t, device, "an input")
-            keep.append(t)
-        ptrs.append(t.data_ptr())
-    M = int(sh.shape[1]) if ptrs[2] is not None else 0
-    p = GsrParams(P, int(rs.sh_degree), M, W, H, float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier), 0, 0, 1,
-                  int(reference_lists()), *ptrs)
+    # (opacity lives in the geometry arena; the pointer only has to be non-NULL: means3D stands in)
+    p, M, keep = _view_params(rs, (rs.bg, means3D, sh, colors, means3D, scales, rotations, cov3D_precomp, rs.viewmatrix, rs.projmatrix,
+                                   rs.campos), W, H, 0, 1)
     if grad_color.dtype is not _F32 or grad_color.device != device or not grad_color.is_contiguous():
         grad_color = _f32c(grad_color, device, "dL_dout_color")
-    z = dict(dtype=_F32, device=device)
-    has_sr = ptrs[5] is not None
-    g_means2D, g_colors, g_opacity = torch.empty((P, 3), **z), torch.empty((P, 3), **z), torch.empty((P, 1), **z)
-    g_means3D, g_cov3D, g_sh = torch.empty((P, 3), **z), torch.empty((P, 6), **z), torch.empty((P, M, 3), **z)
-    g_scales = torch.empty((P, 3), **z) if has_sr else torch.zeros((P, 3), **z)
-    g_rot = torch.empty((P, 4), **z) if has_sr else torch.zeros((P, 4), **z)
+    grads = _grad_tensors(means3D.shape[0], M, device, scales.numel() != 0)
     g, i, b = layout
     base = arenas.data_ptr()
     with _on_device(device):
-        stream = _raw_stream(device.index) if _raw_stream is not None and device.index is not None else torch.cuda.current_stream(device).cuda_stream
-        if deterministic:
-            CALLS["backward_det"] += 1
-            scratch = det_scratch(1, P, W, H, pairs, b, device)
-            rc = lib.gsr_backward_batch_det(C.byref(p), 1, radii.data_ptr(), base, g, base + g + i, b, base + g, i, grad_color.data_ptr(),
-                                            g_means2D.data_ptr(), g_opacity.data_ptr(), g_colors.data_ptr(), g_means3D.data_ptr(),
-                                            g_cov3D.data_ptr(), g_sh.data_ptr() if M else None, g_scales.data_ptr(), g_rot.data_ptr(),
-                                            scratch.data_ptr(), scratch.numel(), stream)
-        else:
-            CALLS["backward"] += 1
-            rc = lib.gsr_backward_batch(C.byref(p), 1, radii.data_ptr(), base, g, base + g + i, b, base + g, i, grad_color.data_ptr(),
-                                        g_means2D.data_ptr(), g_opacity.data_ptr(), g_colors.data_ptr(), g_means3D.data_ptr(),
-                                        g_cov3D.data_ptr(), g_sh.data_ptr() if M else None, g_scales.data_ptr(), g_rot.data_ptr(), stream)
-    if rc != 0:
-        raise RuntimeError(lib.gsr_last_error().decode("utf-8", "replace"))
-    return g_means2D, g_colors, g_opacity, g_means3D, g_cov3D, g_sh, g_scales, g_rot
+        _colour_backward(p, 1, radii, (base, g, base + g + i, b, base + g, i), grad_color, grads, W, H, device, deterministic, pairs)
+    return grads
 
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
@@ -744,7 +741,7 @@ def recolor(background, means3D, colors, sh, degree, campos, image_height, image
                 raise RuntimeError("recolor: per-view colours must have shape (V, P, 3)")
             _check(lib.gsr_forward_recolor(C.byref(p), V, per_view, geomBuffer.data_ptr(), geomBuffer.numel(), binningBuffer.data_ptr(),
                                            binningBuffer.numel(), imgBuffer.data_ptr(), imgBuffer.numel(),
-                                           out_color.data_ptr(), torch.cuda.current_stream(device).cuda_stream))
+                                           out_color.data_ptr(), _stream_handle(device)))
             del keep
     return out_color[0] if single else out_color
 
@@ -763,43 +760,17 @@ def rasterize_gaussians_backward_batch(background, means3D, radii, colors, scale
     P = means3D.shape[0]
     V, H, W = int(dL_dout_color.shape[0]), int(dL_dout_color.shape[2]), int(dL_dout_color.shape[3])
     M = int(sh.shape[1]) if sh.numel() != 0 and sh.shape[0] != 0 else 0
-    z = dict(dtype=torch.float32, device=device)
-    # Nothing is cleared here: the per-Gaussian backward kernel writes every output for every Gaussian (the reference
-    # zero-fills nine tensors, rasterize_points.cu:151-159), and the accumulation records live in the geometry arena.
-    has_sr = scales.numel() != 0 and P != 0
-    e_or_z = (_alloc or torch.empty) if P != 0 else torch.zeros
-    dL_dmeans2D = e_or_z((P, 3), **z)
-    dL_dcolors = e_or_z((P, 3), **z)
-    dL_dopacity = e_or_z((P, 1), **z)
-    dL_dmeans3D = e_or_z((P, 3), **z)
-    dL_dcov3D = e_or_z((P, 6), **z)
-    dL_dsh = e_or_z((P, M, 3), **z)
-    dL_dscales = e_or_z((P, 3), **z) if has_sr else torch.zeros((P, 3), **z)
-    dL_drotations = e_or_z((P, 4), **z) if has_sr else torch.zeros((P, 4), **z)
+    grads = _grad_tensors(P, M, device, scales.numel() != 0, _alloc)
     if deterministic is None:
         deterministic = deterministic_active()
     if P != 0:
         with _on_device(device):
-            stream = _stream_handle(device)
-            # (opacity lives in the geom arena; the pointer only has to be non-NULL: means3D stands in)
-            p, keep = _params(background, means3D, colors, means3D, scales, rotations, scale_modifier,
-                              cov3D_precomp, viewmatrices, projmatrices, tan_fovx, tan_fovy, H, W, sh, degree, camposs, False,
-                              debug, True)
-            dpix = _f32c(dL_dout_color, device, "dL_dout_color")
-            radii_c = radii.contiguous()
-            common = (C.byref(p), V, radii_c.data_ptr(), geomBuffer.data_ptr(), geomBuffer.numel(), binningBuffer.data_ptr(),
-                      binningBuffer.numel(), imageBuffer.data_ptr(), imageBuffer.numel(), dpix.data_ptr(), dL_dmeans2D.data_ptr(),
-                      dL_dopacity.data_ptr(), dL_dcolors.data_ptr(), dL_dmeans3D.data_ptr(), dL_dcov3D.data_ptr(), _ptr(dL_dsh),
-                      dL_dscales.data_ptr(), dL_drotations.data_ptr())
-            if deterministic:
-                CALLS["backward_det"] += 1
-                scratch = det_scratch(V, P, W, H, pairs, binningBuffer.numel(), device)
-                _check(lib.gsr_backward_batch_det(*common, scratch.data_ptr(), scratch.numel(), stream))
-            else:
-                CALLS["backward"] += 1
-                _check(lib.gsr_backward_batch(*common, stream))
+            p, keep, radii_c, dpix = _bwd_inputs(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
+                                                 viewmatrices, projmatrices, tan_fovx, tan_fovy, dL_dout_color, sh, degree, camposs, debug)
+            _colour_backward(p, V, radii_c, _arena_args(geomBuffer, binningBuffer, imageBuffer), dpix, grads, W, H, device,
+                             deterministic, pairs)
             del keep
-    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+    return grads
 
 
 def extra_state(geomBuffer):
@@ -819,47 +790,29 @@ def rasterize_gaussians_backward_channels_batch(background, means3D, radii, colo
     P = means3D.shape[0]
     V, H, W = int(dL_dout_color.shape[0]), int(dL_dout_color.shape[2]), int(dL_dout_color.shape[3])
     M = int(sh.shape[1]) if sh.numel() != 0 and sh.shape[0] != 0 else 0
-    xv, xs, xb = extra
-    split = isinstance(xv, (tuple, list))
-    nx = 8 if split else int(xv.shape[-1])
-    x_per_view = 2 if split else int(xv.dim() == 3)
-    z = dict(dtype=torch.float32, device=device)
-    has_sr = scales.numel() != 0 and P != 0
-    e_or_z = torch.empty if P != 0 else torch.zeros
-    g = [e_or_z((P, 3), **z), e_or_z((P, 3), **z), e_or_z((P, 1), **z), e_or_z((P, 3), **z), e_or_z((P, 6), **z), e_or_z((P, M, 3), **z),
-         e_or_z((P, 3), **z) if has_sr else torch.zeros((P, 3), **z), e_or_z((P, 4), **z) if has_sr else torch.zeros((P, 4), **z)]
-    n_out = P * 4 * (1 + V) if split else P * nx * (V if x_per_view else 1)
-    gx = e_or_z((n_out,), **z)
+    nx, x_per_view, xv, xs, xb = _extra_layout(extra, P, V, device)
+    grads = _grad_tensors(P, M, device, scales.numel() != 0)
+    n_out = P * 4 * (1 + V) if x_per_view == 2 else P * nx * (V if x_per_view else 1)
+    gx = (torch.empty if P != 0 else torch.zeros)((n_out,), dtype=_F32, device=device)
     if P != 0:
         st = state if state is not None else extra_state(geomBuffer)
         if st is None:
             raise RuntimeError("backward_channels: the forward kept no extra-channel state (a channels forward with need_backward=True)")
         with _on_device(device):
-            stream = _stream_handle(device)
-            p, keep = _params(background, means3D, colors, means3D, scales, rotations, scale_modifier,
-                              cov3D_precomp, viewmatrices, projmatrices, tan_fovx, tan_fovy, H, W, sh, degree, camposs, False,
-                              debug, True)
-            if split:
-                xv_c = torch.cat([_f32c(xv[0], device, "extra").reshape(-1), _f32c(xv[1], device, "extra").reshape(-1)])
-            else:
-                xv_c = _f32c(xv, device, "extra")
-            xb_c = _f32c(xb.reshape(-1), device, "bg_extra")
-            xs_c = None if xs is None else _f32c(xs, device, "extra_view_scale")
-            dpix = _f32c(dL_dout_color, device, "dL_dout_color")
+            p, keep, radii_c, dpix = _bwd_inputs(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
+                                                 viewmatrices, projmatrices, tan_fovx, tan_fovy, dL_dout_color, sh, degree, camposs, debug)
+            xv, xs, xb = _extra_f32(xv, xs, xb, device)
             dx = _f32c(dL_dout_extra, device, "dL_dout_extra")
-            radii_c = radii.contiguous()
             _check(lib.gsr_backward_batch_channels(
-                C.byref(p), V, radii_c.data_ptr(), geomBuffer.data_ptr(), geomBuffer.numel(), binningBuffer.data_ptr(),
-                binningBuffer.numel(), imageBuffer.data_ptr(), imageBuffer.numel(), dpix.data_ptr(), g[0].data_ptr(), g[2].data_ptr(),
-                g[1].data_ptr(), g[3].data_ptr(), g[4].data_ptr(), _ptr(g[5]), g[6].data_ptr(), g[7].data_ptr(), nx, x_per_view,
-                xv_c.data_ptr(), None if xs_c is None else xs_c.data_ptr(), xb_c.data_ptr(), st[0].data_ptr(), st[0].numel(),
-                dx.data_ptr(), gx.data_ptr(), stream))
+                *_bwd_head(p, V, radii_c, _arena_args(geomBuffer, binningBuffer, imageBuffer), dpix, grads), nx, x_per_view,
+                xv.data_ptr(), _ptr(xs), xb.data_ptr(), st[0].data_ptr(), st[0].numel(), dx.data_ptr(), gx.data_ptr(),
+                _stream_handle(device)))
             del keep
-    if split:
+    if x_per_view == 2:
         gx = (gx[:P * 4].reshape(P, 4), gx[P * 4:].reshape(V, P, 4))
     else:
         gx = gx.reshape((V, P, nx) if x_per_view else (P, nx))
-    return tuple(g) + (gx,)
+    return grads + (gx,)
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
@@ -885,7 +838,7 @@ def mark_visible(means3D, viewmatrix, projmatrix):
             v = _f32c(viewmatrix, device, "viewmatrix")
             pr = _f32c(projmatrix, device, "projmatrix")
             _check(lib.gsr_mark_visible(P, m.data_ptr(), v.data_ptr(), pr.data_ptr(), present.data_ptr(),
-                                        torch.cuda.current_stream(device).cuda_stream))
+                                        _stream_handle(device)))
     return present
 
 
@@ -923,7 +876,7 @@ def query(name, P, W, H, R, geom, binning, img, view=0, n_views=1):
         _check(lib.gsr_query(C.byref(p), Q[name], geom.data_ptr() + view * g_stride,
                              (binning.data_ptr() + view * b_stride) if binning.numel() else None, b_stride + 256,
                              img.data_ptr() + view * i_stride, int(R), out.data_ptr(), out.numel() * out.element_size(),
-                             torch.cuda.current_stream(geom.device).cuda_stream))
+                             _stream_handle(geom.device)))
     return out
 
 
@@ -948,7 +901,6 @@ class ClockProbe:
     clock per launch, in MHz (include/gsr.h gsr_clock_probe_launch)."""
 
     def __init__(self, device, capacity=256, iters=256):
-        import threading
         self.device, self.iters, self.n, self._mu = device, int(iters), 0, threading.Lock()
         with torch.cuda.device(device):
             self.buf = torch.zeros((capacity, 2), dtype=torch.int64, device=device)
@@ -976,7 +928,7 @@ class ClockProbe:
 
 def selftest(device):
     with torch.cuda.device(device):
-        _check(lib.gsr_selftest(torch.cuda.current_stream(device).cuda_stream))
+        _check(lib.gsr_selftest(_stream_handle(device)))
 
 
 def set_backward_moments(mode):

@@ -326,3 +326,24 @@ def test_short_host_path_equals_the_general_path_and_survives_a_grown_frame(gpu_
     finally:
         N.forward_view = real
     assert d._C.forward_view is real
+
+
+def test_short_host_path_refuses_a_means3D_that_is_not_P_by_3(gpu_device):
+    """With a warm capacity hint the per-view call takes the short path, which hands raw pointers to the C ABI: a [P, 4] means3D has to
+    fall back to the general path and raise its shape error, not be read as P x 3 floats."""
+    from diff_gaussian_rasterization import GaussianRasterizer, _native as N
+    dev = gpu_device
+    s = build_scene("capsule_circle")
+    L = dict(means3D=_leaf(s.means3D, dev), shs=_leaf(s.shs, dev), opacities=_leaf(s.opacities.reshape(-1, 1), dev),
+             scales=_leaf(s.scales, dev), rotations=_leaf(s.rotations, dev))
+    L["means2D"] = torch.zeros_like(L["means3D"])
+    N.reset_capacity_hints()
+    with torch.no_grad():
+        for _ in range(2):                     # (the first call sets the capacity hint, the second takes the short path)
+            GaussianRasterizer(_settings(s, dev))(**L)
+        assert N._CAP_HINT.get(N._cap_key(dev, s.P, s.W, s.H)) is not None
+        L["means3D"] = torch.cat([L["means3D"].detach(), torch.ones((s.P, 1), device=dev)], 1).contiguous()
+        assert N.forward_view(_settings(s, dev), L["means3D"], L["shs"], torch.Tensor([]), L["opacities"], L["scales"], L["rotations"],
+                              torch.Tensor([]), False) is None
+        with pytest.raises(RuntimeError, match=r"means3D must have dimensions \(num_points, 3\)"):
+            GaussianRasterizer(_settings(s, dev))(**L)
