@@ -218,6 +218,26 @@ def test_batch_edge_cases_vs_oracle(oracle, gpu_device):
     grads = N.rasterize_gaussians_backward_batch(args[0], args[1], radii, args[2], args[4], args[5], 1.0, args[7], args[8], args[9],
                                                  args[10], args[11], dL, args[14], args[15], args[16], geom, binning, img, False)
     assert all(torch.isfinite(x).all() for x in grads)
+    # the gradients of the 17 views (one of them empty) against the summed oracle gradients -- or, after an expf threshold flip
+    # between glibc and ocml, the summed reference-build gradients -- like test_batch_forward_backward_vs_oracle
+    names = ("dL_dmean2D", "dL_dcolor", "dL_dopacity", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot")
+    gp = {n: x.cpu().numpy() for n, x in zip(names, grads)}
+    ones = np.ones((3, H, W), np.float32)
+    scenes = [util.scene_from(g, v, W, H, bg=(0.2, 0.5, 0.7)) for v in vs]
+    total, flips = None, 0
+    for v, s in enumerate(scenes):
+        o, go = oracle.forward_backward(s, ones)
+        flips += int((np.abs(color[v].cpu().numpy() - o["out_color"]).max(axis=0) > 1e-4).sum())
+        go = {k: go[k].astype(np.float64) for k in names}
+        total = go if total is None else {k: total[k] + go[k] for k in total}
+    if flips:
+        ref = util.reference_build()
+        total = None
+        for s in scenes:
+            _, gr = ref.forward_backward(s, ones)
+            gr = {k: gr[k].astype(np.float64) for k in names}
+            total = gr if total is None else {k: total[k] + gr[k] for k in total}
+    check_grads(gp, total, "17 views (one empty) vs summed %s gradients" % ("reference-build" if flips else "oracle"))
     # empty cloud: zero images (not the background), like the reference's P == 0 shortcut
     e = torch.empty(0)
     z = torch.zeros((0, 3), device=dev)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import util
+from grad_ladder import Float64, assert_exits_stay_rare, hold_to_reference, new_tally
 from util import run_product
 
 pytestmark = pytest.mark.gpu
@@ -22,8 +23,7 @@ N_CASES = int(os.environ.get("GSR_FUZZ_CASES", "512"))
 # rows compared need one.
 # `*_reference_outside_too`: rows outside the plain bar against the float64 value in which the library is at least as close to that
 # value as the reference build is -- the reference itself misses the bar there; recorded, but not an escape of the library.
-TALLY = dict(cases=0, rows=0, cases_exit_4x_reference=0, rows_exit_4x_reference=0, cases_exit_conditioning=0, rows_exit_conditioning=0,
-             cases_reference_outside_too=0, rows_reference_outside_too=0)
+TALLY = new_tally()
 MAX_CASE_FRACTION = 0.01
 MAX_ROW_FRACTION = 1e-4
 # `reference_outside_too` has a cap of its own (looser: those are rows on which the REFERENCE misses the bar against the float64
@@ -82,100 +82,8 @@ def test_random_case_matches_reference_build(i, gpu_device):
         assert p[k][vis].tobytes() == r[k][vis].tobytes(), "case %d %s" % (i, k)
     assert p["final_T"].tobytes() == r["final_T"].tobytes()
     assert p["out_color"].tobytes() == r["out_color"].tobytes()
-    oracle_grads = None
-    TALLY["cases"] += 1
-    used_4x = used_cond = used_ref_too = False
-    for k, a in gp.items():
-        b = gr[k]
-        if a.size == 0 and b.size == 0:
-            continue
-        assert a.shape == b.shape, "case %d %s" % (i, k)
-        assert np.isfinite(a).all(), "case %d %s" % (i, k)
-        TALLY["rows"] += int(a.shape[0])
-        scale = np.abs(b).max()
-        d_ref = np.abs(a.astype(np.float64) - b.astype(np.float64)).max()
-        bad_el, bad_row, _ = util.grad_violations(a, b)
-        if bad_el == 0 and bad_row == 0:
-            continue
-        # Both sides sum thousands of fp32 terms in different (for the reference: unspecified, atomic) orders, and the
-        # per-Gaussian chain conic -> cov3D -> scale / rotation / mean can amplify that rounding noise by 10^3..10^5 on an
-        # ill-conditioned splat (a nearly singular conic).  The plain-C oracle's float32 restatement is no arbiter there: it
-        # evaluates every per-(pixel, entry) term and that chain in float32 with the reference's own expression order, so it
-        # shares the reference build's rounding (the double SUMS of those float32 terms lie 2e-7..8e-7 of max|g| from the
-        # true sums on the parity scenes, more than either implementation's summation error).  The exact value comes from
-        # float64 end to end: the oracle's float64 render backward (orc_render_backward_fp64: every term in double, the
-        # float forward's hit / stop decisions) feeding the float64 chain of tests/fp64_backward.py; the library must be
-        # inside the usual bar against it, or no further from it than 4x the reference build's own distance, row by row.
-        if oracle_grads is None:
-            from oracle.oracle import Oracle
-            from fp64_backward import gaussian_backward_fp64
-            of, og = Oracle().forward_backward(s, dL, exact=True)   # noqa: F841 (of / og are used by the conditioning check below)
-            of_grads_f32 = {n: og[n] for n in ("dL_dmean2D", "dL_dconic", "dL_dcolor")}   # double sums of the float32 terms
-            og = dict(og, **og["exact"])                              # render-level sums: the float64 ones
-            oracle_grads = dict(og)
-            oracle_grads.update(gaussian_backward_fp64(s, of["radii"], of["clamped"], og["dL_dmean2D"], og["dL_dconic"], og["dL_dcolor"]))
-        o = np.asarray(oracle_grads[k], np.float64).reshape(a.shape[0], -1)
-        a2, b2 = a.astype(np.float64).reshape(a.shape[0], -1), b.astype(np.float64).reshape(a.shape[0], -1)
-        rn = np.linalg.norm(o, axis=1)
-        r_lib, r_build = np.linalg.norm(a2 - o, axis=1), np.linalg.norm(b2 - o, axis=1)
-        plain = r_lib <= util.ROW_REL * rn + util.ROW_ABS * rn.max() + 1e-30          # the usual row bar, against the exact value
-        ok = r_lib <= np.maximum(util.ROW_REL * rn + util.ROW_ABS * rn.max(), 4 * r_build) + 1e-30
-        no_worse = ~plain & (r_lib <= r_build)          # the reference build is outside the bar too, and further out
-        if no_worse.any():
-            used_ref_too = True
-            TALLY["rows_reference_outside_too"] += int(no_worse.sum())
-        n4 = int((ok & ~plain & ~no_worse).sum())
-        if n4:
-            used_4x = True
-            TALLY["rows_exit_4x_reference"] += n4
-            w = np.nonzero(ok & ~plain & ~no_worse)[0]
-            print("fuzz exit (4x reference): case %d %s rows %s: lib-exact %s, ref-exact %s, row bar %s" % (
-                i, k, w.tolist()[:4], r_lib[w][:4], r_build[w][:4], (util.ROW_REL * rn + util.ROW_ABS * rn.max())[w][:4]))
-        if not ok.all() and k in ("dL_dmean3D", "dL_dcov3D", "dL_dscale", "dL_drot"):
-            # Still outside: is the row simply that ill-conditioned?  (a) The render-level sums every float32 implementation
-            # feeds into the chain carry rounding noise: push noise of that size through the float64 chain and see how far the
-            # exact result moves.  (b) The chain itself rounds: run the very same expressions in float32 and see how far THAT
-            # lands from the float64 result.  A row passes if the library is within 6 sigma of (a) or within 4x the distance
-            # (b) -- i.e. as good as float32 arithmetic gets on that splat.
-            bad = np.nonzero(~ok)[0]
-            rng = np.random.default_rng(4242 + i)
-            base = gaussian_backward_fp64(s, of["radii"], of["clamped"], og["dL_dmean2D"], og["dL_dconic"], og["dL_dcolor"], rows=bad)[k]
-            dev = np.zeros(bad.size)
-            f32 = {n: np.asarray(of_grads_f32[n], np.float64).reshape(np.asarray(og[n]).shape) for n in ("dL_dmean2D", "dL_dconic", "dL_dcolor")}
-            for _ in range(8):
-                # size of the noise, per element: relative 1e-6, plus an absolute floor of 2e-7 of the array's largest entry (a
-                # per-Gaussian sum over pixels of terms of both signs can cancel, its rounding noise does not shrink with it: two
-                # runs of this library differ by that much in dL_dmean2D -- float atomics commit in arrival order --
-                # scripts/diag_fuzz_state.py), plus the distance between the float32 per-(pixel, entry) terms (the reference's
-                # arithmetic, summed without error: the oracle's float32 restatement) and the float64 value of the same sum --
-                # what evaluating power / exp / the recurrences in float32 costs on THIS splat whatever the summation (a needle
-                # 100 pixels long seen from half a unit away: 7e-5 of the value, where a compact splat has 1e-7)
-                noisy = [np.asarray(og[n], np.float64) * (1.0 + 1e-6 * rng.standard_normal(np.asarray(og[n]).shape))
-                         + 2e-7 * np.abs(np.asarray(og[n], np.float64)).max() * rng.standard_normal(np.asarray(og[n]).shape)
-                         + np.abs(f32[n] - np.asarray(og[n], np.float64)) * rng.standard_normal(np.asarray(og[n]).shape)
-                         for n in ("dL_dmean2D", "dL_dconic", "dL_dcolor")]
-                out = gaussian_backward_fp64(s, of["radii"], of["clamped"], *noisy, rows=bad)[k]
-                dev += ((out - base).reshape(bad.size, -1) ** 2).sum(1)
-            sigma = np.sqrt(dev / 8)
-            f32 = gaussian_backward_fp64(s, of["radii"], of["clamped"], og["dL_dmean2D"], og["dL_dconic"], og["dL_dcolor"], rows=bad,
-                                         dtype=np.float32)[k].astype(np.float64)
-            r_f32 = np.sqrt(((f32 - base).reshape(bad.size, -1) ** 2).sum(1))
-            ok[bad] = r_lib[bad] <= np.maximum(6 * sigma, 4 * r_f32)
-            if ok[bad].any():
-                used_cond = True
-                TALLY["rows_exit_conditioning"] += int(ok[bad].sum())
-                # how large the float32-vs-float64 term of the noise model is when this exit fires (relative to the exact sums): a
-                # drift of this term -- the exit leaning on it more and more -- shows here
-                f32_term = max(float(np.abs(np.asarray(of_grads_f32[n], np.float64).reshape(np.asarray(og[n]).shape) - np.asarray(og[n], np.float64)).max()
-                                     / (np.abs(np.asarray(og[n], np.float64)).max() + 1e-300)) for n in ("dL_dmean2D", "dL_dconic", "dL_dcolor"))
-                TALLY["max_f32_term_at_conditioning_exit"] = max(TALLY.get("max_f32_term_at_conditioning_exit", 0.0), f32_term)
-                print("fuzz exit (conditioning): case %d %s rows %s: lib-exact %s, 6 sigma %s, 4 x f32 chain %s; |f32 terms - f64| up to %.2e of max|g|"
-                      % (i, k, bad[ok[bad]].tolist()[:4], r_lib[bad][ok[bad]][:4], (6 * sigma)[ok[bad]][:4], (4 * r_f32)[ok[bad]][:4], f32_term))
-        assert ok.all(), "case %d %s: %d rows; worst lib-exact %.3g (ref-exact %.3g there), lib-ref max %.3g, max|g| %.3g" % (
-            i, k, int((~ok).sum()), r_lib[~ok].max(), r_build[~ok][np.argmax(r_lib[~ok])], d_ref, scale)
-    TALLY["cases_exit_4x_reference"] += int(used_4x)
-    TALLY["cases_exit_conditioning"] += int(used_cond)
-    TALLY["cases_reference_outside_too"] += int(used_ref_too and not (used_4x or used_cond))
+    # the gradient comparison and its counted fallbacks: tests/grad_ladder.py (shared with the batched sweep)
+    hold_to_reference("case %d" % i, 4242 + i, gp, gr, Float64([s], [dL]), TALLY)
 
 
 def test_fuzz_escape_hatches_stay_rare():
@@ -183,12 +91,4 @@ def test_fuzz_escape_hatches_stay_rare():
     if TALLY["cases"] == 0:
         pytest.skip("no fuzz case ran in this process")
     print("fuzz tally:", TALLY)
-    cases = TALLY["cases_exit_4x_reference"] + TALLY["cases_exit_conditioning"]
-    rows = TALLY["rows_exit_4x_reference"] + TALLY["rows_exit_conditioning"]
-    # (at least one case is always allowed: small sweeps must not fail on a single ill-conditioned splat)
-    assert cases <= max(1, int(MAX_CASE_FRACTION * TALLY["cases"])), TALLY
-    assert rows <= max(2, int(MAX_ROW_FRACTION * TALLY["rows"])), TALLY
-    assert TALLY["cases_reference_outside_too"] <= max(2, int(MAX_CASE_FRACTION_REF_TOO * TALLY["cases"])), TALLY
-    assert TALLY["rows_reference_outside_too"] <= max(8, int(MAX_ROW_FRACTION_REF_TOO * TALLY["rows"])), TALLY
-    # the float32-evaluation term of the conditioning exit's noise model stays what it was introduced for (needles: ~7e-5)
-    assert TALLY.get("max_f32_term_at_conditioning_exit", 0.0) <= 1e-3, TALLY
+    assert_exits_stay_rare(TALLY, MAX_CASE_FRACTION, MAX_ROW_FRACTION, MAX_CASE_FRACTION_REF_TOO, MAX_ROW_FRACTION_REF_TOO)
