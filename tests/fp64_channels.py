@@ -126,7 +126,9 @@ def channels_backward_fp64(oracle, g, views, W, H, dense_extra, scale, bg_extra,
 
 def channels_backward_fp64_scenes(oracle, scenes, dense_extra, scale, bg_extra, dL_dpix, dL_dextra, nthreads=16):
     """channels_backward_fp64 with one oracle Scene per view (the colour run: cloud, camera, colours, background).
-    Returns dict(views=[dict(mean2D [P,2], conic [P,3] (x, y, w), opacity [P], colour [P,3], extra [P, nx], fwd, scene)],
+    Returns dict(views=[dict(mean2D [P,2], conic [P,3] (x, y, w), opacity [P], colour [P,3], extra [P, nx], fwd, scene,
+                             exact / f32 = the render-level sums as grad_ladder.Float64.views() names them: dL_dmean2D [P,3],
+                             dL_dconic [P,4], dL_dcolor [P,3], in float64 / as the double sums of the oracle's float32 terms)],
                  grads=dict(dL_dmean2D [P,3], dL_dcolor, dL_dopacity [P,1], dL_dmean3D, dL_dcov3D, dL_dsh?, dL_dscale?, dL_drot?))."""
     dense = np.asarray(dense_extra, F)
     V, P, nx = dense.shape
@@ -143,8 +145,11 @@ def channels_backward_fp64_scenes(oracle, scenes, dense_extra, scale, bg_extra, 
             ex = gr["exact"]
             m2, con, op = ex["dL_dmean2D"][:, :2].copy(), ex["dL_dconic"][:, [0, 1, 3]].copy(), ex["dL_dopacity"][:, 0].copy()
             col = ex["dL_dcolor"].copy()
+            # the double sums of the oracle's float32 terms of the same runs (the noise model of tests/grad_ladder.py)
+            m2_32, con_32 = gr["dL_dmean2D"].astype(np.float64), gr["dL_dconic"].astype(np.float64)
         else:
             m2, con, op, col = np.zeros((0, 2)), np.zeros((0, 3)), np.zeros(0), np.zeros((0, 3))
+            m2_32, con_32 = np.zeros((0, 3)), np.zeros((0, 4))
         gx = np.zeros((P, nx))
         for ks in _groups(nx):
             cols = np.zeros((P, 3), F)
@@ -161,16 +166,21 @@ def channels_backward_fp64_scenes(oracle, scenes, dense_extra, scale, bg_extra, 
             con += e["dL_dconic"][:, [0, 1, 3]]
             op += e["dL_dopacity"][:, 0]
             gx[:, ks] = e["dL_dcolor"][:, :len(ks)] * sc[v, ks].astype(np.float64)
+            m2_32 = m2_32 + gxr["dL_dmean2D"]
+            con_32 = con_32 + gxr["dL_dconic"]
+        conic4 = np.zeros((P, 4))
+        conic4[:, [0, 1, 3]] = con
         if P:
-            conic4 = np.zeros((P, 4))
-            conic4[:, [0, 1, 3]] = con
             chain = gaussian_backward_fp64(s, fwd["radii"], fwd["clamped"], np.concatenate([m2, np.zeros((P, 1))], 1), conic4, col)
             for k, a in chain.items():
                 add(k, a)
         add("dL_dmean2D", np.concatenate([m2, np.zeros((P, 1))], 1))
         add("dL_dcolor", col)
         add("dL_dopacity", op[:, None])
-        out.append(dict(mean2D=m2, conic=con, opacity=op, colour=col, extra=gx, fwd=fwd, scene=s))
+        out.append(dict(mean2D=m2, conic=con, opacity=op, colour=col, extra=gx, fwd=fwd, scene=s,
+                        exact=dict(dL_dmean2D=np.concatenate([m2, np.zeros((P, 1))], 1), dL_dconic=conic4, dL_dcolor=col),
+                        f32=dict(dL_dmean2D=m2_32, dL_dconic=con_32,
+                                 dL_dcolor=gr["dL_dcolor"].astype(np.float64) if P else np.zeros((0, 3)))))
     return dict(views=out, grads=tot)
 
 

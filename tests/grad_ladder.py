@@ -1,5 +1,6 @@
 """The gradient comparison of the randomised sweeps (tests/test_gpu_fuzz.py: one view; tests/test_gpu_batch_fuzz.py: sums over the
-views of a batch), with its fallbacks counted.
+views of a batch; tests/test_gpu_channel_fuzz.py: the same with the extra channels' share, ChannelsFloat64), with its fallbacks
+counted.
 
 A library gradient tensor is first held to the reference build's by util.grad_violations.  On a violation the ladder is
   1. float64, summed over the views, is the arbiter: the oracle's float64 render backward per view feeding the float64 chain of
@@ -57,6 +58,34 @@ class Float64:
                         tot[k] = tot.get(k, 0.0) + np.asarray(a, np.float64)
             self._total = tot
         return self._total
+
+
+class ChannelsFloat64(Float64):
+    """Float64 for a channels backward: the render-level sums of a view are those of its colour run plus one colors_precomp run per
+    group of three extra channels (tests/fp64_channels.channels_backward_fp64_scenes, computed when first asked for); the chain is
+    linear in them, so chain() and the noise model of hold_to_reference apply unchanged.  result(): that function's dict (per view
+    also opacity, colour and extra, the records and dL/d values of the view)."""
+
+    def __init__(self, scenes, dense_extra, scale, bg_extra, dLs, dL_dextra, nthreads=1):
+        Float64.__init__(self, scenes, dLs, nthreads)
+        self.extra = (dense_extra, scale, bg_extra, dL_dextra)
+        self._result = None
+
+    def result(self):
+        if self._result is None:
+            from fp64_channels import channels_backward_fp64_scenes
+            from oracle.oracle import Oracle
+            dense, scale, bgx, dx = self.extra
+            self._result = channels_backward_fp64_scenes(Oracle(), self.scenes, dense, scale, bgx, self.dLs, dx, nthreads=self.nthreads)
+        return self._result
+
+    def views(self):
+        if self._views is None:
+            self._views = self.result()["views"]
+        return self._views
+
+    def total(self):
+        return self.result()["grads"]
 
 
 def hold_to_reference(tag, seed, gp, gr, f64, tally, label="fuzz"):

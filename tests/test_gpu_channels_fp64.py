@@ -79,16 +79,19 @@ def _err(a, b):
     return d / m if m > 0 else (0.0 if d == 0 else np.inf)
 
 
-def _ref_decomposition(ref, scenes, dense, sc, bgx, dpix, dx):
-    """the same sums made of the reference build's float32 colour backwards: per view (mean2D [P,2], conic [P,3], dL/d extra
-    [P,nx]) and the per-Gaussian gradients summed over the views"""
+def _ref_decomposition(ref, scenes, dense, sc, bgx, dpix, dx, images=None):
+    """the same sums made of the reference build's float32 colour backwards: per view (mean2D [P,2], conic [P,3], opacity [P],
+    colour [P,3], dL/d extra [P,nx]) and the eight per-Gaussian gradients summed over the views (dL_dcolor / dL_dsh: the colour
+    run's).  images: an array [V, nx, H, W] that receives the forwards of the group runs (a group's three planes of out_color)"""
     from fp64_channels import _groups, with_colours
     V, P, nx = dense.shape
     views, tot = [], {}
+    shared = ("dL_dmean2D", "dL_dopacity", "dL_dmean3D", "dL_dscale", "dL_drot", "dL_dcov3D")
     for v, s in enumerate(scenes):
         _, g = ref.forward_backward(s, dpix[v])
         m2, con = g["dL_dmean2D"][:, :2].astype(np.float64), g["dL_dconic"][:, [0, 1, 3]].astype(np.float64)
-        for k in ("dL_dmean3D", "dL_dscale", "dL_drot", "dL_dcov3D"):
+        op = g["dL_dopacity"].reshape(-1).astype(np.float64)
+        for k in shared + ("dL_dcolor", "dL_dsh"):
             tot[k] = tot.get(k, 0.0) + g[k].astype(np.float64)
         gx = np.zeros((P, nx))
         for ks in _groups(nx):
@@ -98,13 +101,16 @@ def _ref_decomposition(ref, scenes, dense, sc, bgx, dpix, dx):
             b3[:len(ks)] = bgx[ks]
             dl = np.zeros((3, s.H, s.W), F)
             dl[:len(ks)] = dx[v, ks]
-            _, gr = ref.forward_backward(with_colours(s, cols, b3), dl)
+            fw, gr = ref.forward_backward(with_colours(s, cols, b3), dl)
+            if images is not None:
+                images[v, ks] = fw["out_color"][:len(ks)]
             m2 = m2 + gr["dL_dmean2D"][:, :2]
             con = con + gr["dL_dconic"][:, [0, 1, 3]]
-            for k in ("dL_dmean3D", "dL_dscale", "dL_drot", "dL_dcov3D"):
+            op = op + gr["dL_dopacity"].reshape(-1)
+            for k in shared:
                 tot[k] = tot[k] + gr[k].astype(np.float64)
             gx[:, ks] = gr["dL_dcolor"][:, :len(ks)].astype(np.float64) * sc[v, ks]
-        views.append(dict(mean2D=m2, conic=con, extra=gx))
+        views.append(dict(mean2D=m2, conic=con, opacity=op, colour=g["dL_dcolor"].astype(np.float64), extra=gx))
     return views, tot
 
 
