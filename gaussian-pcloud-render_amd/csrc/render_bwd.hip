@@ -31,37 +31,18 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "render_walk.hpp"
 #include "tile_cull.hpp"
 
 namespace gsr {
 
 constexpr int BGRP = 4;  // entries evaluated per inner-loop trip
-#ifndef GSR_BWD_SUBQ_DEFAULT
-#define GSR_BWD_SUBQ_DEFAULT 2
+constexpr int BWD_SUBQ_DEFAULT = 2;   // which moments the contraction takes unless told otherwise (backward_subquadrant_moments)
+// static grids of more groups of 32 workgroups than this pull their work units instead (launch_render_backward;
+// scripts/debug/bwd_fill_ab.sh builds with other values)
+#ifndef GSR_BWD_FILL
+#define GSR_BWD_FILL 4096
 #endif
-
-#ifndef GSR_BWD_DIV
-#define GSR_BWD_DIV 1   // how T / (1 - alpha) is formed (see phase 1 of the group loop)
-#endif
-#ifndef GSR_BWD_NOFMA
-#define GSR_BWD_NOFMA 0
-#endif
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// see render_fwd.hip: prefetch loads hidden from hipcc's waitcnt pass, retired by hand
-__device__ __forceinline__ void bw_prefetch16(f32x4& dst, const void* p)
-{
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(p) : "memory");
-}
-__device__ __forceinline__ void bw_prefetch4(uint32_t& dst, const void* p)
-{
-    asm volatile("global_load_dword %0, %1, off" : "=v"(dst) : "v"(p) : "memory");
-}
-__device__ __forceinline__ void bw_prefetch4f(float& dst, const void* p)
-{
-    asm volatile("global_load_dword %0, %1, off" : "=v"(dst) : "v"(p) : "memory");
-}
 
 // LDS staging of the surviving entries (see render_fwd.hip for why not v_readlane): compacted, four entries per
 // group, component-major inside the group: x0..x3 | y0..y3 | A | B | C | opacity | r | g | b | id  (10 x 16 B), so one
@@ -73,33 +54,6 @@ __device__ __forceinline__ void bw_prefetch4f(float& dst, const void* p)
 // minimum for 64 lanes.  Measured: SQ_LDS_BANK_CONFLICT 5.35e7 -> 4.67e7 per 12-view launch (-13 %), kernel time unchanged -- the
 // conflicts are not what the kernel waits for (profiles/r06_bench_rocprofv3_summary.txt).
 constexpr int QUAD_WORDS = 44;
-
-// core of ocml expf without its range clamps; bit-identical to expf on [-103, 0] (see render_fwd.hip)
-__device__ __forceinline__ float bw_exp_nonpos(float x)
-{
-    const float ph = x * 0x1.715476p+0f;
-    float pl = __builtin_fmaf(x, 0x1.715476p+0f, -ph);
-    pl = __builtin_fmaf(x, 0x1.4ae0bep-26f, pl);
-    const float e = __builtin_rintf(ph);
-    const float r = __builtin_amdgcn_exp2f((ph - e) + pl);
-    return __builtin_ldexpf(r, (int)e);
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ f32x2 bw_exp_nonpos2(f32x2 x)
-{
-    const f32x2 c = {0x1.715476p+0f, 0x1.715476p+0f}, cc = {0x1.4ae0bep-26f, 0x1.4ae0bep-26f};
-    const f32x2 ph = x * c;
-    f32x2 pl = __builtin_elementwise_fma(x, c, -ph);
-    pl = __builtin_elementwise_fma(x, cc, pl);
-    const f32x2 e = {__builtin_rintf(ph.x), __builtin_rintf(ph.y)};
-    const f32x2 a = (ph - e) + pl;
-    f32x2 r;
-    r.x = __builtin_ldexpf(__builtin_amdgcn_exp2f(a.x), (int)e.x);
-    r.y = __builtin_ldexpf(__builtin_amdgcn_exp2f(a.y), (int)e.y);
-    return r;
-}
 
 // ---- cross-lane helpers -------------------------------------------------------------------------------
 template <int CTRL, int ROW_MASK, int BANK_MASK>
@@ -234,39 +188,6 @@ __device__ __forceinline__ f32x4 mm_contract_sq(const float* mrow, const float (
     return acc;
 }
 
-#ifdef GSR_BWD_EMUL
-// DIAGNOSTIC build only (scripts/leases/gpu_session_r4b.sh): the same contraction as mm_contract by plain arithmetic, pixels in
-// raster order -- GSR_BWD_EMUL = 1: float fmaf chain, 2: double -- to tell the matrix cores' summation apart from the
-// moment shift when the accuracy of the sums is in question.  dpx: [3][64] dL_dpixel of the item, raster order.
-__device__ __forceinline__ f32x4 mm_contract_emul(const float* mrow, const float* dpx, uint32_t lane)
-{
-    const uint32_t j = lane & 15u;
-    f32x4 acc;
-    for (int r = 0; r < 4; r++) {
-        const uint32_t i = 4u * (lane >> 4) + (uint32_t)r;
-#if GSR_BWD_EMUL == 2
-        double sum = 0.0;
-#else
-        float sum = 0.f;
-#endif
-        for (uint32_t p = 0; p < 64u; p++) {
-            const float cx = (float)(p & 7u) - 3.5f, cy = (float)(p >> 3) - 3.5f;
-            const uint32_t c = i & 3u;
-            float f = c == 0 ? 1.f : c == 1 ? cx : c == 2 ? cy : (i == 3 ? cx * cx : i == 7 ? cx * cy : cy * cy);
-            if (i >= 12u) f = i < 15u ? dpx[(i - 12u) * 64u + p] : 0.f;
-            const float d = mrow[j * MM_STRIDE + mm_pos(p)];
-#if GSR_BWD_EMUL == 2
-            sum += (double)f * (double)d;
-#else
-            sum = __builtin_fmaf(f, d, sum);
-#endif
-        }
-        acc[r] = (float)sum;
-    }
-    return acc;
-}
-#endif
-
 __global__ void k_selftest_mm(float* out256)
 {
     __shared__ __attribute__((aligned(16))) float mrow[16 * MM_STRIDE];
@@ -314,8 +235,10 @@ int selftest_mm(hipStream_t stream, float* d_scratch256)
 // 4 entries with a hit, 5 (pixel, entry) hits, 6 batches flushed, 7 2x2 pixel blocks hit per batch (summed)
 __device__ unsigned long long g_bwd_stats[8];
 #define BWD_STAT(i, v) do { if (lane == 0) atomicAdd(&g_bwd_stats[i], (unsigned long long)(v)); } while (0)
+#define BWD_HITS(...) __VA_ARGS__   // (statements whose variables only BWD_STAT reads: under WALK_STAT they warn as unused in a plain -DGSR_STATS build)
 #else
 #define BWD_STAT(i, v) do { } while (0)
+#define BWD_HITS(...)
 #ifdef GSR_STATS
 __device__ unsigned long long g_bwd_stats[8];
 #endif
@@ -324,23 +247,22 @@ __device__ unsigned long long g_bwd_stats[8];
 #ifdef GSR_STATS
 // per-workgroup (= wave) time split of the LAST backward launch, 10-ns ticks: 0 whole life, 1 waiting at the rotation point
 // (next round's records AND this round's atomics: stores count in vmcnt on gfx9), 2 item set-up (per-pixel state, first
-// records), 3 footprint test + staging, 4 group evaluation + reduction + atomics issue, 5 rounds, 6 groups, 7 items
+// records), 3 footprint test + staging, 4 group evaluation + reduction + atomics issue, 5 start tick, 6 groups, 7 items
 constexpr int BW_REC = 1 << 17;
 __device__ unsigned g_bwd_rec[BW_REC][8];
-#define BW_T(var) const unsigned long long var = wall_clock64()
 // raw per-workgroup records of the last launch, eight words each (scripts/debug/bwd_tail.py)
 int debug_bwd_records(unsigned* out, int n)
 {
-    static unsigned host[BW_REC][8];
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_bwd_rec), sizeof(host)) != hipSuccess) return -1;
+    const auto host = read_wave_records(g_bwd_rec, 0);
+    if (host == nullptr) return -1;
     if (n > BW_REC) n = BW_REC;
     for (int r = 0; r < n; r++) for (int i = 0; i < 8; i++) out[r * 8 + i] = host[r][i];
     return n;
 }
 int debug_bwd_times(unsigned long long* out8, int reset)
 {
-    static unsigned host[BW_REC][8];
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_bwd_rec), sizeof(host)) != hipSuccess) return -1;
+    const auto host = read_wave_records(g_bwd_rec, reset);
+    if (host == nullptr) return -1;
     for (int i = 0; i < 8; i++) out8[i] = 0;
     unsigned long long longest = 0, waves = 0;
     for (int r = 0; r < BW_REC; r++) {
@@ -350,10 +272,6 @@ int debug_bwd_times(unsigned long long* out8, int reset)
     }
     out8[5] = longest;   // (rounds are not reported any more) the longest-lived wave
     out8[7] = (out8[7] << 20) | waves;   // items in the upper bits, waves that ran in the lower 20
-    if (reset) {
-        for (int r = 0; r < BW_REC; r++) for (int i = 0; i < 8; i++) host[r][i] = 0;
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_bwd_rec), host, sizeof(host)) != hipSuccess) return -1;
-    }
     return 0;
 }
 #endif
@@ -403,10 +321,7 @@ struct RenderBwdX {
 // the quadrant-centred moments grows with that ratio; on the benchmark views no evaluated entry exceeds 20 (the alpha >= 1/255
 // footprint ends at ~17: scripts/analysis/subq_flag_hist.py), so their batches never pay, while sub-pixel splats seen from a
 // quadrant away -- where the 4x-the-reference errors of the conic gradient come from -- do.
-#ifndef GSR_SUBQ_M
-#define GSR_SUBQ_M 20.f
-#endif
-constexpr float SUBQ_M = GSR_SUBQ_M;
+constexpr float SUBQ_M = 20.f;
 // The kernel body, shared by the colour backward (NX = 0: k_render_backward<MODE>) and the channels backward (NX = 4 / 8:
 // k_render_backward<MODE, NX>; every NX-dependent line below is compiled out of the colour kernels).  With NX extra channels
 // e_k = extra_k * view_scale_k composited by the forward with the colour's alphas, a (pixel, entry) pair's d = c . dL_dpixel gains
@@ -484,9 +399,6 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
     __shared__ __attribute__((aligned(16))) float mrow[16 * MM_STRIDE];   // 8 entries x {q, u} rows x 64 pixels
     // the staged entries' extra values: group g, channel c = the four entries' values at 4 (NX g + c)
     __shared__ __attribute__((aligned(16))) float stage_x[NX > 0 ? 16 * 4 * NX : 4];
-#ifdef GSR_BWD_EMUL
-    __shared__ float dpx_raster[3 * 64];
-#endif
     float am[16];                                                          // A operands of the 16 K steps (basis)
     float amx[NX > 0 ? 16 : 1];                                            // the same for the extras' contraction (rows xd)
     mm_basis<SUBQ>(am, threadIdx.x);
@@ -503,10 +415,8 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
     const uint32_t mm_cB = mm_g < 3u ? (mm_j < 4u ? mm_c2 : 2u + mm_g) : (mm_j >= 12u ? 5u : mm_j >= 8u ? 6u : 7u);
     const uint32_t mm_offP = mm_g == 0 ? 8u : 12u, mm_offQ = mm_g == 0 ? 12u : 16u;   // conic A|B resp. B|C
     const float mm_dd = -(mm_g == 0 ? (float)(0.5 * a.W) : (float)(0.5 * a.H));
-#ifdef GSR_STATS
-    BW_T(tw0);
-    unsigned long long tw_wait = 0, tw_setup = 0, tw_stage = 0, tw_eval = 0, n_rounds = 0, n_groups = 0, n_items_done = 0;
-#endif
+    WALK_T(tw0);
+    WALK_STAT(unsigned long long tw_wait = 0, tw_setup = 0, tw_stage = 0, tw_eval = 0, n_groups = 0, n_items_done = 0;)
   // Which items a workgroup takes.  STATIC (a.dynamic == 0; the launch has a quartet of workgroups per eight items or more): quartet
   // (b, b + 8, b + 16, b + 24) takes item (group / V) * 8 + b % 8 and every (groups per view * 8)-th after it, one quadrant each -- with
   // at least as many quartets as items that is one item per quartet in dispatch order, heaviest first.  DYNAMIC (batches, whose grid
@@ -528,33 +438,23 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
         item_idx += static_stride;
     }
     if (item_idx >= n_items) break;
-#ifdef GSR_STATS
-    BW_T(ti0);
-    n_items_done++;
-#endif
+    WALK_T(ti0);
+    WALK_STAT(n_items_done++;)
     const uint32_t item = a.items[item_idx];
     const uint32_t tile = item & ((1u << BWD_TILE_BITS) - 1u), chunk = item >> BWD_TILE_BITS;
     const uint32_t lane = threadIdx.x;
-    const uint32_t tx = tile % (uint32_t)a.gridx, ty = tile / (uint32_t)a.gridx;
-    const uint32_t x0 = tx * TILE_X + (q & 1u) * 8u, y0 = ty * TILE_Y + (q >> 1) * 8u;
-    const uint32_t px = x0 + (lane & 7u), py = y0 + (lane >> 3);
-    const bool inside = px < (uint32_t)a.W && py < (uint32_t)a.H;
-    const float pixf_x = (float)px, pixf_y = (float)py;
-    const float x0f = (float)x0, y0f = (float)y0;
+    QuadGeom g;
+    quad_geom(g, tile, q, a.gridx, a.W, a.H, lane);
+    const uint32_t px = g.px, py = g.py;
+    const bool inside = g.inside;
+    const float pixf_x = g.pixf_x, pixf_y = g.pixf_y, x0f = g.x0f, y0f = g.y0f;
     const size_t pix = (size_t)py * a.W + px, N = (size_t)a.W * a.H;
 
     const uint32_t last_contributor = inside ? a.n_contrib[pix] : 0u;
     // entries [0, total) are walked, last first: nothing beyond the quadrant's largest n_contrib was consumed here
-    int total;
-    {
-        uint32_t m = last_contributor;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const uint32_t o = __shfl_xor(m, d, 64);
-            m = m > o ? m : o;
-        }
-        total = (int)__builtin_amdgcn_readfirstlane(m);   // every lane holds the maximum: tell the compiler it is uniform
-    }
+    uint32_t reach = last_contributor;
+    wave_max_of(reach);
+    const int total = (int)__builtin_amdgcn_readfirstlane(reach);   // every lane holds the maximum: tell the compiler it is uniform
     // this item's slice of the list: entries [lo, hi0), walked last first
     const int lo = (int)(chunk << a.chunk_shift);
     if (lo >= total) continue;
@@ -618,9 +518,6 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
         }
     }
     mm_basis_dpx(am, mrow, lane);
-#ifdef GSR_BWD_EMUL
-    dpx_raster[lane] = dpx0; dpx_raster[64 + lane] = dpx1; dpx_raster[128 + lane] = dpx2;
-#endif
     const float mm_sx = x0f + 3.5f, mm_sy = y0f + 3.5f;   // quadrant centre
 
     // Where this lane's reduced value goes.  Even lane 2i owns value i of the 32-batch: entry k = i >> 3 of the group,
@@ -663,42 +560,37 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
     uint32_t id_cur, id_nxt, id_nn;
     {
         const int f0 = hi0 - 1 - (int)lane, f1 = hi0 - 65 - (int)lane;
-        bw_prefetch4(id_cur, plist + (f0 >= lo ? f0 : lo));
-        bw_prefetch4(id_nxt, plist + (f1 >= lo ? f1 : lo));
+        prefetch4(id_cur, plist + (f0 >= lo ? f0 : lo));
+        prefetch4(id_nxt, plist + (f1 >= lo ? f1 : lo));
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(id_cur), "+v"(id_nxt)::"memory");
         const Splat* sp = a.splat + id_cur;
-        bw_prefetch16(c0, &sp->q0);
-        bw_prefetch16(c1, &sp->q1);
-        bw_prefetch4f(c2b, &sp->q2);
+        prefetch16(c0, &sp->q0);
+        prefetch16(c1, &sp->q1);
+        prefetch4f(c2b, &sp->q2);
         if constexpr (NX > 0) {
-            bw_prefetch16(cx0, x_lo + (size_t)id_cur * x_nx);
-            if (NX > 4) bw_prefetch16(cx1, x_hi + (size_t)id_cur * x_nx);
+            prefetch16(cx0, x_lo + (size_t)id_cur * x_nx);
+            if (NX > 4) prefetch16(cx1, x_hi + (size_t)id_cur * x_nx);
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(c0), "+v"(c1), "+v"(c2b), "+v"(cx0), "+v"(cx1)::"memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(c0), "+v"(c1), "+v"(c2b)::"memory");
         }
     }
-#ifdef GSR_STATS
-    { BW_T(ti1); tw_setup += ti1 - ti0; }
-#endif
+    WALK_STAT({ WALK_T(ti1); tw_setup += ti1 - ti0; })
     unsigned long long hit_px = 0;   // pixels hit by some entry of the open batch
     uint32_t nb = 0, gq0 = 0;   // groups in the open batch (it may span rounds), the staging group of its first one
     for (int hi = hi0; hi > lo; hi -= 64) {
-#ifdef GSR_STATS
-        BW_T(tr0);
-        n_rounds++;
-#endif
+        WALK_T(tr0);
         {
             const Splat* sp = a.splat + id_nxt;
-            bw_prefetch16(n0, &sp->q0);
-            bw_prefetch16(n1, &sp->q1);
-            bw_prefetch4f(n2b, &sp->q2);
+            prefetch16(n0, &sp->q0);
+            prefetch16(n1, &sp->q1);
+            prefetch4f(n2b, &sp->q2);
             if constexpr (NX > 0) {
-                bw_prefetch16(nx0, x_lo + (size_t)id_nxt * x_nx);
-                if (NX > 4) bw_prefetch16(nx1, x_hi + (size_t)id_nxt * x_nx);
+                prefetch16(nx0, x_lo + (size_t)id_nxt * x_nx);
+                if (NX > 4) prefetch16(nx1, x_hi + (size_t)id_nxt * x_nx);
             }
             const int f2 = hi - 129 - (int)lane;
-            bw_prefetch4(id_nn, plist + (f2 >= lo ? f2 : lo));
+            prefetch4(id_nn, plist + (f2 >= lo ? f2 : lo));
         }
         const int f_lane = hi - 1 - (int)lane;
         // only pixels whose last contributor lies beyond this round's first entry can be hit by the round: test
@@ -742,18 +634,14 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
         BWD_STAT(0, 1);
         BWD_STAT(1, __popcll(mask));
         int quad = 0;
-#ifdef GSR_STATS
-        BW_T(tr1);
-        tw_stage += tr1 - tr0;
-#endif
+        WALK_T(tr1);
+        WALK_STAT(tw_stage += tr1 - tr0;)
         const bool last_round = hi - 64 <= lo;
         for (;;) {
           const bool more = mask != 0;
           if (more) {
             BWD_STAT(2, 1);
-#ifdef GSR_STATS
-            n_groups++;
-#endif
+            WALK_STAT(n_groups++;)
             float ex[BGRP], ey[BGRP], eA[BGRP], eB[BGRP], eC[BGRP], eo[BGRP], er[BGRP], eg[BGRP], eb[BGRP];
             uint32_t ef[BGRP];
             {
@@ -799,7 +687,7 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
                 const f32x2 B2 = {eB[k], eB[k + 1]}, C2 = {eC[k], eC[k + 1]}, O2 = {eo[k], eo[k + 1]};
                 const f32x2 dx = X - pixf_x, dy = Y - pixf_y;
                 const f32x2 power = -0.5f * (A2 * dx * dx + C2 * dy * dy) - B2 * dx * dy;
-                const f32x2 G = bw_exp_nonpos2(power);
+                const f32x2 G = exp_nonpos2(power);
                 const f32x2 al = O2 * G;
                 Gs[k] = G.x; Gs[k + 1] = G.y;
                 alphas[k] = fminf(0.99f, al.x);
@@ -809,14 +697,12 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
                 any_lane_hit = any_lane_hit || hits[k] || hits[k + 1];
             }
             if (__builtin_amdgcn_ballot_w64(any_lane_hit) != 0) {
-#if defined(GSR_STATS) && defined(GSR_STATS_HITS)
             BWD_STAT(3, 1);
-            for (int k = 0; k < BGRP; k++) {
+            BWD_HITS(for (int k = 0; k < BGRP; k++) {
                 const uint64_t hm = __ballot(hits[k]);
                 BWD_STAT(4, hm != 0 ? 1 : 0);
                 BWD_STAT(5, __popcll(hm));
-            }
-#endif
+            })
 
             // Phase 1 (branch-free): advance the per-pixel recurrences through the four entries.
             // The reference tracks accum_rec[ch], the colour accumulated behind the current entry, only to form
@@ -834,38 +720,19 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
                 const bool hit = hits[k];
                 const float alpha = hit ? alphas[k] : 0.f;
                 const float om = 1.f - alpha;
-#if GSR_BWD_DIV == 0
-                const float rcp = __builtin_amdgcn_rcpf(om);
-                const float Tn = T * rcp;
-#elif GSR_BWD_DIV == 1
                 // T / (1 - alpha) as the reference writes it (CR/backward.cu:503), without the ten instructions of the generic
                 // division: v_rcp_f32 (1 ulp) gives the quotient to ~1.5 ulp, one residual step T - om * q (exact in the FMA)
                 // brings it to the correctly rounded value except when the exact quotient lies within ~2^-22 ulp of a rounding
                 // boundary.  No scaling is needed: om is in [0.01, 1] and T in [1e-4 * 0.01, 1].
+                // (The forms that lost -- v_rcp_f32 alone, a refined reciprocal, the generic division: profiles/r04_bwd_accuracy.txt, profiles/r05_bwd_accuracy.txt.)
                 const float rcp = __builtin_amdgcn_rcpf(om);
                 const float q0 = T * rcp;
                 const float Tn = __builtin_fmaf(__builtin_fmaf(-om, q0, T), rcp, q0);
-#elif GSR_BWD_DIV == 2
-                const float r0 = __builtin_amdgcn_rcpf(om);
-                const float rcp = __builtin_fmaf(__builtin_fmaf(-om, r0, 1.f), r0, r0);
-                const float q0 = T * rcp;
-                const float Tn = __builtin_fmaf(__builtin_fmaf(-om, q0, T), rcp, q0);
-#else
-                const float rcp = 1.f / om;
-                const float Tn = T / om;
-#endif
-#if GSR_BWD_NOFMA
-                const float d = (er[k] * dpx0 + eg[k] * dpx1) + eb[k] * dpx2;
-                const float sn = last_alpha * last_d + (1.f - last_alpha) * s_rec;
-                float dL_dalpha = (d - sn) * Tn;
-                dL_dalpha = dL_dalpha + (-T_final * rcp) * bg_dot_dpixel;
-#else
                 float d = __builtin_fmaf(eb[k], dpx2, __builtin_fmaf(eg[k], dpx1, er[k] * dpx0));
                 if constexpr (NX > 0) d += xdot[k];
                 const float sn = __builtin_fmaf(last_alpha, last_d - s_rec, s_rec);  // la*last_d + (1-la)*s
                 float dL_dalpha = (d - sn) * Tn;
                 dL_dalpha = __builtin_fmaf(neg_tfb, rcp, dL_dalpha);   // (-T_final / (1 - alpha)) * bg . dL_dpixel
-#endif
                 // lanes that do not hit contribute exact zeros: every product of phase 2 carries a factor Gh or alpha*T
                 // (dL_dalpha itself stays finite, so 0 * dL_dalpha is 0)
                 dLa[k] = dL_dalpha;
@@ -953,20 +820,8 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
                 if (mm_u) { o1 = S1; o2 = Ay; }                                              // colour r, g (row 3, u columns: sums of rows 12, 13)
                 o3 = Az;                                                                     // colour b
             } else {
-#ifdef GSR_BWD_EMUL
-            const f32x4 acc = mm_contract_emul(mrow, dpx_raster, lane);
-#else
             const f32x4 acc = mm_contract(mrow, am, lane, hit_blocks);
-#endif
             const float S1 = acc.x, Sx = acc.y, Sy = acc.z, V3 = acc.w;
-#ifdef GSR_BWD_SHIFT64
-            // DIAGNOSTIC: the moment shift in double
-            const double bxd = (double)eX - (double)mm_sx, byd = (double)eY - (double)mm_sy;
-            const double Dxd = bxd * S1 - Sx, Dyd = byd * S1 - Sy;
-            const double t2d = (mm_g == 0 ? bxd : byd) * (mm_g == 2u ? Dyd : Dxd) - (mm_g == 2u ? byd : bxd) * (mm_g == 0 ? Sx : Sy) + V3;
-            o1 = (float)(-0.5 * cO * t2d);
-            o2 = (float)(((double)cO * mm_dd) * ((double)cP * Dxd + (double)cQ * Dyd));
-#else
             const float bx = eX - mm_sx, by = eY - mm_sy;             // splat centre - quadrant centre
             const float Dx = __builtin_fmaf(bx, S1, -Sx), Dy = __builtin_fmaf(by, S1, -Sy);   // sum q dx, sum q dy
             // second moments about the splat centre: sum q dx^2 = bx Dx - bx Sx + Sxx, sum q dx dy = by Dx - bx Sy + Sxy,
@@ -975,7 +830,6 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
                                             __builtin_fmaf(-(mm_g == 2u ? by : bx), mm_g == 0 ? Sx : Sy, V3));
             o1 = -0.5f * cO * t2;                                                  // conic x | y | w
             o2 = (cO * mm_dd) * __builtin_fmaf(cP, Dx, cQ * Dy);                   // mean2D x | y
-#endif
             if (mm_g == 2u) o2 = S1;                                                     // opacity
             if (mm_u) { o1 = acc.x; o2 = acc.y; }                                        // colour r, g (row 3, u columns)
             o3 = acc.z;                                                                  // colour b
@@ -1023,29 +877,23 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
             if (lane < (uint32_t)QUAD_WORDS) stage[16 * QUAD_WORDS + lane] = stage[gq0 * QUAD_WORDS + lane];
             gq0 = 16u;
         }
-#ifdef GSR_STATS
-        BW_T(tr2);
-        tw_eval += tr2 - tr1;
-#endif
+        WALK_T(tr2);
+        WALK_STAT(tw_eval += tr2 - tr1;)
         if constexpr (NX > 0) asm volatile("s_waitcnt vmcnt(0)" : "+v"(n0), "+v"(n1), "+v"(n2b), "+v"(id_nn), "+v"(nx0), "+v"(nx1)::"memory");
         else asm volatile("s_waitcnt vmcnt(0)" : "+v"(n0), "+v"(n1), "+v"(n2b), "+v"(id_nn)::"memory");
-#ifdef GSR_STATS
-        { BW_T(tr3); tw_wait += tr3 - tr2; }
-#endif
+        WALK_STAT({ WALK_T(tr3); tw_wait += tr3 - tr2; })
         c0 = n0; c1 = n1; c2b = n2b;
         if constexpr (NX > 0) { cx0 = nx0; cx1 = nx1; }
         id_cur = id_nxt;
         id_nxt = id_nn;
     }
   }
-#ifdef GSR_STATS
-    if (threadIdx.x == 0 && blockIdx.x < (unsigned)BW_REC) {
-        BW_T(tw1);
+    WALK_STAT(if (threadIdx.x == 0 && blockIdx.x < (unsigned)BW_REC) {
+        WALK_T(tw1);
         unsigned* r_ = g_bwd_rec[blockIdx.x];
         r_[0] = (unsigned)(tw1 - tw0); r_[1] = (unsigned)tw_wait; r_[2] = (unsigned)tw_setup; r_[3] = (unsigned)tw_stage;
         r_[4] = (unsigned)tw_eval; r_[5] = (unsigned)tw0; r_[6] = (unsigned)n_groups; r_[7] = (unsigned)n_items_done;   // (5: start tick)
-    }
-#endif
+    })
 }
 
 
@@ -1061,9 +909,10 @@ int debug_bwd_stats(unsigned long long* out8, int reset)
 }
 #endif
 
-// Which moments the contraction takes: 0 (default) about the quadrant centre, 1 about the four sub-quadrant centres (mean2D / conic
-// sums at the reference build's accuracy, for more flush arithmetic).  GSR_BWD_SUBQ in the environment when the library is first
-// used, or gsr_set_backward_moments() (tests, scripts/bwd_accuracy.py).
+// Which moments the contraction takes: 0 about the quadrant centre, 1 about the four sub-quadrant centres (mean2D / conic sums at
+// the reference build's accuracy, for more flush arithmetic), 2 (default) the sub-quadrant ones only for the batches that hold a
+// flagged splat (MODE above).  GSR_BWD_SUBQ in the environment when the library is first used, or gsr_set_backward_moments()
+// (tests, scripts/bwd_accuracy.py).
 static std::atomic<int> g_bwd_subq{-1};
 int backward_subquadrant_moments(int set)
 {
@@ -1071,11 +920,25 @@ int backward_subquadrant_moments(int set)
     int v = g_bwd_subq.load();
     if (v < 0) {
         const char* e = getenv("GSR_BWD_SUBQ");
-        v = e ? atoi(e) : GSR_BWD_SUBQ_DEFAULT;
-        v = v < 0 || v > 2 ? GSR_BWD_SUBQ_DEFAULT : v;
+        v = e ? atoi(e) : BWD_SUBQ_DEFAULT;
+        v = v < 0 || v > 2 ? BWD_SUBQ_DEFAULT : v;
         g_bwd_subq.store(v);
     }
     return v;
+}
+
+// the runtime moments mode (backward_subquadrant_moments) as the kernel's compile-time MODE
+template <int NX, typename... XS>
+static void launch_bwd_kernel(dim3 grid, hipStream_t stream, const RenderBwdArgs& a, const XS&... xs)
+{
+    const auto launch = [&](auto mode) {
+        hipLaunchKernelGGL((k_render_backward<decltype(mode)::value, NX, XS...>), grid, dim3(64), 0, stream, a, xs...);
+    };
+    switch (backward_subquadrant_moments(-1)) {
+    case 1: launch(std::integral_constant<int, 1>{}); break;
+    case 2: launch(std::integral_constant<int, 2>{}); break;
+    default: launch(std::integral_constant<int, 0>{}); break;
+    }
 }
 
 int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, const float* dL_dpix,
@@ -1089,27 +952,18 @@ int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B,
     a.accum = B.iv.accum;
     a.point_list = point_list;
     a.splat = B.g.splat;
-    a.W = p.W; a.H = p.H;
-    a.gridx = (p.W + TILE_X - 1) / TILE_X;
-    const int gridy = (p.H + TILE_Y - 1) / TILE_Y;
+    set_frame_args(a, p, B);
     a.bg = p.bg;
     a.final_T = B.iv.final_T;
     a.n_contrib = B.iv.n_contrib;
     a.dL_dpix = dL_dpix;
     a.grad_rec = B.grad_rec; a.gr_stride = B.gr_stride;
     a.counters = B.g.counters;
-    a.num_tiles = a.gridx * gridy;
-    a.chunk_shift = B.chunk_shift();
-    a.V = (uint32_t)B.V;
-    a.g_stride = B.g_stride; a.b_stride = B.b_stride; a.iv_stride = B.iv_stride;
     // the number of items is only known on the device.  A quartet of workgroups per eight tiles covers the items of a single view one
     // to one (rarely more items than tiles); a batch would need V times that, so its workgroups -- about two per wave slot of the chip
     // (five waves per SIMD, four SIMDs per CU), dealt to the views in groups of 32 -- pull work units until their view's queues are empty
     static const int cus = [] { int dev = 0, n = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
     int64_t groups = div_up(a.num_tiles, 8);
-#ifndef GSR_BWD_FILL
-#define GSR_BWD_FILL 4096
-#endif
     // (batches only: a single view's 1 280 waves per XCD pulling from ONE counter wait for it -- 0.39 instead of 0.25 ms -- however
     // many tiles the image has)
     a.dynamic = (B.V > 1 && groups * B.V > GSR_BWD_FILL) ? 1u : 0u;
@@ -1122,30 +976,15 @@ int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B,
         x.extra_scale = X->view_scale; x.bg_extra = X->bg;
         x.xckpt = X->state.ckpt; x.xaccum = X->state.accum; x.x_stride = X->state_stride;
         x.dL_dextra = XG->dL_dextra; x.grad = XG->grad; x.grad_hi = XG->grad_hi;
-        const int mode = backward_subquadrant_moments(-1);
-#define GSR_LAUNCH_BWD_X(M_, NX_) hipLaunchKernelGGL((k_render_backward<M_, NX_, RenderBwdX>), grid, dim3(64), 0, L.stream, a, x)
-        if (X->nx == 4) {
-            if (mode == 1) GSR_LAUNCH_BWD_X(1, 4); else if (mode == 2) GSR_LAUNCH_BWD_X(2, 4); else GSR_LAUNCH_BWD_X(0, 4);
-        } else {
-            if (mode == 1) GSR_LAUNCH_BWD_X(1, 8); else if (mode == 2) GSR_LAUNCH_BWD_X(2, 8); else GSR_LAUNCH_BWD_X(0, 8);
-        }
-#undef GSR_LAUNCH_BWD_X
+        if (X->nx == 4) launch_bwd_kernel<4>(grid, L.stream, a, x);
+        else launch_bwd_kernel<8>(grid, L.stream, a, x);
         return check_launch(L, "render_backward_channels");
     }
     if (D != nullptr) {
-        const RenderBwdDet d = *D;
-        switch (backward_subquadrant_moments(-1)) {
-        case 1: hipLaunchKernelGGL((k_render_backward<1, 0, RenderBwdDet>), grid, dim3(64), 0, L.stream, a, d); break;
-        case 2: hipLaunchKernelGGL((k_render_backward<2, 0, RenderBwdDet>), grid, dim3(64), 0, L.stream, a, d); break;
-        default: hipLaunchKernelGGL((k_render_backward<0, 0, RenderBwdDet>), grid, dim3(64), 0, L.stream, a, d); break;
-        }
+        launch_bwd_kernel<0>(grid, L.stream, a, *D);
         return check_launch(L, "render_backward_det");
     }
-    switch (backward_subquadrant_moments(-1)) {
-    case 1: hipLaunchKernelGGL((k_render_backward<1, 0>), grid, dim3(64), 0, L.stream, a); break;
-    case 2: hipLaunchKernelGGL((k_render_backward<2, 0>), grid, dim3(64), 0, L.stream, a); break;
-    default: hipLaunchKernelGGL((k_render_backward<0, 0>), grid, dim3(64), 0, L.stream, a); break;
-    }
+    launch_bwd_kernel<0>(grid, L.stream, a);
     return check_launch(L, "render_backward");
 }
 

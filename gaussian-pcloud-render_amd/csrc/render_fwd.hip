@@ -30,6 +30,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "render_walk.hpp"
 #include "tile_cull.hpp"
 
 namespace gsr {
@@ -65,67 +66,6 @@ struct RenderArgs {
     float* xaccum;
     size_t x_stride;
 };
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// Prefetch loads are issued as inline asm so that hipcc's waitcnt pass does not see them: left to itself it puts
-// an s_waitcnt for the NEXT round's records inside the CURRENT round's evaluation loop and re-exposes the gather
-// latency every 64 entries.  The loads are retired by hand with one s_waitcnt vmcnt(0) at the rotation point; that
-// asm takes the destination registers as in/out operands, so nothing can read them earlier.
-__device__ __forceinline__ void prefetch16(f32x4& dst, const void* p)
-{
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(p) : "memory");
-}
-__device__ __forceinline__ void prefetch4(uint32_t& dst, const void* p)
-{
-    asm volatile("global_load_dword %0, %1, off" : "=v"(dst) : "v"(p) : "memory");
-}
-__device__ __forceinline__ void prefetch4f(float& dst, const void* p)
-{
-    asm volatile("global_load_dword %0, %1, off" : "=v"(dst) : "v"(p) : "memory");
-}
-__device__ __forceinline__ void retire_prefetch(f32x4& a, f32x4& b, float& c, uint32_t& d)
-{
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)::"memory");
-}
-
-__device__ __forceinline__ void retire_prefetch_x(f32x4& a, f32x4& b, float& c, uint32_t& d, f32x4& e, f32x4& f)
-{
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f)::"memory");
-}
-
-// exp(x) for the compositing loop.  Instruction-for-instruction the core of the ocml expf that `exp(power)` of the
-// reference resolves to under hipcc (extended-precision x*log2(e), v_rndne, v_exp_f32, v_ldexp_f32), minus its two
-// range clamps: x > 88.7 -> inf and x < -103.3 -> 0.  Neither can change a decision or a blended value: entries
-// with power > 0 are skipped before alpha is used, and for x < -103 both forms give a value < 1e-44, far below
-// the 1/255 cut for any finite opacity.  For every x in [-103, 0] the result is bit-identical to expf(x).
-__device__ __forceinline__ float exp_nonpos(float x)
-{
-    const float ph = x * 0x1.715476p+0f;
-    float pl = __builtin_fmaf(x, 0x1.715476p+0f, -ph);
-    pl = __builtin_fmaf(x, 0x1.4ae0bep-26f, pl);
-    const float e = __builtin_rintf(ph);
-    const float r = __builtin_amdgcn_exp2f((ph - e) + pl);
-    return __builtin_ldexpf(r, (int)e);
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// two-entry version: the multiplies / fused multiply-adds / adds become packed fp32 instructions (v_pk_*_f32, two
-// IEEE operations per lane per issue slot); rounding per component is that of exp_nonpos
-__device__ __forceinline__ f32x2 exp_nonpos2(f32x2 x)
-{
-    const f32x2 c = {0x1.715476p+0f, 0x1.715476p+0f}, cc = {0x1.4ae0bep-26f, 0x1.4ae0bep-26f};
-    const f32x2 ph = x * c;
-    f32x2 pl = __builtin_elementwise_fma(x, c, -ph);
-    pl = __builtin_elementwise_fma(x, cc, pl);
-    const f32x2 e = {__builtin_rintf(ph.x), __builtin_rintf(ph.y)};
-    const f32x2 a = (ph - e) + pl;
-    f32x2 r;
-    r.x = __builtin_ldexpf(__builtin_amdgcn_exp2f(a.x), (int)e.x);
-    r.y = __builtin_ldexpf(__builtin_amdgcn_exp2f(a.y), (int)e.y);
-    return r;
-}
 
 // Broadcast of the surviving entries to the 64 pixels goes through LDS: the lanes whose entry survived the footprint
 // test write their records, compacted and interleaved in PAIRS (x0 x1 y0 y1 | A0 A1 B0 B1 | C0 C1 o0 o1 |
@@ -192,16 +132,15 @@ __device__ __forceinline__ bool stage_entry(float* stage, int pw, uint32_t slot,
 // instrumentation build only: where the forward waves' time goes, summed over the waves of the launches since the last reset
 // (10-ns ticks): 0 whole life, 1 waiting for the next round's records at the rotation point, 2 footprint test + staging,
 // 3 pair evaluation, 4 waves, 5 rounds, 6 pairs evaluated
-// (one record per wave of the LAST launch -- same-address atomics from 390 K waves would be what gets measured)
 constexpr int FW_REC = 1 << 19;
 __device__ unsigned g_fwd_rec[FW_REC][8];
 __device__ unsigned g_fwd_hw[FW_REC][2];   // where and when each wave ran: HW_ID | XCC_ID << 28, start tick (low 32 bits)
 // raw per-wave records of the last launch, ten words per wave (scripts/debug/fwd_placement.py)
 int debug_fwd_records(unsigned* out, int n)
 {
-    static unsigned host[FW_REC][8], hw[FW_REC][2];
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_fwd_rec), sizeof(host)) != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(hw, HIP_SYMBOL(g_fwd_hw), sizeof(hw)) != hipSuccess) return -1;
+    const auto host = read_wave_records(g_fwd_rec, 0);
+    const auto hw = read_wave_records(g_fwd_hw, 0);
+    if (host == nullptr || hw == nullptr) return -1;
     if (n > FW_REC) n = FW_REC;
     for (int r = 0; r < n; r++) {
         for (int i = 0; i < 8; i++) out[r * 10 + i] = host[r][i];
@@ -209,32 +148,35 @@ int debug_fwd_records(unsigned* out, int n)
     }
     return n;
 }
-#define FW_T(var) const unsigned long long var = wall_clock64()
 int debug_fwd_times(unsigned long long* out8, int reset)
 {
-    static unsigned host[FW_REC][8];
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_fwd_rec), sizeof(host)) != hipSuccess) return -1;
+    const auto host = read_wave_records(g_fwd_rec, reset);
+    if (host == nullptr) return -1;
     for (int i = 0; i < 8; i++) out8[i] = 0;
     for (int r = 0; r < FW_REC; r++) {
         for (int i = 0; i < 7; i++) out8[i] += host[r][i];
         if (host[r][0] > out8[7]) out8[7] = host[r][0];   // the longest-lived wave
     }
-    if (reset) {
-        for (int r = 0; r < FW_REC; r++) for (int i = 0; i < 8; i++) host[r][i] = 0;
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_fwd_rec), host, sizeof(host)) != hipSuccess) return -1;
-    }
     return 0;
 }
 #endif
+// a forward wave's record (word 7: what the kernel adds of its own) and where and when it ran
+#define FW_PUT_RECORD(word7)                                                                                                        \
+    WALK_STAT(if (lane == 0 && blockIdx.x < (unsigned)FW_REC) {                                                                     \
+        WALK_T(tw1);                                                                                                                \
+        unsigned* r_ = g_fwd_rec[blockIdx.x];                                                                                       \
+        r_[0] = (unsigned)(tw1 - tw0); r_[1] = (unsigned)tw_wait; r_[2] = (unsigned)tw_stage; r_[3] = (unsigned)tw_eval;            \
+        r_[4] = 1u; r_[5] = (unsigned)n_rounds; r_[6] = (unsigned)n_pairs; r_[7] = (word7);                                         \
+        g_fwd_hw[blockIdx.x][0] = __builtin_amdgcn_s_getreg(63492) | (__builtin_amdgcn_s_getreg(63508) << 28); /* HW_ID, XCC_ID */  \
+        g_fwd_hw[blockIdx.x][1] = (unsigned)tw0;                                                                                    \
+    })
 
 template <int NX>
 __global__ __launch_bounds__(64) void k_render_forward(RenderArgs a)
 {
-#ifdef GSR_STATS
-    FW_T(tw0);
-    unsigned long long tw_wait = 0, tw_stage = 0, tw_eval = 0, n_rounds = 0, n_pairs = 0;
-    unsigned live_cnt = 64, n_pairs_le8 = 0, n_pairs_le16 = 0, n_pairs_le32 = 0;   // pairs evaluated while <= 8 / 16 / 32 pixels were live
-#endif
+    WALK_T(tw0);
+    WALK_STAT(unsigned long long tw_wait = 0, tw_stage = 0, tw_eval = 0, n_rounds = 0, n_pairs = 0;)
+    WALK_STAT(unsigned live_cnt = 64, n_pairs_le8 = 0, n_pairs_le16 = 0, n_pairs_le32 = 0;)   // pairs evaluated while <= 8 / 16 / 32 pixels were live
     static_assert(NX == 0 || NX == 4 || NX == 8, "extra channels come in quads");
     constexpr int PW = PAIR_WORDS + 2 * NX;   // words per staged pair
     // XCD-aware work mapping: workgroup b runs on XCD b % 8 (each XCD has its own L2), so the four quadrant waves of
@@ -297,9 +239,7 @@ __global__ __launch_bounds__(64) void k_render_forward(RenderArgs a)
     bool crossed = false;  // this quadrant walked past a BWD_CHUNK boundary (wave-uniform)
     bool done = !inside;
     bool all_done = __all(done);
-#ifdef GSR_STATS
-    live_cnt = (unsigned)__popcll(__ballot(!done));
-#endif
+    WALK_STAT(live_cnt = (unsigned)__popcll(__ballot(!done));)
     if (!all_done) {
         int ax, ay, bx, by;
         live_box(__ballot(!done), ax, ay, bx, by);
@@ -359,10 +299,8 @@ __global__ __launch_bounds__(64) void k_render_forward(RenderArgs a)
                 crossed = true;
             }
 
-#ifdef GSR_STATS
-            FW_T(ts0);
-            n_rounds++;
-#endif
+            WALK_T(ts0);
+            WALK_STAT(n_rounds++;)
             // which of this round's 64 entries can reach alpha >= 1/255 somewhere in this quadrant?
             const bool valid = base + (int)lane < total;
             const bool touch = valid && may_touch_rect(c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, bx0, by0, bx1, by1);
@@ -393,9 +331,7 @@ __global__ __launch_bounds__(64) void k_render_forward(RenderArgs a)
                 // Pair p+1 is read from LDS while pair p is evaluated.  The loop body is written out twice with the two
                 // register sets swapped, so no register moves are needed to rotate them.
                 auto eval_pair = [&](const PairRec<NX>& r) {
-#ifdef GSR_STATS
-                    n_pairs_le8 += live_cnt <= 8; n_pairs_le16 += live_cnt <= 16; n_pairs_le32 += live_cnt <= 32;
-#endif
+                    WALK_STAT(n_pairs_le8 += live_cnt <= 8; n_pairs_le16 += live_cnt <= 16; n_pairs_le32 += live_cnt <= 32;)
                     // this pair has landed (DS returns in order); the 5 + NX / 2 reads of the next pair stay in flight
                     __builtin_amdgcn_s_waitcnt(NX == 0 ? 0xC57F : NX == 4 ? 0xC77F : 0xC97F);   // lgkmcnt(5 / 7 / 9)
                     // alpha of each entry; ae = alpha where the entry counts for this pixel, else 0.  The two entries
@@ -457,9 +393,7 @@ __global__ __launch_bounds__(64) void k_render_forward(RenderArgs a)
                         done = done || s0 || s1;
                         const uint64_t live = __ballot(!done);
                         all_done = live == 0;
-#ifdef GSR_STATS
-                        live_cnt = (unsigned)__popcll(live);
-#endif
+                        WALK_STAT(live_cnt = (unsigned)__popcll(live);)
                         if (!all_done) {   // a pixel stopped: the rounds still to come only need entries that reach the rest
                             int ax, ay, bx, by;
                             live_box(live, ax, ay, bx, by);
@@ -471,10 +405,8 @@ __global__ __launch_bounds__(64) void k_render_forward(RenderArgs a)
                 // and the loop ends on the pair count alone: when every pixel is done the count is set to 0.
                 int npairs = (int)((nsurv + 1u) >> 1);
                 int pair = 0;
-#ifdef GSR_STATS
-                FW_T(ts1);
-                tw_stage += ts1 - ts0;
-#endif
+                WALK_T(ts1);
+                WALK_STAT(tw_stage += ts1 - ts0;)
                 PairRec<NX> ra = read_pair<NX>(stage, 0), rb;
                 for (;;) {
                     rb = read_pair<NX>(stage, pair + 1);
@@ -486,18 +418,12 @@ __global__ __launch_bounds__(64) void k_render_forward(RenderArgs a)
                     if (all_done) npairs = 0;
                     if (++pair >= npairs) break;
                 }
-#ifdef GSR_STATS
-                { FW_T(ts2); tw_eval += ts2 - ts1; n_pairs += (unsigned long long)pair; }
-#endif
+                WALK_STAT({ WALK_T(ts2); tw_eval += ts2 - ts1; n_pairs += (unsigned long long)pair; })
             }
-#ifdef GSR_STATS
-            FW_T(ts3);
-#endif
+            WALK_T(ts3);
             if (NX > 0) retire_prefetch_x(n0, n1, n2b, id_nn, nx0, nx1);
             else retire_prefetch(n0, n1, n2b, id_nn);
-#ifdef GSR_STATS
-            { FW_T(ts4); tw_wait += ts4 - ts3; }
-#endif
+            WALK_STAT({ WALK_T(ts4); tw_wait += ts4 - ts3; })
             if (all_done) break;
             c0 = n0; c1 = n1; c2b = n2b;
             if (NX > 0) { cx0 = nx0; cx1 = nx1; }
@@ -506,17 +432,7 @@ __global__ __launch_bounds__(64) void k_render_forward(RenderArgs a)
         }
     }
 
-#ifdef GSR_STATS
-    if (lane == 0 && blockIdx.x < (unsigned)FW_REC) {
-        FW_T(tw1);
-        unsigned* r_ = g_fwd_rec[blockIdx.x];
-        r_[0] = (unsigned)(tw1 - tw0); r_[1] = (unsigned)tw_wait; r_[2] = (unsigned)tw_stage; r_[3] = (unsigned)tw_eval;
-        r_[4] = 1u; r_[5] = (unsigned)n_rounds; r_[6] = (unsigned)n_pairs;
-        r_[7] = n_pairs_le8 | (n_pairs_le16 << 10) | (n_pairs_le32 << 20);   // (10 bits each: a wave evaluates < 1024 pairs)
-        g_fwd_hw[blockIdx.x][0] = __builtin_amdgcn_s_getreg(63492) | (__builtin_amdgcn_s_getreg(63508) << 28);   // HW_ID, XCC_ID
-        g_fwd_hw[blockIdx.x][1] = (unsigned)tw0;
-    }
-#endif
+    FW_PUT_RECORD(n_pairs_le8 | (n_pairs_le16 << 10) | (n_pairs_le32 << 20));   // (10 bits each: a wave evaluates < 1024 pairs)
     // instrumentation: how many list entries this tile really needed (max over its pixels); tile_need is zeroed
     // before the launch
     {
@@ -590,10 +506,8 @@ __device__ __forceinline__ void swap_halves2(float& a_lo, float& a_hi, float& b_
 
 __global__ __launch_bounds__(64) void k_render_forward_half(RenderArgs a)
 {
-#ifdef GSR_STATS
-    FW_T(tw0);
-    unsigned long long tw_wait = 0, tw_stage = 0, tw_eval = 0, n_rounds = 0, n_pairs = 0;   // (n_pairs: steps of four entries here)
-#endif
+    WALK_T(tw0);
+    WALK_STAT(unsigned long long tw_wait = 0, tw_stage = 0, tw_eval = 0, n_rounds = 0, n_pairs = 0;)   // (n_pairs: steps of four entries here)
     constexpr int PW = PAIR_WORDS;
     // workgroup b runs on XCD b % 8: the eight half-quadrants of one tile are b, b + 8, ..., b + 56 (one L2 fetch of list and records);
     // groups of 64 workgroups (8 tiles x 8 halves) are dealt to the views round-robin like the 8 x 8 kernel's groups of 32
@@ -614,12 +528,11 @@ __global__ __launch_bounds__(64) void k_render_forward_half(RenderArgs a)
     const uint32_t tile = a.tile_order[order_slot];
     const uint32_t sb = (blockIdx.x >> 3) & 7u, q = sb >> 1, hf = sb & 1u;
     const uint32_t lane = threadIdx.x, pl = lane & 31u, eg = lane >> 5;   // pixel of the half, entry group
-    const uint32_t tx = tile % (uint32_t)a.gridx, ty = tile / (uint32_t)a.gridx;
-    const uint32_t x0 = tx * TILE_X + (q & 1u) * 8u, y0 = ty * TILE_Y + (q >> 1) * 8u + hf * 4u;
-    const uint32_t px = x0 + (pl & 7u), py = y0 + (pl >> 3);
-    const bool inside = px < (uint32_t)a.W && py < (uint32_t)a.H;
-    const float pixf_x = (float)px, pixf_y = (float)py;
-    const float x0f = (float)x0, y0f = (float)y0;
+    QuadGeom g;
+    quad_geom(g, tile, q, a.gridx, a.W, a.H, pl, hf * 4u);
+    const uint32_t px = g.px, py = g.py;
+    const bool inside = g.inside;
+    const float pixf_x = g.pixf_x, pixf_y = g.pixf_y, x0f = g.x0f, y0f = g.y0f;
     float bx0 = x0f, by0 = y0f, bx1 = x0f + 7.f, by1 = y0f + 3.f;
 
     __shared__ __attribute__((aligned(16))) float stage[35 * PW];   // 32 pairs + a zero pair behind an odd count + read-ahead
@@ -672,10 +585,8 @@ __global__ __launch_bounds__(64) void k_render_forward_half(RenderArgs a)
                 if (eg == 0) a.ckpt[slot * 256 + q * 64 + hf * 32u + pl] = make_float4(T, C01.x, C01.y, C2);
                 crossed = true;
             }
-#ifdef GSR_STATS
-            FW_T(ts0);
-            n_rounds++;
-#endif
+            WALK_T(ts0);
+            WALK_STAT(n_rounds++;)
             const bool valid = base + (int)lane < total;
             const bool touch = valid && may_touch_rect(c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, bx0, by0, bx1, by1);
             const uint64_t mask = __ballot(touch);
@@ -775,10 +686,8 @@ __global__ __launch_bounds__(64) void k_render_forward_half(RenderArgs a)
                     }
                 };
                 int step = 0;
-#ifdef GSR_STATS
-                FW_T(ts1);
-                tw_stage += ts1 - ts0;
-#endif
+                WALK_T(ts1);
+                WALK_STAT(tw_stage += ts1 - ts0;)
                 StepRec ra = load_step(0), rb;
                 for (;;) {
                     rb = load_step(step + 1);
@@ -788,41 +697,22 @@ __global__ __launch_bounds__(64) void k_render_forward_half(RenderArgs a)
                     eval_step(rb);
                     if (all_done || ++step >= nsteps) break;
                 }
-#ifdef GSR_STATS
-                { FW_T(ts2); tw_eval += ts2 - ts1; n_pairs += (unsigned long long)step + 1ull; }
-#endif
+                WALK_STAT({ WALK_T(ts2); tw_eval += ts2 - ts1; n_pairs += (unsigned long long)step + 1ull; })
             }
-#ifdef GSR_STATS
-            FW_T(ts3);
-#endif
+            WALK_T(ts3);
             retire_prefetch(n0, n1, n2b, id_nn);
-#ifdef GSR_STATS
-            { FW_T(ts4); tw_wait += ts4 - ts3; }
-#endif
+            WALK_STAT({ WALK_T(ts4); tw_wait += ts4 - ts3; })
             if (all_done) break;
             c0 = n0; c1 = n1; c2b = n2b;
             id_cur = id_nxt;
             id_nxt = id_nn;
         }
     }
-#ifdef GSR_STATS
     // (record layout of the 8 x 8 kernel; word 6 counts steps, word 7 is the tile's list length: scripts/debug/fwd_half_tail.py)
-    if (lane == 0 && blockIdx.x < (unsigned)FW_REC) {
-        FW_T(tw1);
-        unsigned* r_ = g_fwd_rec[blockIdx.x];
-        r_[0] = (unsigned)(tw1 - tw0); r_[1] = (unsigned)tw_wait; r_[2] = (unsigned)tw_stage; r_[3] = (unsigned)tw_eval;
-        r_[4] = 1u; r_[5] = (unsigned)n_rounds; r_[6] = (unsigned)n_pairs; r_[7] = (unsigned)total;
-        g_fwd_hw[blockIdx.x][0] = __builtin_amdgcn_s_getreg(63492) | (__builtin_amdgcn_s_getreg(63508) << 28);   // HW_ID, XCC_ID
-        g_fwd_hw[blockIdx.x][1] = (unsigned)tw0;
-    }
-#endif
+    FW_PUT_RECORD((unsigned)total);
     {
         uint32_t need = inside ? (done ? stop_at : (uint32_t)total) : 0u;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const uint32_t o = __shfl_xor(need, d, 64);
-            need = need > o ? need : o;
-        }
+        wave_max_of(need);
         if (lane == 0 && need != 0) atomicMax(&a.tile_need[tile], need);
     }
     if (inside && eg == 0) {
@@ -864,9 +754,7 @@ int launch_render_forward(const Launch& L, const gsr_params& p, const Batch& B, 
     a.tile_order = B.iv.tile_order;
     a.point_list = point_list;
     a.splat = B.g.splat;
-    a.W = p.W; a.H = p.H;
-    a.gridx = (p.W + TILE_X - 1) / TILE_X;
-    const int gridy = (p.H + TILE_Y - 1) / TILE_Y;
+    set_frame_args(a, p, B);
     a.bg = p.bg;
     a.out_color = out_color;
     a.final_T = B.iv.final_T;
@@ -874,11 +762,7 @@ int launch_render_forward(const Launch& L, const gsr_params& p, const Batch& B, 
     a.tile_need = B.iv.tile_need;
     a.ckpt = with_ckpt ? B.b.ckpt : nullptr;
     a.accum = B.iv.accum;
-    a.V = (uint32_t)B.V;
-    a.g_stride = B.g_stride; a.b_stride = B.b_stride; a.iv_stride = B.iv_stride;
-    const int T = a.gridx * gridy;
-    a.num_tiles = T;
-    a.chunk_shift = B.chunk_shift();
+    const int T = a.num_tiles;
     // tile_need was cleared at the start of the frame (k_preprocess; the host on a retry / re-render)
     a.extra = nullptr; a.extra_scale = nullptr; a.bg_extra = nullptr; a.out_extra = nullptr; a.extra_vstride = 0;
     a.extra_hi = nullptr; a.extra_hi_vstride = 0;
