@@ -8,47 +8,72 @@
 // quadrant terminate in the forward pass, and covers only the pixels that consumed that deep in the backward pass).
 // Skipping is invisible in the results as long as it is CONSERVATIVE: an entry is dropped for a quadrant only
 // when  max over the quadrant's pixel centres of power(d) + E  <  log(1/(255*opacity)),  where
-// power(d) = -0.5 (A dx^2 + C dy^2) - B dx dy is concave for a positive-definite conic, its maximum over a
-// rectangle is found exactly on the centre / the four edges, and E bounds the fp32 rounding of both this
-// bound and the per-pixel evaluation (~170 ulp of the largest term, plus 1e-4 absolute).
+// power(d) = -0.5 (A dx^2 + C dy^2) - B dx dy is concave for a positive-definite conic with its maximum, 0, at the splat centre;
+// its maximum over a rectangle that does not hold the centre lies on one of the (at most two) edges that FACE the centre
+// (may_touch_rect), and E bounds the fp32 rounding of both this bound and the per-pixel evaluation (~170 ulp of the largest
+// term, plus 1e-4 absolute).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 
 namespace gsr {
 
-__device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
+__host__ __device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
+
+// The two hardware approximations of the footprint test, 1 ulp each on the device (v_rcp_f32, v_log_f32); the host build, which
+// exists for the test of the bound's algebra (tests/footprint_bound_main.cpp), takes the plain forms.
+__host__ __device__ __forceinline__ float cull_rcp(float x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_rcpf(x);
+#else
+    return 1.0f / x;
+#endif
+}
+__host__ __device__ __forceinline__ float cull_log2(float x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_logf(x);
+#else
+    return log2f(x);
+#endif
+}
 
 // May the Gaussian (mean (mx,my), conic (A,B,C), opacity o) reach alpha >= 1/255 at a pixel centre inside the
 // rectangle [x0, x1] x [y0, y1] (pixel-centre coordinates, inclusive)?  false = provably not.
-__device__ __forceinline__ bool may_touch_rect(float mx, float my, float A, float B, float C, float o, float x0, float y0,
-                                               float x1, float y1)
+//
+// The bound m >= max of power over the rectangle.  In d = mean - pixel the rectangle is [dxl, dxh] x [dyl, dyh] and the splat
+// centre is the origin.  (ex, ey) = the origin clamped to the rectangle, component by component.  If the origin lies inside,
+// both are 0 and both candidates below are power(0, 0) = 0, the true maximum.  Otherwise take any point p of the rectangle and
+// walk the ray from the origin to p: the first point of the rectangle on it lies on an edge that faces the origin -- the
+// vertical line dx = ex if ex != 0, the horizontal line dy = ey if ey != 0 -- and a concave function with its maximum at the
+// origin only falls along a ray from it, so power(p) <= power(that point) <= the maximum over the facing edges.  The two far
+// edges never decide and are not evaluated.  Along dx = ex the maximiser of the (concave, one-dimensional) power is
+// dy = -B ex / C clamped to [dyl, dyh]; along dy = ey it is dx = -B ey / A clamped to [dxl, dxh].  When ex == 0 (the centre is
+// above or below the rectangle) the first candidate is power(0, ey), a point of the horizontal facing edge: redundant, never
+// too large; likewise for ey == 0.
+__host__ __device__ __forceinline__ bool may_touch_rect(float mx, float my, float A, float B, float C, float o, float x0, float y0,
+                                                        float x1, float y1)
 {
     // NaN anywhere must mean "keep".  No explicit test is needed: every comparison below is written so that it is
     // false for NaN operands and false means keep (NaN opacity: not <= 0, thr = NaN; NaN conic: not provably concave;
     // NaN mean: E = NaN), and fmaxf drops a NaN candidate without making the bound larger than a real one.
     if (o <= 0.f) return false;  // alpha = o*exp(..) <= 0 < 1/255 at every pixel
     if (!(A > 0.f && C > 0.f && A * C - B * B > 0.f)) return true;  // not provably concave: keep
-    const float thr = -__logf(255.0f * o);  // alpha >= 1/255  <=>  power >= thr
+    // alpha >= 1/255  <=>  power >= thr = -log(255 o) = -ln 2 * log2(255 o).  The hardware log2 is good to 1 ulp and the product
+    // with ln 2 adds a rounding: |error| <= 3e-7 |thr|, and near 255 o = 1, where thr -> 0 and a relative bound says nothing,
+    // <= 1e-7 absolute (rounding of 255 o).  Both lie inside the 1e-5 |thr| + 1e-4 of E.  (A denormal 255 o may be flushed:
+    // thr = +inf, drop -- right, alpha <= o < 1/255.)
+    const float thr = -0x1.62e430p-1f * cull_log2(255.0f * o);
     // d = mean - pixel over the rectangle
     const float dxl = mx - x1, dxh = mx - x0, dyl = my - y1, dyh = my - y0;
-    float m;
-    if (dxl <= 0.f && dxh >= 0.f && dyl <= 0.f && dyh >= 0.f) {
-        m = 0.f;  // the mean lies inside the rectangle
-    } else {
-        m = -3.0e38f;
-        // Along an edge the maximiser is -B e / C (or / A), clamped to the edge.  A 1-ulp reciprocal is enough: evaluating
-        // the concave power a relative 1e-7 away from its maximiser lowers the value by ~1e-14 of its terms, far inside E.
-        const float nB_over_C = -B * __builtin_amdgcn_rcpf(C), nB_over_A = -B * __builtin_amdgcn_rcpf(A);
-#pragma unroll
-        for (int e = 0; e < 2; e++) {
-            const float ex = e ? dxh : dxl;
-            const float yy = clampf(nB_over_C * ex, dyl, dyh);
-            m = fmaxf(m, -0.5f * (A * ex * ex + C * yy * yy) - B * ex * yy);
-            const float ey = e ? dyh : dyl;
-            const float xx = clampf(nB_over_A * ey, dxl, dxh);
-            m = fmaxf(m, -0.5f * (A * xx * xx + C * ey * ey) - B * xx * ey);
-        }
-    }
+    const float ex = clampf(0.f, dxl, dxh), ey = clampf(0.f, dyl, dyh);
+    // A 1-ulp reciprocal is enough: evaluating the concave power a relative 1e-7 away from its maximiser lowers the value by
+    // ~1e-14 of its terms, far inside E.
+    const float yy = clampf(-B * cull_rcp(C) * ex, dyl, dyh);
+    float m = -0.5f * (A * ex * ex + C * yy * yy) - B * ex * yy;
+    const float xx = clampf(-B * cull_rcp(A) * ey, dxl, dxh);
+    m = fmaxf(m, -0.5f * (A * xx * xx + C * ey * ey) - B * xx * ey);
     const float ax = fmaxf(fabsf(dxl), fabsf(dxh)), ay = fmaxf(fabsf(dyl), fabsf(dyh));
     const float E = 1.0e-5f * (A * ax * ax + C * ay * ay + fabsf(B) * ax * ay) + 1.0e-4f + 1.0e-5f * fabsf(thr);
     return !(m + E < thr);
