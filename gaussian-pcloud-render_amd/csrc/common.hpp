@@ -431,6 +431,7 @@ int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B,
                            const ExtraChannels* X = nullptr, const ExtraGrads* XG = nullptr, const RenderBwdDet* D = nullptr);
 int backward_subquadrant_moments(int set);   // render_bwd.hip: set >= 0 stores; 1 = moments about the sub-quadrant centres
 int forward_half_views(int set);   // render_fwd.hip: set >= 0 stores; returns the views per submission up to which the half-quadrant forward runs
+int render_math(int set);           // render_fwd.hip: 0 / 1 stores, < 0 queries, > 1 is refused; returns the arithmetic mode of the inference forwards (0 exact, 1 fast)
 int selftest_mm(hipStream_t stream, float* d_scratch256);   // the matrix-core pixel contraction of the render backward
 // det_backward.hip: the steps of the deterministic backward around the storing render backward (D: view 0's scratch, d_stride apart)
 int launch_det_prepare(const Launch& L, const Batch& B, const DetView& D, size_t d_stride, const uint32_t* point_list, int T);

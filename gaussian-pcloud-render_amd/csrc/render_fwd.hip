@@ -28,6 +28,7 @@
 // simple_raw_render.py:410-524).  The extra values ride in the pair records next to the colour; NX = 0 is the plain kernel.
 #include <atomic>
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.hpp"
 #include "render_walk.hpp"
@@ -171,9 +172,29 @@ int debug_fwd_times(unsigned long long* out8, int reset)
         g_fwd_hw[blockIdx.x][1] = (unsigned)tw0;                                                                                    \
     })
 
-template <int NX>
-__global__ __launch_bounds__(64) void k_render_forward(RenderArgs a)
+// The arithmetic mode (render_math.hpp; gsr_set_render_math) is the TYPE of a trailing kernel argument, like the backward's
+// RenderBwdDet: the exact kernels take none -- MS is empty -- and keep their names, arguments and machine code; the fast ones are
+// k_render_forward<NX, RenderFast> and k_render_forward_half(RenderArgs, RenderFast).  Only the alpha evaluation, the blend and the
+// fold of the conic at staging differ (if constexpr); the gather pipeline, the culling, the LDS layout and the stores are one text.
+struct RenderFast {
+    uint32_t mode;   // 1 (never read: the type is the switch)
+};
+template <typename... MS> constexpr bool fwd_is_fast = (std::is_same<MS, RenderFast>::value || ...);
+
+// one channel (or channel pair) of one entry blended into a pixel's sum: exact (c e) t plus an add; fast one fused multiply-add with
+// w = e t -- the same expression for every channel of the entry, so it is formed once.  e = 0 leaves the sum unchanged bit for bit
+// in both (a sum is never -0).
+template <bool FAST, typename V>
+__device__ __forceinline__ void blend(V& acc, V c, float e, float t)
 {
+    if constexpr (FAST) blend_fast(acc, c, e * t);
+    else acc += c * e * t;
+}
+
+template <int NX, typename... MS>
+__global__ __launch_bounds__(64) void k_render_forward(RenderArgs a, MS...)
+{
+    constexpr bool FAST = fwd_is_fast<MS...>;
     WALK_T(tw0);
     WALK_STAT(unsigned long long tw_wait = 0, tw_stage = 0, tw_eval = 0, n_rounds = 0, n_pairs = 0;)
     WALK_STAT(unsigned live_cnt = 64, n_pairs_le8 = 0, n_pairs_le16 = 0, n_pairs_le32 = 0;)   // pairs evaluated while <= 8 / 16 / 32 pixels were live
@@ -311,6 +332,9 @@ __global__ __launch_bounds__(64) void k_render_forward(RenderArgs a)
                 const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
                 const uint32_t nsurv = (uint32_t)__popcll(mask);
                 if (touch) {
+                    if constexpr (FAST) {   // (after the footprint test; the round's records are not read again)
+                        c0.z = fold_square_term(c0.z); c0.w = fold_cross_term(c0.w); c1.x = fold_square_term(c1.x);
+                    }
                     const bool lone = stage_entry(stage, PW, slot, nsurv, c0, c1, c2b, (uint32_t)(base + (int)lane + 1));
                     if (NX > 0) {
                         f32x4 e0 = cx0, e1 = cx1;
@@ -340,9 +364,19 @@ __global__ __launch_bounds__(64) void k_render_forward(RenderArgs a)
                     const f32x2 X = {r.xy.x, r.xy.y}, Y = {r.xy.z, r.xy.w}, A2 = {r.ab.x, r.ab.y}, B2 = {r.ab.z, r.ab.w};
                     const f32x2 C2p = {r.co.x, r.co.y}, O2 = {r.co.z, r.co.w};
                     const f32x2 dx = X - pixf_x, dy = Y - pixf_y;
-                    const f32x2 power = -0.5f * (A2 * dx * dx + C2p * dy * dy) - B2 * dx * dy;
-                    const f32x2 al = O2 * exp_nonpos2(power);
-                    const float alpha0 = fminf(0.99f, al.x), alpha1 = fminf(0.99f, al.y);
+                    // (fast mode: A2, B2, C2p are the conic folded at staging and `power` is p2 = power log2 e, of the same sign)
+                    f32x2 power;
+                    float alpha0, alpha1;
+                    if constexpr (FAST) {
+                        power = power2_fast(A2, B2, C2p, dx, dy);
+                        alpha0 = alpha_fast(O2.x, power.x);
+                        alpha1 = alpha_fast(O2.y, power.y);
+                    } else {
+                        power = power_exact(A2, B2, C2p, dx, dy);
+                        const f32x2 al = O2 * exp_nonpos2(power);
+                        alpha0 = fminf(0.99f, al.x);
+                        alpha1 = fminf(0.99f, al.y);
+                    }
                     const bool cnt0 = !done && !(power.x > 0.0f) && !(alpha0 < 1.0f / 255.0f);
                     const bool cnt1 = !done && !(power.y > 0.0f) && !(alpha1 < 1.0f / 255.0f);
                     const float ae0 = cnt0 ? alpha0 : 0.f, ae1 = cnt1 ? alpha1 : 0.f;
@@ -354,14 +388,14 @@ __global__ __launch_bounds__(64) void k_render_forward(RenderArgs a)
                     if (!__any(T2 < 0.0001f)) {
                         // ae = 0 adds a zero, which leaves C unchanged bit-for-bit (C is never -0)
                         const f32x2 rg0 = {r.rg.x, r.rg.y}, rg1 = {r.rg.z, r.rg.w};
-                        C01 += rg0 * ae0 * T;
-                        C2 += r.b.x * ae0 * T;
-                        C01 += rg1 * ae1 * T1;
-                        C2 += r.b.y * ae1 * T1;
+                        blend<FAST>(C01, rg0, ae0, T);
+                        blend<FAST>(C2, r.b.x, ae0, T);
+                        blend<FAST>(C01, rg1, ae1, T1);
+                        blend<FAST>(C2, r.b.y, ae1, T1);
 #pragma unroll
                         for (int j = 0; j < NX / 2; j++) {
-                            CX[j] += f32x2{r.ex[j].x, r.ex[j].y} * ae0 * T;
-                            CX[j] += f32x2{r.ex[j].z, r.ex[j].w} * ae1 * T1;
+                            blend<FAST>(CX[j], f32x2{r.ex[j].x, r.ex[j].y}, ae0, T);
+                            blend<FAST>(CX[j], f32x2{r.ex[j].z, r.ex[j].w}, ae1, T1);
                         }
                         last_contributor = cnt0 ? eidx0 : last_contributor;
                         last_contributor = cnt1 ? eidx1 : last_contributor;
@@ -377,14 +411,14 @@ __global__ __launch_bounds__(64) void k_render_forward(RenderArgs a)
                         const float be0 = b0 ? alpha0 : 0.f, be1 = b1 ? alpha1 : 0.f;
                         const float U1 = T * (1 - be0), U2 = U1 * (1 - be1);
                         const f32x2 rg0 = {r.rg.x, r.rg.y}, rg1 = {r.rg.z, r.rg.w};
-                        C01 += rg0 * be0 * T;
-                        C2 += r.b.x * be0 * T;
-                        C01 += rg1 * be1 * U1;
-                        C2 += r.b.y * be1 * U1;
+                        blend<FAST>(C01, rg0, be0, T);
+                        blend<FAST>(C2, r.b.x, be0, T);
+                        blend<FAST>(C01, rg1, be1, U1);
+                        blend<FAST>(C2, r.b.y, be1, U1);
 #pragma unroll
                         for (int j = 0; j < NX / 2; j++) {
-                            CX[j] += f32x2{r.ex[j].x, r.ex[j].y} * be0 * T;
-                            CX[j] += f32x2{r.ex[j].z, r.ex[j].w} * be1 * U1;
+                            blend<FAST>(CX[j], f32x2{r.ex[j].x, r.ex[j].y}, be0, T);
+                            blend<FAST>(CX[j], f32x2{r.ex[j].z, r.ex[j].w}, be1, U1);
                         }
                         last_contributor = b0 ? eidx0 : last_contributor;
                         last_contributor = b1 ? eidx1 : last_contributor;
@@ -504,230 +538,18 @@ __device__ __forceinline__ void swap_halves2(float& a_lo, float& a_hi, float& b_
     b_hi = __uint_as_float(b[1]);
 }
 
+// The body is one text for both arithmetic modes (render_fwd_half_body.hpp, included into each kernel with FAST set): the exact kernel
+// keeps its name, its one argument and its machine code -- as a template or through an inlined body function it would keep neither --
+// and the fast one is its overload with the mode argument.
 __global__ __launch_bounds__(64) void k_render_forward_half(RenderArgs a)
 {
-    WALK_T(tw0);
-    WALK_STAT(unsigned long long tw_wait = 0, tw_stage = 0, tw_eval = 0, n_rounds = 0, n_pairs = 0;)   // (n_pairs: steps of four entries here)
-    constexpr int PW = PAIR_WORDS;
-    // workgroup b runs on XCD b % 8: the eight half-quadrants of one tile are b, b + 8, ..., b + 56 (one L2 fetch of list and records);
-    // groups of 64 workgroups (8 tiles x 8 halves) are dealt to the views round-robin like the 8 x 8 kernel's groups of 32
-    const uint32_t group = blockIdx.x >> 6;
-    const uint32_t view = group % a.V;
-    const uint32_t order_slot = (group / a.V) * 8u + (blockIdx.x & 7u);
-    if (order_slot >= (uint32_t)a.num_tiles) return;
-    a.ranges = at_view(a.ranges, a.iv_stride, view);
-    a.tile_order = at_view(a.tile_order, a.iv_stride, view);
-    a.final_T = at_view(a.final_T, a.iv_stride, view);
-    a.n_contrib = at_view(a.n_contrib, a.iv_stride, view);
-    a.tile_need = at_view(a.tile_need, a.iv_stride, view);
-    a.accum = at_view(a.accum, a.iv_stride, view);
-    a.point_list = at_view(a.point_list, a.b_stride, view);
-    if (a.ckpt) a.ckpt = at_view(a.ckpt, a.b_stride, view);
-    a.splat = at_view(a.splat, a.g_stride, view);
-    a.out_color += (size_t)view * 3u * (size_t)a.W * (size_t)a.H;
-    const uint32_t tile = a.tile_order[order_slot];
-    const uint32_t sb = (blockIdx.x >> 3) & 7u, q = sb >> 1, hf = sb & 1u;
-    const uint32_t lane = threadIdx.x, pl = lane & 31u, eg = lane >> 5;   // pixel of the half, entry group
-    QuadGeom g;
-    quad_geom(g, tile, q, a.gridx, a.W, a.H, pl, hf * 4u);
-    const uint32_t px = g.px, py = g.py;
-    const bool inside = g.inside;
-    const float pixf_x = g.pixf_x, pixf_y = g.pixf_y, x0f = g.x0f, y0f = g.y0f;
-    float bx0 = x0f, by0 = y0f, bx1 = x0f + 7.f, by1 = y0f + 3.f;
-
-    __shared__ __attribute__((aligned(16))) float stage[35 * PW];   // 32 pairs + a zero pair behind an odd count + read-ahead
-
-    const uint2 range = a.ranges[tile];
-    const int total = (int)(range.y - range.x);
-
-    float T = 1.0f;
-    f32x2 C01 = {0.f, 0.f};
-    float C2 = 0.f;
-    uint32_t last_contributor = 0;
-    uint32_t stop_at = 0;
-    bool crossed = false;
-    bool done = !inside;
-    bool all_done = __all(done);
-    if (!all_done) {
-        int ax, ay, bx, by;
-        live_box(__ballot(!done) & 0xFFFFFFFFull, ax, ay, bx, by);   // (both halves of the wave hold the same 32 pixels)
-        bx0 = x0f + (float)ax; by0 = y0f + (float)ay; bx1 = x0f + (float)bx; by1 = y0f + (float)by;
-    }
-
-    if (!all_done && total > 0) {
-        const uint32_t* plist = a.point_list + range.x;
-        const int last = total - 1;
-        f32x4 c0, c1, n0, n1;
-        float c2b, n2b;
-        uint32_t id_cur, id_nxt, id_nn;
-        {
-            prefetch4(id_cur, plist + ((int)lane < total ? (int)lane : last));
-            prefetch4(id_nxt, plist + (64 + (int)lane < total ? 64 + (int)lane : last));
-            asm volatile("s_waitcnt vmcnt(0)" : "+v"(id_cur), "+v"(id_nxt)::"memory");
-            const Splat* sp = a.splat + id_cur;
-            prefetch16(c0, &sp->q0);
-            prefetch16(c1, &sp->q1);
-            prefetch4f(c2b, &sp->q2);
-            retire_prefetch(c0, c1, c2b, id_nxt);
-        }
-        for (int base = 0; base < total; base += 64) {
-            {
-                const Splat* sp = a.splat + id_nxt;
-                prefetch16(n0, &sp->q0);
-                prefetch16(n1, &sp->q1);
-                prefetch4f(n2b, &sp->q2);
-                const int i2 = base + 128 + (int)lane;
-                prefetch4(id_nn, plist + (i2 < total ? i2 : last));
-            }
-            // the backward's slice-boundary state: pixel (x, y) of the quadrant sits at index 8 y + x = 32 hf + pl, as in the 8 x 8 kernel
-            if (a.ckpt != nullptr && base != 0 && (base & ((1 << a.chunk_shift) - 1)) == 0 && (base >> a.chunk_shift) < BWD_MAX_CHUNKS) {
-                const size_t slot = (size_t)(range.x >> a.chunk_shift) + (size_t)(base >> a.chunk_shift);
-                if (eg == 0) a.ckpt[slot * 256 + q * 64 + hf * 32u + pl] = make_float4(T, C01.x, C01.y, C2);
-                crossed = true;
-            }
-            WALK_T(ts0);
-            WALK_STAT(n_rounds++;)
-            const bool valid = base + (int)lane < total;
-            const bool touch = valid && may_touch_rect(c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, bx0, by0, bx1, by1);
-            const uint64_t mask = __ballot(touch);
-            if (mask != 0) {
-                const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-                const uint32_t nsurv = (uint32_t)__popcll(mask);
-                const int npairs = (int)((nsurv + 1u) >> 1);
-                if (touch) stage_entry(stage, PW, slot, nsurv, c0, c1, c2b, (uint32_t)(base + (int)lane + 1));
-                // an odd number of PAIRS: the upper half's record of the last step is a pair of opacity 0 (alpha 0: never counted)
-                if ((npairs & 1) && lane < (uint32_t)PW) stage[npairs * PW + lane] = 0.f;
-                const int nsteps = (npairs + 1) >> 1;
-                // a step's seven LDS reads: the half's own pair record (alpha of two entries) and, from both records of the step,
-                // colours and list positions.  The next step's are issued before the current one is evaluated (two register sets
-                // taking turns, like the 8 x 8 kernel's pairs); the read past the last step lands in the spare records.
-                struct StepRec {
-                    f32x4 xy, ab, co, rgA, rgB;
-                    f32x2 bA, bB;
-                    uint2 posA, posB;
-                };
-                auto load_step = [&](int st) {
-                    StepRec r;
-                    const float* po = stage + (2 * st + (int)eg) * PW;
-                    const float* pa = stage + (2 * st) * PW;
-                    r.xy = *(const f32x4*)(po + 0);
-                    r.ab = *(const f32x4*)(po + 4);
-                    r.co = *(const f32x4*)(po + 8);
-                    r.rgA = *(const f32x4*)(pa + 12);
-                    r.rgB = *(const f32x4*)(pa + PW + 12);
-                    r.bA = *(const f32x2*)(pa + 16);
-                    r.bB = *(const f32x2*)(pa + PW + 16);
-                    r.posA = *(const uint2*)(pa + 18);
-                    r.posB = *(const uint2*)(pa + PW + 18);
-                    return r;
-                };
-                auto eval_step = [&](const StepRec& r) {
-                    const f32x4 rgA = r.rgA, rgB = r.rgB;
-                    const f32x2 bA = r.bA, bB = r.bB;
-                    const uint2 posA = r.posA, posB = r.posB;
-                    const f32x2 X = {r.xy.x, r.xy.y}, Y = {r.xy.z, r.xy.w}, A2 = {r.ab.x, r.ab.y}, B2 = {r.ab.z, r.ab.w};
-                    const f32x2 C2p = {r.co.x, r.co.y}, O2 = {r.co.z, r.co.w};
-                    const f32x2 dx = X - pixf_x, dy = Y - pixf_y;
-                    const f32x2 power = -0.5f * (A2 * dx * dx + C2p * dy * dy) - B2 * dx * dy;
-                    const f32x2 al = O2 * exp_nonpos2(power);
-                    const float alpha0 = fminf(0.99f, al.x), alpha1 = fminf(0.99f, al.y);
-                    // an entry counts for a pixel that is still live when the STEP begins; pixels that stop inside the step are
-                    // handled by the exact path below.  alpha >= 1/255 > 0 for every counted entry, so "counted" <=> e != 0.
-                    float ea = (!done && !(power.x > 0.0f) && !(alpha0 < 1.0f / 255.0f)) ? alpha0 : 0.f;
-                    float eb = (!done && !(power.y > 0.0f) && !(alpha1 < 1.0f / 255.0f)) ? alpha1 : 0.f;
-                    float e0 = ea, e2 = ea, e1 = eb, e3 = eb;
-                    swap_halves2(e0, e2, e1, e3);   // e0 / e1: the lower half's two entries, e2 / e3: the upper half's, in every lane
-                    const float T1 = T * (1 - e0), T2 = T1 * (1 - e1), T3 = T2 * (1 - e2), T4 = T3 * (1 - e3);
-                    if (!__any(T4 < 0.0001f)) {
-                        // no pixel of the wave stops inside the step (T never increases, every live pixel has T >= 1e-4)
-                        C01 += f32x2{rgA.x, rgA.y} * e0 * T;
-                        C2 += bA.x * e0 * T;
-                        C01 += f32x2{rgA.z, rgA.w} * e1 * T1;
-                        C2 += bA.y * e1 * T1;
-                        C01 += f32x2{rgB.x, rgB.y} * e2 * T2;
-                        C2 += bB.x * e2 * T2;
-                        C01 += f32x2{rgB.z, rgB.w} * e3 * T3;
-                        C2 += bB.y * e3 * T3;
-                        last_contributor = e0 != 0.f ? posA.x : last_contributor;
-                        last_contributor = e1 != 0.f ? posA.y : last_contributor;
-                        last_contributor = e2 != 0.f ? posB.x : last_contributor;
-                        last_contributor = e3 != 0.f ? posB.y : last_contributor;
-                        T = T4;
-                    } else {
-                        // some pixel stops inside these four entries: the reference's sequence, entry by entry.  s: the entry
-                        // would take T below 1e-4 -> the pixel stops and the entry is NOT blended; b: the entry is blended.
-                        bool stopped = false;
-                        const float es[4] = {e0, e1, e2, e3};
-                        const f32x2 rgs[4] = {f32x2{rgA.x, rgA.y}, f32x2{rgA.z, rgA.w}, f32x2{rgB.x, rgB.y}, f32x2{rgB.z, rgB.w}};
-                        const float bs[4] = {bA.x, bA.y, bB.x, bB.y};
-                        const uint32_t ps[4] = {posA.x, posA.y, posB.x, posB.y};
-#pragma unroll
-                        for (int k = 0; k < 4; k++) {
-                            const bool c = es[k] != 0.f && !stopped;
-                            const float Tn = T * (1 - es[k]);
-                            const bool sk = c && (Tn < 0.0001f);
-                            const bool bk = c && !sk;
-                            const float be = bk ? es[k] : 0.f;
-                            C01 += rgs[k] * be * T;
-                            C2 += bs[k] * be * T;
-                            T = T * (1 - be);
-                            last_contributor = bk ? ps[k] : last_contributor;
-                            stop_at = sk ? ps[k] : stop_at;
-                            stopped = stopped || sk;
-                        }
-                        done = done || stopped;
-                        const uint64_t live = __ballot(!done) & 0xFFFFFFFFull;
-                        all_done = live == 0;
-                        if (!all_done) {
-                            int ax, ay, bx, by;
-                            live_box(live, ax, ay, bx, by);
-                            bx0 = x0f + (float)ax; by0 = y0f + (float)ay; bx1 = x0f + (float)bx; by1 = y0f + (float)by;
-                        }
-                    }
-                };
-                int step = 0;
-                WALK_T(ts1);
-                WALK_STAT(tw_stage += ts1 - ts0;)
-                StepRec ra = load_step(0), rb;
-                for (;;) {
-                    rb = load_step(step + 1);
-                    eval_step(ra);
-                    if (all_done || ++step >= nsteps) break;
-                    ra = load_step(step + 1);
-                    eval_step(rb);
-                    if (all_done || ++step >= nsteps) break;
-                }
-                WALK_STAT({ WALK_T(ts2); tw_eval += ts2 - ts1; n_pairs += (unsigned long long)step + 1ull; })
-            }
-            WALK_T(ts3);
-            retire_prefetch(n0, n1, n2b, id_nn);
-            WALK_STAT({ WALK_T(ts4); tw_wait += ts4 - ts3; })
-            if (all_done) break;
-            c0 = n0; c1 = n1; c2b = n2b;
-            id_cur = id_nxt;
-            id_nxt = id_nn;
-        }
-    }
-    // (record layout of the 8 x 8 kernel; word 6 counts steps, word 7 is the tile's list length: scripts/debug/fwd_half_tail.py)
-    FW_PUT_RECORD((unsigned)total);
-    {
-        uint32_t need = inside ? (done ? stop_at : (uint32_t)total) : 0u;
-        wave_max_of(need);
-        if (lane == 0 && need != 0) atomicMax(&a.tile_need[tile], need);
-    }
-    if (inside && eg == 0) {
-        const size_t pix = (size_t)py * a.W + px, N = (size_t)a.W * a.H;
-        a.final_T[pix] = T;
-        a.n_contrib[pix] = last_contributor;
-        a.out_color[pix] = C01.x + T * a.bg[0];
-        a.out_color[N + pix] = C01.y + T * a.bg[1];
-        a.out_color[2 * N + pix] = C2 + T * a.bg[2];
-        if (crossed) {
-            a.accum[pix] = C01.x;
-            a.accum[N + pix] = C01.y;
-            a.accum[2 * N + pix] = C2;
-        }
-    }
+    constexpr bool FAST = false;
+#include "render_fwd_half_body.hpp"
+}
+__global__ __launch_bounds__(64) void k_render_forward_half(RenderArgs a, RenderFast)
+{
+    constexpr bool FAST = true;
+#include "render_fwd_half_body.hpp"
 }
 
 // views per submission up to which the forward runs in half-quadrant mode: GSR_FWD_HALF_V in the environment when the library is
@@ -742,6 +564,21 @@ int forward_half_views(int set)
         v = e ? atoi(e) : 1;
         if (v < 0) v = 0;
         g_fwd_half_v.store(v);
+    }
+    return v;
+}
+
+// arithmetic of the forwards that save nothing for a backward: GSR_RENDER_MATH in the environment when the library is first used
+// (0 exact, the default; 1 fast), or gsr_set_render_math().  set < 0 queries; a value above 1 is refused (the value in force stays).
+static std::atomic<int> g_render_math{-1};
+int render_math(int set)
+{
+    if (set == 0 || set == 1) g_render_math.store(set);
+    int v = g_render_math.load();
+    if (v < 0) {
+        const char* e = getenv("GSR_RENDER_MATH");
+        v = (e && atoi(e) == 1) ? 1 : 0;
+        g_render_math.store(v);
     }
     return v;
 }
@@ -768,18 +605,30 @@ int launch_render_forward(const Launch& L, const gsr_params& p, const Batch& B, 
     a.extra_hi = nullptr; a.extra_hi_vstride = 0;
     a.xckpt = nullptr; a.xaccum = nullptr; a.x_stride = 0;
     const dim3 grid((unsigned)div_up(T, 8) * 32u * (unsigned)B.V);
+    // a permission, not a demand: a forward that saves for a backward runs the exact kernels whatever the switch says (the backward
+    // re-evaluates alpha in exact arithmetic against this forward's T, C and n_contrib)
+    const bool fast = !with_ckpt && render_math(-1) == 1;
+    const RenderFast F{1u};
     if (X != nullptr && X->nx > 0) {
         a.extra = X->values; a.extra_scale = X->view_scale; a.bg_extra = X->bg; a.out_extra = X->out; a.extra_vstride = X->view_stride;
         a.extra_hi = X->values_hi; a.extra_hi_vstride = X->hi_view_stride;
         if (with_ckpt && X->state.ckpt != nullptr) {
             a.xckpt = X->state.ckpt; a.xaccum = X->state.accum; a.x_stride = X->state_stride;
         }
-        if (X->nx == 4) hipLaunchKernelGGL(k_render_forward<4>, grid, dim3(64), 0, L.stream, a);
-        else hipLaunchKernelGGL(k_render_forward<8>, grid, dim3(64), 0, L.stream, a);
+        if (X->nx == 4) {
+            if (fast) hipLaunchKernelGGL((k_render_forward<4, RenderFast>), grid, dim3(64), 0, L.stream, a, F);
+            else hipLaunchKernelGGL(k_render_forward<4>, grid, dim3(64), 0, L.stream, a);
+        } else {
+            if (fast) hipLaunchKernelGGL((k_render_forward<8, RenderFast>), grid, dim3(64), 0, L.stream, a, F);
+            else hipLaunchKernelGGL(k_render_forward<8>, grid, dim3(64), 0, L.stream, a);
+        }
     } else if (B.V <= forward_half_views(-1)) {
-        hipLaunchKernelGGL(k_render_forward_half, dim3((unsigned)div_up(T, 8) * 64u * (unsigned)B.V), dim3(64), 0, L.stream, a);
+        const dim3 grid_half((unsigned)div_up(T, 8) * 64u * (unsigned)B.V);
+        if (fast) hipLaunchKernelGGL((void (*)(RenderArgs, RenderFast))k_render_forward_half, grid_half, dim3(64), 0, L.stream, a, F);
+        else hipLaunchKernelGGL((void (*)(RenderArgs))k_render_forward_half, grid_half, dim3(64), 0, L.stream, a);
     } else {
-        hipLaunchKernelGGL(k_render_forward<0>, grid, dim3(64), 0, L.stream, a);
+        if (fast) hipLaunchKernelGGL((k_render_forward<0, RenderFast>), grid, dim3(64), 0, L.stream, a, F);
+        else hipLaunchKernelGGL(k_render_forward<0>, grid, dim3(64), 0, L.stream, a);
     }
     return check_launch(L, "render_forward");
 }

@@ -1,16 +1,14 @@
 // render_walk.hpp -- what the render kernels (render_fwd.hip: k_render_forward<NX>, k_render_forward_half; render_bwd.hip:
-// k_render_backward<MODE, NX, ...>) share.  All three: the vector types, the hand-retired prefetch loads, exp_nonpos, the
-// instrumentation macros and the host helpers.  k_render_forward_half and k_render_backward also the quadrant geometry and the
-// wave maximum; k_render_forward<NX> keeps its own copies of those two, because its machine code moves with the shared ones
+// k_render_backward<MODE, NX, ...>) share.  All three: the hand-retired prefetch loads, the instrumentation macros and the host
+// helpers (the vector types and exp_nonpos come with render_math.hpp).  k_render_forward_half and k_render_backward also the quadrant
+// geometry and the wave maximum; k_render_forward<NX> keeps its own copies of those two, because its machine code moves with the shared ones
 // (profiles/r10_render_walk_refactor.txt, which also records why the gather pipeline itself is still written out per kernel).
 #pragma once
 
 #include "common.hpp"
+#include "render_math.hpp"
 
 namespace gsr {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Prefetch loads are issued as inline asm so that hipcc's waitcnt pass does not see them: left to itself it puts
 // an s_waitcnt for the NEXT round's records inside the CURRENT round's evaluation loop and re-exposes the gather
@@ -35,37 +33,6 @@ __device__ __forceinline__ void retire_prefetch(f32x4& a, f32x4& b, float& c, ui
 __device__ __forceinline__ void retire_prefetch_x(f32x4& a, f32x4& b, float& c, uint32_t& d, f32x4& e, f32x4& f)
 {
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f)::"memory");
-}
-
-// exp(x) for the compositing loop.  Instruction-for-instruction the core of the ocml expf that `exp(power)` of the
-// reference resolves to under hipcc (extended-precision x*log2(e), v_rndne, v_exp_f32, v_ldexp_f32), minus its two
-// range clamps: x > 88.7 -> inf and x < -103.3 -> 0.  Neither can change a decision or a blended value: entries
-// with power > 0 are skipped before alpha is used, and for x < -103 both forms give a value < 1e-44, far below
-// the 1/255 cut for any finite opacity.  For every x in [-103, 0] the result is bit-identical to expf(x).
-__device__ __forceinline__ float exp_nonpos(float x)
-{
-    const float ph = x * 0x1.715476p+0f;
-    float pl = __builtin_fmaf(x, 0x1.715476p+0f, -ph);
-    pl = __builtin_fmaf(x, 0x1.4ae0bep-26f, pl);
-    const float e = __builtin_rintf(ph);
-    const float r = __builtin_amdgcn_exp2f((ph - e) + pl);
-    return __builtin_ldexpf(r, (int)e);
-}
-
-// two-entry version: the multiplies / fused multiply-adds / adds become packed fp32 instructions (v_pk_*_f32, two
-// IEEE operations per lane per issue slot); rounding per component is that of exp_nonpos
-__device__ __forceinline__ f32x2 exp_nonpos2(f32x2 x)
-{
-    const f32x2 c = {0x1.715476p+0f, 0x1.715476p+0f}, cc = {0x1.4ae0bep-26f, 0x1.4ae0bep-26f};
-    const f32x2 ph = x * c;
-    f32x2 pl = __builtin_elementwise_fma(x, c, -ph);
-    pl = __builtin_elementwise_fma(x, cc, pl);
-    const f32x2 e = {__builtin_rintf(ph.x), __builtin_rintf(ph.y)};
-    const f32x2 a = (ph - e) + pl;
-    f32x2 r;
-    r.x = __builtin_ldexpf(__builtin_amdgcn_exp2f(a.x), (int)e.x);
-    r.y = __builtin_ldexpf(__builtin_amdgcn_exp2f(a.y), (int)e.y);
-    return r;
 }
 
 // Where a wave's pixels are: quadrant q of `tile` (8 x 8 pixels from (x0, y0); the half-quadrant forward passes the pixel index

@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from . import _native as _C
 from ._native import get_deterministic, set_deterministic  # noqa: F401  (the deterministic-backward switch)
+from ._native import get_render_math, set_render_math  # noqa: F401  (arithmetic mode of the inference forwards)
 
 
 def cpu_deep_copy_tuple(input_tuple):

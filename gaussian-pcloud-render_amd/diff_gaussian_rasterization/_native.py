@@ -66,6 +66,7 @@ _DECL = {
     "gsr_set_profiling": (None, [_int]),
     "gsr_set_forward_half_views": (_int, [_int]),
     "gsr_set_backward_moments": (_int, [_int]),
+    "gsr_set_render_math": (_int, [_int]),
     "gsr_get_profile": (_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _int]),
     "gsr_selftest": (_int, [_fp]),
     "gsr_d2h_count": (C.c_longlong, []),
@@ -937,6 +938,31 @@ def set_backward_moments(mode):
     that kernel's time), 2 (default) per batch of eight entries, the sub-quadrant way only where a splat lies far from the quadrant
     centre in its own sigmas (1.33x / 2.1x, +0.8 %); include/gsr.h gsr_set_backward_moments, GSR_BWD_SUBQ.  Returns the mode in force."""
     return int(lib.gsr_set_backward_moments(int(mode)))
+
+
+_RENDER_MATH = {"exact": 0, "fast": 1}
+
+
+def set_render_math(mode):
+    """Arithmetic of the inference forwards (need_backward = False): "exact" / 0 (default) bit-identical to the reference build,
+    "fast" / 1 fewer instructions per (pixel, entry), within the 1e-4 contract of the exact mode except at threshold decisions,
+    deterministic, not bit-identical to the reference; training forwards ignore it (include/gsr.h gsr_set_render_math,
+    GSR_RENDER_MATH).  Process-wide.  Returns the name of the mode in force."""
+    if isinstance(mode, str):
+        if mode not in _RENDER_MATH:
+            raise ValueError("render math is 'exact' or 'fast' (0 or 1), not %r" % (mode,))
+        m = _RENDER_MATH[mode]
+    else:
+        m = int(mode)
+        if isinstance(mode, bool) or m not in (0, 1):
+            raise ValueError("render math is 'exact' or 'fast' (0 or 1), not %r" % (mode,))
+    lib.gsr_set_render_math(m)
+    return get_render_math()
+
+
+def get_render_math():
+    """"exact" or "fast": the arithmetic mode of the inference forwards in force"""
+    return "fast" if int(lib.gsr_set_render_math(-1)) == 1 else "exact"
 
 
 def set_profiling(on):

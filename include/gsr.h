@@ -321,6 +321,21 @@ int gsr_set_forward_half_views(int views);
  * Returns the value in force. */
 int gsr_set_backward_moments(int mode);
 
+/* Arithmetic of the forward render of INFERENCE calls (GSR_RENDER_MATH in the environment, read when the library is first used):
+ * 0 (DEFAULT) exact: the reference's operations one rounding at a time; images, final_T and n_contrib equal a strict-order build of
+ * the reference bit for bit.  1 fast (csrc/render_math.hpp): the constants -0.5 log2(e) / -log2(e) folded into the conic once per staged
+ * entry, the power as two multiplies and two fused multiply-adds, alpha = min(0.99, o 2^p) on the hardware's exp2 without range
+ * reduction, and one fused multiply-add per blended channel.  What the fast mode promises: it is deterministic from call to call (and
+ * the same in both forward kernels, alone or in a batch); radii, num_rendered, lists and ranges are those of the exact mode; every
+ * alpha is as accurate against float64 as the exact mode's, so images lie within the contract's 1e-4 of the exact mode's except at
+ * pixels where an alpha sits on the 1/255 cut or a transmittance on the 1e-4 stop and the decision falls the other way (the reference
+ * as shipped, compiled with FMA contraction, differs from its strict build in the same way).  What it does not promise: bit-identity
+ * with any build of the reference.  The mode is a permission, not a demand: it applies to forwards that save nothing for a backward
+ * (need_backward = 0: gsr_forward_batch, gsr_forward_batch_channels, gsr_forward_batch_channels_train, gsr_forward_stage2,
+ * gsr_forward_recolor); a forward with need_backward = 1 runs the exact kernels whatever the switch says, and every backward is
+ * untouched.  mode < 0 only queries; a value above 1 is refused and changes nothing.  Returns the value in force. */
+int gsr_set_render_math(int mode);
+
 const char* gsr_last_error(void);
 const char* gsr_version(void);
 

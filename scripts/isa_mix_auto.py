@@ -35,7 +35,9 @@ def classify(op, rest):
 
 
 def kernel_body(lines, sym):
-    st = next(i for i, l in enumerate(lines) if l.startswith("_Z") and sym in l.split(":")[0] and l.split(";")[0].strip().endswith(":"))
+    # (a symbol that is a whole label's tail wins over one that merely contains it: the exact half kernel's name is a prefix of the fast one's)
+    labels = [(i, l.split(":")[0]) for i, l in enumerate(lines) if l.startswith("_Z") and sym in l.split(":")[0] and l.split(";")[0].strip().endswith(":")]
+    st = next((i for i, n in labels if n.endswith(sym)), labels[0][0])
     end = next(i for i in range(st, len(lines)) if "s_endpgm" in lines[i])
     return [l.strip() for l in lines[st:end + 1]]
 
@@ -97,8 +99,13 @@ def has(seg, pat):
 
 
 JOBS = [("render_bwd-hip-amdgcn-amd-amdhsa-gfx950.s", "k_render_backwardILi0E", "k_render_backward<0>: the common path of the default k_render_backward<2> (same loops; <2> adds one compare per staged entry, a ballot per batch and the cold sub-quadrant path)", True),
-        ("render_fwd-hip-amdgcn-amd-amdhsa-gfx950.s", "k_render_forwardILi0E", "k_render_forward<0> (8 x 8 quadrants: batches)", False),
-        ("render_fwd-hip-amdgcn-amd-amdhsa-gfx950.s", "k_render_forward_half", "k_render_forward_half (single-view submissions)", False)]
+        ("render_fwd-hip-amdgcn-amd-amdhsa-gfx950.s", "k_render_forwardILi0EJEE", "k_render_forward<0> (8 x 8 quadrants: batches)", False),
+        ("render_fwd-hip-amdgcn-amd-amdhsa-gfx950.s", "k_render_forward_halfENS_10RenderArgsE", "k_render_forward_half (single-view submissions)", False),
+        # the fast arithmetic mode of the inference forwards (gsr_set_render_math(1)): the same kernels with a RenderFast argument
+        ("render_fwd-hip-amdgcn-amd-amdhsa-gfx950.s", "k_render_forwardILi0EJNS_10RenderFastEEE", "k_render_forward<0, RenderFast> (fast render math)", False),
+        ("render_fwd-hip-amdgcn-amd-amdhsa-gfx950.s", "k_render_forwardILi8EJEE", "k_render_forward<8> (eight extra channels)", False),
+        ("render_fwd-hip-amdgcn-amd-amdhsa-gfx950.s", "k_render_forwardILi8EJNS_10RenderFastEEE", "k_render_forward<8, RenderFast> (fast render math)", False),
+        ("render_fwd-hip-amdgcn-amd-amdhsa-gfx950.s", "k_render_forward_halfENS_10RenderArgsENS_10RenderFastE", "k_render_forward_half(RenderArgs, RenderFast) (fast render math)", False)]
 for fn, sym, title, bwd in JOBS:
     lines = open(os.path.join(BUILD, fn)).read().splitlines()
     body = kernel_body(lines, sym)
