@@ -565,7 +565,28 @@ size_t gsr_backward_det_bytes(int V, int P, int W, int H, int64_t pairs)
     return (size_t)V * det_view_bytes(W, H, pairs) + 256;
 }
 
-// ---- the backward: one sequence behind gsr_backward, gsr_backward_batch, gsr_backward_batch_det and gsr_backward_batch_channels ----
+// per-view bytes of the deterministic channels backward's scratch: the colour block, then the extras' slots
+static size_t det_x_view_bytes(int W, int H, int64_t pairs, int nx)
+{
+    const int T = ((W + TILE_X - 1) / TILE_X) * ((H + TILE_Y - 1) / TILE_Y);
+    return align_up(det_x_view(nullptr, T, pairs, nx).bytes, 256);
+}
+// bytes of the staging of the rows the views share, behind the V view blocks
+static size_t det_x_stage_bytes(int V, int P, int nx, int extra_per_view)
+{
+    return align_up((size_t)V * (size_t)(P > 0 ? P : 0) * (size_t)det_x_shared_channels(nx, extra_per_view) * sizeof(float), 256);
+}
+
+size_t gsr_backward_det_channels_bytes(int V, int P, int W, int H, int64_t pairs, int nx, int extra_per_view)
+{
+    if (V < 1 || W <= 0 || H <= 0) return 0;
+    if ((nx != 4 && nx != 8) || extra_per_view < 0 || extra_per_view > 2 || (extra_per_view == 2 && nx != 8)) return 0;
+    if (pairs > 0xFFFFFFFFll) pairs = 0xFFFFFFFFll;
+    return (size_t)V * det_x_view_bytes(W, H, pairs, nx) + det_x_stage_bytes(V, P, nx, extra_per_view) + 256;
+}
+
+// ---- the backward: one sequence behind gsr_backward, gsr_backward_batch, gsr_backward_batch_det, gsr_backward_batch_channels and
+// gsr_backward_batch_channels_det ----
 struct BwdGrads {   // dL/d image in, the eight gradient outputs (include/gsr.h)
     const float* dL_dpix;
     float *dL_dmean2D, *dL_dopacity, *dL_dcolor, *dL_dmean3D, *dL_dcov3D, *dL_dsh, *dL_dscale, *dL_drot;
@@ -631,12 +652,12 @@ static int check_bwd_frame(const void* geom, const gsr_params* p, int V, const B
     return GSR_OK;
 }
 
-// det / x: at most one of the two optional parts (there is no deterministic channels backward).
+// det / x: the two optional parts; both = the deterministic channels backward (the scratch block then also holds the extras' slots
+// and the staging of the rows the views share).
 static int backward_impl(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
                          size_t binning_bytes, const void* image, size_t image_bytes, const BwdGrads& G, const BwdDet* det, BwdExtra* x,
                          gsr_stream_t stream)
 {
-    if (det && x) return fail(GSR_ERR_INVALID, "[gsr] backward: no deterministic backward of the extra channels");
     if (int e = check_params(p, V)) return e;
     if (p->P == 0) return GSR_OK;
     // which fault a call with several reports is part of each entry's contract: the colour entries look at the pointers first, the
@@ -653,14 +674,36 @@ static int backward_impl(const gsr_params* p, int V, const int* radii, const voi
         return e;
     const Launch L{(hipStream_t)stream, p->debug};
     const int T = tile_count(p), res = sorted_buffer(T);
+    if (x) {
+        const int nx = x->X.nx;
+        x->X.state = xstate_view(align256(const_cast<void*>(x->state)), p->W, p->H, B.b.cap, nx);
+        x->X.state_stride = xstate_view_bytes(p->W, p->H, B.b.cap, nx);
+        if (x->state_bytes < (size_t)V * x->X.state_stride + 256)
+            return fail(GSR_ERR_CAPACITY, "[gsr] extra-state block too small for this binning arena");
+    }
     // deterministic: one slot per (consumed list entry, quadrant) in the caller's scratch block.  The block has to hold the
     // forward's lists: their largest per-view pair count from the arena's record, or -- no record -- the binning arena's capacity
     DetView D{};
     size_t d_stride = 0;
-    if (det) {
-        int64_t n = list_pairs >= 0 ? list_pairs : B.b.cap;
-        if (n > B.b.cap) n = B.b.cap;
-        if (n < 1) n = 1;
+    float *d_xpart = nullptr, *d_stage = nullptr;   // deterministic channels backward: view 0's extra slots, the shared rows' staging
+    size_t d_stage_bytes = 0;
+    int64_t n = list_pairs >= 0 ? list_pairs : B.b.cap;
+    if (n > B.b.cap) n = B.b.cap;
+    if (n < 1) n = 1;
+    if (det && x) {
+        const int nx = x->X.nx;
+        const size_t need = gsr_backward_det_channels_bytes(V, p->P, p->W, p->H, n, nx, x->layout);
+        if (!det->scratch || det->bytes < need)
+            return fail(GSR_ERR_CAPACITY, "[gsr] backward_channels_det: scratch block too small (%zu < %zu = "
+                        "gsr_backward_det_channels_bytes(%d, %d, %d, %d, %lld, %d, %d): the forward's lists hold up to %lld pairs per view)",
+                        det->bytes, need, V, p->P, p->W, p->H, (long long)n, nx, x->layout, (long long)n);
+        const DetXView DX = det_x_view(align256(det->scratch), T, n, nx);
+        D = DX.d;
+        d_xpart = DX.xpart;
+        d_stride = det_x_view_bytes(p->W, p->H, n, nx);
+        d_stage = reinterpret_cast<float*>(reinterpret_cast<char*>(align256(det->scratch)) + (size_t)V * d_stride);
+        d_stage_bytes = (size_t)V * (size_t)p->P * (size_t)det_x_shared_channels(nx, x->layout) * sizeof(float);
+    } else if (det) {
         const size_t need = gsr_backward_det_bytes(V, p->P, p->W, p->H, n);
         if (!det->scratch || det->bytes < need)
             return fail(GSR_ERR_CAPACITY, "[gsr] backward_det: scratch block too small (%zu < %zu = gsr_backward_det_bytes(%d, %d, %d, %d, %lld): "
@@ -669,18 +712,15 @@ static int backward_impl(const gsr_params* p, int V, const int* radii, const voi
         D = det_view(align256(det->scratch), T, n);
         d_stride = det_view_bytes(p->W, p->H, n);
     }
-    if (x) {
-        const int nx = x->X.nx;
-        x->X.state = xstate_view(align256(const_cast<void*>(x->state)), p->W, p->H, B.b.cap, nx);
-        x->X.state_stride = xstate_view_bytes(p->W, p->H, B.b.cap, nx);
-        if (x->state_bytes < (size_t)V * x->X.state_stride + 256)
-            return fail(GSR_ERR_CAPACITY, "[gsr] extra-state block too small for this binning arena");
-    }
     {
         ProfScope ps("bwd_items", L.stream);
         // dL/d extra values are accumulated with atomics, views that share an array into the same rows: clear the output first
+        // (deterministic: the ordered reduction writes the rows of the Gaussians it reaches with plain stores; the others stay zero,
+        // in the caller's per-view rows and in the staging of the shared ones)
         const size_t n_out = !x ? 0 : (size_t)p->P * (x->layout == 0 ? x->X.nx : x->layout == 1 ? V * x->X.nx : (1 + V) * 4);
         if (x && hipMemsetAsync(x->XG.grad, 0, n_out * sizeof(float), L.stream) != hipSuccess)
+            return fail(GSR_ERR_HIP, "[gsr] memset failed: %s", hipGetErrorString(hipGetLastError()));
+        if (d_stage_bytes != 0 && hipMemsetAsync(d_stage, 0, d_stage_bytes, L.stream) != hipSuccess)
             return fail(GSR_ERR_HIP, "[gsr] memset failed: %s", hipGetErrorString(hipGetLastError()));
         if (int e = launch_bwd_items(L, B, T, p->P)) return e;
     }
@@ -698,12 +738,23 @@ static int backward_impl(const gsr_params* p, int V, const int* radii, const voi
     {
         ProfScope ps("render_backward", L.stream);
         const RenderBwdDet d{D.part, D.flags, D.slot_base, d_stride, (uint32_t)D.cap};
-        if (int e = launch_render_backward(L, *p, B, B.b.val[res], G.dL_dpix, x ? &x->X : nullptr, x ? &x->XG : nullptr, det ? &d : nullptr))
+        // (storing channels kernels: the extras' sums go to the scratch block's slots, not to the caller's output)
+        const ExtraGrads xg_slots{x ? x->XG.dL_dextra : nullptr, d_xpart, nullptr};
+        if (int e = launch_render_backward(L, *p, B, B.b.val[res], G.dL_dpix, x ? &x->X : nullptr, !x ? nullptr : det ? &xg_slots : &x->XG,
+                                           det ? &d : nullptr))
             return e;
     }
     if (det) {
         ProfScope ps("det_reduce", L.stream);
         if (int e = launch_det_reduce(L, B, D, d_stride, dres)) return e;
+    }
+    if (det && x) {
+        ProfScope ps("det_reduce_extra", L.stream);
+        if (int e = launch_det_reduce_extra(L, B, D, d_xpart, d_stride, dres, p->P, x->X.nx, x->layout, x->XG, d_stage)) return e;
+    }
+    if (d_stage_bytes != 0) {
+        ProfScope ps("det_viewsum", L.stream);
+        if (int e = launch_det_viewsum(L, B, p->P, x->X.nx, x->layout, x->XG, d_stage)) return e;
     }
     {
         ProfScope ps("preprocess_backward", L.stream);
@@ -733,6 +784,20 @@ int gsr_backward_batch_det(const gsr_params* p, int V, const int* radii, const v
     return backward_impl(p, V, radii, geom, geom_bytes, binning, binning_bytes, image, image_bytes, G, &det, nullptr, stream);
 }
 
+// the two channels entries: det == NULL is the atomic one
+static int backward_channels(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
+                             size_t binning_bytes, const void* image, size_t image_bytes, const BwdGrads& G, int nx, int extra_per_view,
+                             const float* extra, const float* extra_view_scale, const float* bg_extra, const void* extra_state,
+                             size_t extra_state_bytes, const float* dL_dextra, float* dL_dextra_values, const BwdDet* det,
+                             gsr_stream_t stream)
+{
+    BwdExtra x{{}, {}, extra_per_view, extra_state, extra_state_bytes};
+    if (int e = extra_channels(p, nx, extra_per_view, extra, extra_view_scale, bg_extra, dL_dextra_values, x.X)) return e;
+    if (!dL_dextra || !extra_state) return fail(GSR_ERR_INVALID, "[gsr] dL_dextra / extra_state is NULL");
+    x.XG = ExtraGrads{dL_dextra, dL_dextra_values, extra_per_view == 2 ? dL_dextra_values + (size_t)p->P * 4 : nullptr};
+    return backward_impl(p, V, radii, geom, geom_bytes, binning, binning_bytes, image, image_bytes, G, det, &x, stream);
+}
+
 int gsr_backward_batch_channels(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
                                 size_t binning_bytes, const void* image, size_t image_bytes, const float* dL_dpix, float* dL_dmean2D,
                                 float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
@@ -740,12 +805,23 @@ int gsr_backward_batch_channels(const gsr_params* p, int V, const int* radii, co
                                 const float* extra_view_scale, const float* bg_extra, const void* extra_state, size_t extra_state_bytes,
                                 const float* dL_dextra, float* dL_dextra_values, gsr_stream_t stream)
 {
-    BwdExtra x{{}, {}, extra_per_view, extra_state, extra_state_bytes};
-    if (int e = extra_channels(p, nx, extra_per_view, extra, extra_view_scale, bg_extra, dL_dextra_values, x.X)) return e;
-    if (!dL_dextra || !extra_state) return fail(GSR_ERR_INVALID, "[gsr] dL_dextra / extra_state is NULL");
-    x.XG = ExtraGrads{dL_dextra, dL_dextra_values, extra_per_view == 2 ? dL_dextra_values + (size_t)p->P * 4 : nullptr};
     const BwdGrads G{dL_dpix, dL_dmean2D, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot};
-    return backward_impl(p, V, radii, geom, geom_bytes, binning, binning_bytes, image, image_bytes, G, nullptr, &x, stream);
+    return backward_channels(p, V, radii, geom, geom_bytes, binning, binning_bytes, image, image_bytes, G, nx, extra_per_view, extra,
+                             extra_view_scale, bg_extra, extra_state, extra_state_bytes, dL_dextra, dL_dextra_values, nullptr, stream);
+}
+
+int gsr_backward_batch_channels_det(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
+                                    size_t binning_bytes, const void* image, size_t image_bytes, const float* dL_dpix, float* dL_dmean2D,
+                                    float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                                    float* dL_dscale, float* dL_drot, int nx, int extra_per_view, const float* extra,
+                                    const float* extra_view_scale, const float* bg_extra, const void* extra_state,
+                                    size_t extra_state_bytes, const float* dL_dextra, float* dL_dextra_values, void* det_scratch,
+                                    size_t det_scratch_bytes, gsr_stream_t stream)
+{
+    const BwdGrads G{dL_dpix, dL_dmean2D, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot};
+    const BwdDet det{det_scratch, det_scratch_bytes};
+    return backward_channels(p, V, radii, geom, geom_bytes, binning, binning_bytes, image, image_bytes, G, nx, extra_per_view, extra,
+                             extra_view_scale, bg_extra, extra_state, extra_state_bytes, dL_dextra, dL_dextra_values, &det, stream);
 }
 
 int gsr_backward(const gsr_params* p, const int* radii, int64_t R, const void* geom, size_t geom_bytes, const void* binning,
@@ -887,6 +963,8 @@ int gsr_selftest(gsr_stream_t stream)
     if (rm != 0) return fail(GSR_ERR_HIP, "[gsr] selftest: matrix-core pixel contraction wrong at check %d", rm);
     const int rd = selftest_det_reduce(s);
     if (rd != 0) return fail(GSR_ERR_HIP, "[gsr] selftest: ordered reduction of the deterministic backward differs from the host sum at check %d", rd);
+    const int rx = selftest_det_reduce_extra(s);
+    if (rx != 0) return fail(GSR_ERR_HIP, "[gsr] selftest: ordered reduction of the extra channels differs from the host sum at check %d", rx);
 
     const int64_t n = 100003;
     std::vector<uint32_t> hk(n), hv(n), order(n);

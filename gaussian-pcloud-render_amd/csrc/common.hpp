@@ -322,6 +322,27 @@ inline DetView det_view(void* base, int T, int64_t cap)
     d.bytes = (size_t)(cur - reinterpret_cast<char*>(base));
     return d;
 }
+// The deterministic CHANNELS backward (gsr_backward_batch_channels_det) carves the same view block and, behind it, the extras' slots:
+//   xpart  [cap][4][nx]              dL/d extra of (consumed position, quadrant): nx floats (32 or 64 B per quadrant), written as one
+//                                    16-B store per quad of channels; the flag byte of `flags` covers both slot arrays
+// Behind the V view blocks lies the staging of the rows the views share (extra_per_view 0: [V][P][nx]; 2: [V][P][4]; 1: nothing): the
+// per-view sums, float32, which k_det_viewsum adds for v = 0 .. V - 1.
+struct DetXView {
+    DetView d;
+    float* xpart;
+    size_t bytes;
+};
+inline DetXView det_x_view(void* base, int T, int64_t cap, int nx)
+{
+    DetXView x;
+    x.d = det_view(base, T, cap);
+    char* cur = reinterpret_cast<char*>(base) + x.d.bytes;
+    carve(cur, x.xpart, (size_t)x.d.cap * 4 * (size_t)nx);
+    x.bytes = (size_t)(cur - reinterpret_cast<char*>(base));
+    return x;
+}
+// floats per Gaussian and view of the shared rows' staging
+inline int det_x_shared_channels(int nx, int extra_per_view) { return extra_per_view == 0 ? nx : extra_per_view == 2 ? 4 : 0; }
 // what k_render_backward's storing instantiations (render_bwd.hip) need of it: view 0's arrays and the stride to the next view's
 struct RenderBwdDet {
     float* part;
@@ -426,7 +447,8 @@ struct ExtraGrads {
 };
 int launch_render_forward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, float* out_color,
                           bool with_ckpt, const ExtraChannels* X = nullptr);
-// D != NULL (colour backward only): the storing instantiations -- partial sums go to D's slots instead of into the gradient records
+// D != NULL: the storing instantiations -- partial sums go to D's slots instead of into the gradient records; with extra channels
+// XG->grad is then view 0's extra slots (DetXView::xpart, D->stride bytes per view) and XG->grad_hi is not used
 int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, const float* dL_dpix,
                            const ExtraChannels* X = nullptr, const ExtraGrads* XG = nullptr, const RenderBwdDet* D = nullptr);
 int backward_subquadrant_moments(int set);   // render_bwd.hip: set >= 0 stores; 1 = moments about the sub-quadrant centres
@@ -438,6 +460,13 @@ int launch_det_prepare(const Launch& L, const Batch& B, const DetView& D, size_t
 int launch_det_sort(const Launch& L, const Batch& B, const DetView& D, size_t d_stride, int P, int* result_buffer);
 int launch_det_reduce(const Launch& L, const Batch& B, const DetView& D, size_t d_stride, int sorted_buffer);
 int selftest_det_reduce(hipStream_t stream);   // the ordered reduction against a host sum in the same order, bit for bit
+// the extras' ordered reduction: per view into the caller's per-view rows (XG.grad / grad_hi, layout extra_per_view) or, rows the
+// views share, into `stage` ([V][P][det_x_shared_channels], cleared by the caller); launch_det_viewsum then adds the staged rows
+// of the views, v = 0 .. V - 1, into XG.grad (nothing to do for extra_per_view = 1)
+int launch_det_reduce_extra(const Launch& L, const Batch& B, const DetView& D, const float* xpart, size_t d_stride, int sorted_buffer,
+                            int P, int nx, int extra_per_view, const ExtraGrads& XG, float* stage);
+int launch_det_viewsum(const Launch& L, const Batch& B, int P, int nx, int extra_per_view, const ExtraGrads& XG, const float* stage);
+int selftest_det_reduce_extra(hipStream_t stream);   // both kernels against host sums in the same order, bit for bit
 #ifdef GSR_STATS
 int debug_bwd_stats(unsigned long long* out8, int reset);   // instrumentation build only
 int debug_dup_times(unsigned long long* out8, int reset);

@@ -308,7 +308,7 @@ struct RenderBwdX {
     const float* xaccum;
     size_t x_stride;
     const float* dL_dextra;    // [V][NX][H][W]
-    float* grad;               // layout of `extra`
+    float* grad;               // layout of `extra` (storing kernels: view 0's extra slots, RenderBwdDet::stride bytes per view)
     float* grad_hi;            // layout of `extra_hi`
 };
 
@@ -340,17 +340,26 @@ __device__ __forceinline__ RenderBwdX bwd_x(const RenderBwdDet&) { return Render
 __device__ __forceinline__ RenderBwdDet bwd_det() { return RenderBwdDet{}; }
 __device__ __forceinline__ RenderBwdDet bwd_det(const RenderBwdX&) { return RenderBwdDet{}; }
 __device__ __forceinline__ RenderBwdDet bwd_det(const RenderBwdDet& d) { return d; }
+__device__ __forceinline__ RenderBwdX bwd_x(const RenderBwdX& x, const RenderBwdDet&) { return x; }
+__device__ __forceinline__ RenderBwdDet bwd_det(const RenderBwdX&, const RenderBwdDet& d) { return d; }
 // (the colour kernels take no RenderBwdX argument at all -- XS is empty -- so their kernel arguments, and with them the offsets of the
 // implicit ones, are what they were before the channels backward existed: the same machine code)
 // (the storing kernels carry the slot addressing on top of the colour kernel's 96 registers: four waves per SIMD instead of spills)
+// The STORING CHANNELS kernels, k_render_backward<MODE, 4 / 8, RenderBwdX, RenderBwdDet>: both switches at once.  The nine sums (which
+// carry the extras' share of d) leave through the same storing flush; the second contraction's f32x4 -- four channels of one batch
+// entry -- goes to the entry's extra slot xpart[(position * 4 + quadrant) * NX + 4 * channel quad] with ONE 16-B store, zeros
+// included, under exactly the condition the colour flush marks the (position, quadrant) under: a marked slot is whole in both arrays.
+// RenderBwdX::grad is view 0's xpart there (RenderBwdDet::stride bytes per view); grad_hi is not used.
 template <typename... XS> constexpr bool bwd_is_det = (std::is_same<XS, RenderBwdDet>::value || ...);
+// (the storing channels kernels: with four channels the slot addressing fits the channels kernel's three waves per SIMD; with eight
+// it spilled inside the flush there, so those three instantiations take two waves per SIMD and stay free of scratch)
+template <int NX, typename... XS> constexpr int bwd_waves = NX > 0 ? (NX > 4 && bwd_is_det<XS...> ? 2 : 3) : bwd_is_det<XS...> ? 4 : 5;
 template <int MODE, int NX, typename... XS>
-__attribute__((amdgpu_waves_per_eu(NX > 0 ? 3 : bwd_is_det<XS...> ? 4 : 5, NX > 0 ? 3 : bwd_is_det<XS...> ? 4 : 5)))
+__attribute__((amdgpu_waves_per_eu(bwd_waves<NX, XS...>, bwd_waves<NX, XS...>)))
 __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... xs)
 {
     const RenderBwdX x = bwd_x(xs...);
     constexpr bool DET = bwd_is_det<XS...>;
-    static_assert(!DET || NX == 0, "the storing flush exists for the colour backward only");
     RenderBwdDet det{};
     if constexpr (DET) det = bwd_det(xs...);
     constexpr bool SUBQ = MODE == 1;
@@ -375,8 +384,8 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
     const uint32_t x_nx = x_split ? 4u : (uint32_t)NX;
     const float* const x_lo = NX > 0 ? x.extra + (size_t)view * x.extra_vstride : nullptr;
     const float* const x_hi = NX > 0 ? (x_split ? x.extra_hi + (size_t)view * x.extra_hi_vstride : x_lo + 4) : nullptr;
-    float* const xg_lo = NX > 0 ? x.grad + (size_t)view * x.extra_vstride : nullptr;
-    float* const xg_hi = NX > 0 ? (x_split ? x.grad_hi + (size_t)view * x.extra_hi_vstride : xg_lo + 4) : nullptr;
+    float* const xg_lo = NX > 0 && !DET ? x.grad + (size_t)view * x.extra_vstride : nullptr;
+    float* const xg_hi = NX > 0 && !DET ? (x_split ? x.grad_hi + (size_t)view * x.extra_hi_vstride : xg_lo + 4) : nullptr;
     // storing flush: this view's slots, and which words of a slot the lanes WITHOUT a value of entries 0..3 (A) / 4..7 (B) fill
     // with zeros, so that a slot leaves the wave as one whole 64-B line (28 idle lanes = 4 entries x the 7 unused words 9..15)
     float* det_part = nullptr;
@@ -389,6 +398,8 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
         det_base = at_view(det.slot_base, det.stride, view);
         det_pad = (threadIdx.x >> 4) < 3u ? 9u + 2u * (threadIdx.x >> 4) + ((threadIdx.x >> 2) & 1u) : 15u;
     }
+    float* det_xpart = nullptr;   // storing channels flush: this view's extra slots
+    if constexpr (DET && NX > 0) det_xpart = at_view(x.grad, det.stride, view);
     const uint32_t n_items = at_view(a.item_count, a.iv_stride, view)[0];
     // From here on this view's gradient records hold sums of THIS backward: a later backward on the same arenas has to clear
     // them first (k_bwd_items reads the flag; it has finished: stream order).  Raised before anything is accumulated, so a
@@ -860,6 +871,12 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
             if constexpr (NX > 0) {
                 // dL/d extra: D[i][j] = sum_p xd_i(p) u_j(p); lane (g, column j >= 8) holds channels 4 g .. 4 g + 3 of batch entry j - 8
                 const f32x4 accx = mm_contract(mrow, amx, lane, hit_blocks);
+                if constexpr (DET) {
+                    const uint32_t pos = mm_gb ? posB : posA;
+                    const size_t c = (size_t)det_lo + pos;
+                    if (mm_j >= 8u && mm_g < (uint32_t)(NX / 4) && (mm_gb == 0u || nb == 2u) && pos < det_n && c < (size_t)det.cap)
+                        *reinterpret_cast<f32x4*>(det_xpart + (c * 4u + q) * (size_t)NX + 4u * mm_g) = accx;
+                } else
                 if (mm_j >= 8u && mm_g < (uint32_t)(NX / 4) && (mm_gb == 0u || nb == 2u)) {
                     const uint32_t id = mm_gb ? idB : idA;
                     float* dst = (mm_g == 0u ? xg_lo : xg_hi) + (size_t)id * x_nx;
@@ -976,6 +993,11 @@ int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B,
         x.extra_scale = X->view_scale; x.bg_extra = X->bg;
         x.xckpt = X->state.ckpt; x.xaccum = X->state.accum; x.x_stride = X->state_stride;
         x.dL_dextra = XG->dL_dextra; x.grad = XG->grad; x.grad_hi = XG->grad_hi;
+        if (D != nullptr) {
+            if (X->nx == 4) launch_bwd_kernel<4>(grid, L.stream, a, x, *D);
+            else launch_bwd_kernel<8>(grid, L.stream, a, x, *D);
+            return check_launch(L, "render_backward_channels_det");
+        }
         if (X->nx == 4) launch_bwd_kernel<4>(grid, L.stream, a, x);
         else launch_bwd_kernel<8>(grid, L.stream, a, x);
         return check_launch(L, "render_backward_channels");

@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from . import _native as _C
 from ._native import get_deterministic, set_deterministic  # noqa: F401  (the deterministic-backward switch)
+from ._native import get_deterministic_channels, set_deterministic_channels  # noqa: F401  (the deterministic channels backward's own switch)
 from ._native import get_render_math, set_render_math  # noqa: F401  (arithmetic mode of the inference forwards)
 
 
@@ -348,6 +349,9 @@ class _RasterizeGaussiansViewsChannels(torch.autograd.Function):
         ctx.opacity_shape = tuple(opacities.shape)
         ctx.nx_user = nx_user
         ctx.xstate = _C.extra_state(geomBuffer)
+        # the deterministic channels backward sizes its scratch block by the lists' extent (same host thread as the forward call)
+        ctx.det_channels = get_deterministic_channels()
+        ctx.det_pairs = _C.last_list_pairs(len(settings_list)) if ctx.det_channels and need_backward and means3D.shape[0] != 0 else None
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
                               imgBuffer, view, proj, cam, extra, extra_hi, bg_extra, extra_view_scale)
         ctx.mark_non_differentiable(radii)
@@ -369,7 +373,7 @@ class _RasterizeGaussiansViewsChannels(torch.autograd.Function):
         g = _C.rasterize_gaussians_backward_channels_batch(
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj, rs.tanfovx,
             rs.tanfovy, grad_out_color, sh, rs.sh_degree, cam, geomBuffer, binningBuffer, imgBuffer, rs.debug,
-            (values, xs, bg_extra), grad_out_extra, state=ctx.xstate)
+            (values, xs, bg_extra), grad_out_extra, state=ctx.xstate, deterministic=ctx.det_channels, pairs=ctx.det_pairs)
         g_lo, g_hi = g[8] if split else (g[8], None)
         return _input_grads(g[:8], ctx, sh, colors_precomp, scales, rotations, cov3Ds_precomp, g_lo, g_hi, None, None, None, None)
 
@@ -385,12 +389,17 @@ def rasterize_views_channels(means3D, means2D, opacities, settings_list, extra, 
     `extra` as to every input rasterize_views differentiates; bg_extra and extra_view_scale get none (like the background)."""
     if len(settings_list) == 0:
         raise Exception("rasterize_views_channels: empty settings list")
-    # the channels backward adds dL/d extra with float atomics of its own and has no deterministic counterpart (include/gsr.h)
+    # the atomic channels backward adds dL/d extra with float atomics of its own; the deterministic one (include/gsr.h
+    # gsr_backward_batch_channels_det) is behind a switch of its own, set_deterministic_channels: while that is off, the colour
+    # backward's switches refuse this call as they always did
     _why = ("rasterize_views_channels has no deterministic backward (the extra channels' gradients are accumulated with float "
-            "atomics); render the channels as colours through rasterize_views, or switch the deterministic path off")
-    if get_deterministic() is True:
+            "atomics) unless diff_gaussian_rasterization.set_deterministic_channels(True) selects the deterministic channels "
+            "backward; or render the channels as colours through rasterize_views, or switch the deterministic path off")
+    if get_deterministic_channels():
+        pass
+    elif get_deterministic() is True:
         raise RuntimeError(_why + ": diff_gaussian_rasterization.set_deterministic(False / None)")
-    if get_deterministic() is None and torch.are_deterministic_algorithms_enabled():
+    elif get_deterministic() is None and torch.are_deterministic_algorithms_enabled():
         if torch.is_deterministic_algorithms_warn_only_enabled():
             import warnings
             warnings.warn(_why, UserWarning)

@@ -51,6 +51,7 @@ _DECL = {
     "gsr_binning_bytes": (_size, [_i64]),
     "gsr_extra_state_bytes": (_size, [_int, _int, _i64, _int]),
     "gsr_backward_det_bytes": (_size, [_int, _int, _int, _int, _i64]),
+    "gsr_backward_det_channels_bytes": (_size, [_int, _int, _int, _int, _i64, _int, _int]),
     "gsr_forward_batch": (_int, _FWD + [_fp]),
     "gsr_forward_batch_channels": (_int, _FWD_X + [_fp]),
     "gsr_forward_batch_channels_train": (_int, _FWD_X + [_fp, _size, _fp]),
@@ -60,6 +61,7 @@ _DECL = {
     "gsr_backward_batch": (_int, _BWD + [_fp]),
     "gsr_backward_batch_det": (_int, _BWD + [_fp, _size, _fp]),
     "gsr_backward_batch_channels": (_int, _BWD + [_int, _int, _fp, _fp, _fp, _fp, _size, _fp, _fp, _fp]),
+    "gsr_backward_batch_channels_det": (_int, _BWD + [_int, _int, _fp, _fp, _fp, _fp, _size, _fp, _fp, _fp, _size, _fp]),
     "gsr_backward": (_int, [_pp, _fp, _i64] + _ARENAS + [_fp] * 9 + [_fp]),
     "gsr_mark_visible": (_int, [_int, _fp, _fp, _fp, _fp, _fp]),
     "gsr_query": (_int, [_pp, _int, _fp, _fp, _size, _fp, _i64, _fp, _size, _fp]),
@@ -205,7 +207,8 @@ def set_reference_lists(on):
 # bit-identical gradients from call to call and from process to process for the same inputs and call shape (not across different
 # numbers of views per call), for a scratch block per backward and the time of a sort and an ordered reduction.
 _DETERMINISTIC = [{"0": False, "1": True}.get(os.environ.get("GSR_DETERMINISTIC", "").strip())]
-CALLS = dict(backward=0, backward_det=0)     # colour backwards issued through each entry (tests)
+# backwards issued through each entry (tests): the colour ones, and the deterministic channels backward
+CALLS = dict(backward=0, backward_det=0, backward_channels_det=0)
 
 
 def set_deterministic(flag):
@@ -223,6 +226,23 @@ def deterministic_active():
     return bool(torch.are_deterministic_algorithms_enabled()) if f is None else f
 
 
+# The deterministic CHANNELS backward (include/gsr.h gsr_backward_batch_channels_det) has a switch of its own: set_deterministic and
+# torch's switch keep refusing rasterize_views_channels, as they always did.  With this switch on, rasterize_views_channels (and
+# pcrender.raster_passes.train_passes through it) runs whatever the other switch says, and its backward -- colour and extra
+# channels through one storing kernel -- is bit-identical from call to call.  GSR_DETERMINISTIC_CHANNELS=1 sets the initial value.
+_DETERMINISTIC_CHANNELS = [os.environ.get("GSR_DETERMINISTIC_CHANNELS", "").strip() == "1"]
+
+
+def set_deterministic_channels(flag):
+    """True: rasterize_views_channels differentiates through the deterministic channels backward; False (default): the atomic one."""
+    _DETERMINISTIC_CHANNELS[0] = bool(flag)
+
+
+def get_deterministic_channels():
+    """The value set_deterministic_channels was last given (initially GSR_DETERMINISTIC_CHANNELS=1 in the environment, else False)."""
+    return _DETERMINISTIC_CHANNELS[0]
+
+
 def last_list_pairs(V):
     """largest per-view pair count of the lists of the calling thread's last forward (gsr_last_list_pairs)"""
     pairs = (C.c_int64 * V)()
@@ -236,6 +256,14 @@ def det_scratch(V, P, W, H, pairs, binning_bytes, device):
     if pairs is None:
         pairs = max(1, int(binning_bytes) // max(1, V) // 16)
     return torch.empty((int(lib.gsr_backward_det_bytes(V, P, W, H, int(pairs))),), dtype=torch.uint8, device=device)
+
+
+def det_channels_scratch(V, P, W, H, pairs, binning_bytes, nx, extra_per_view, device):
+    """the scratch block of one deterministic channels backward (gsr_backward_det_channels_bytes); pairs None: as in det_scratch"""
+    if pairs is None:
+        pairs = max(1, int(binning_bytes) // max(1, V) // 16)
+    return torch.empty((int(lib.gsr_backward_det_channels_bytes(V, P, W, H, int(pairs), nx, extra_per_view)),), dtype=torch.uint8,
+                       device=device)
 
 
 # ---- binning-arena capacity -----------------------------------------------------------------------------------------
@@ -781,20 +809,24 @@ def extra_state(geomBuffer):
 
 def rasterize_gaussians_backward_channels_batch(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                                 viewmatrices, projmatrices, tan_fovx, tan_fovy, dL_dout_color, sh, degree, camposs,
-                                                geomBuffer, binningBuffer, imageBuffer, debug, extra, dL_dout_extra, state=None):
+                                                geomBuffer, binningBuffer, imageBuffer, debug, extra, dL_dout_extra, state=None,
+                                                deterministic=False, pairs=None, _alloc=None):
     """Backward of rasterize_gaussians_batch(..., extra=(values, view_scale, bg), need_backward=True) (C ABI
     gsr_backward_batch_channels): `extra` is the forward's triple, dL_dout_extra [V,nx,H,W].  Returns the 8-tuple of
     rasterize_gaussians_backward_batch + dL/d values in the layout of the values ([P,nx], [V,P,nx], or the pair ([P,4], [V,P,4])).
-    state: the forward's extra_state(geomBuffer) (default: looked up on geomBuffer)."""
+    state: the forward's extra_state(geomBuffer) (default: looked up on geomBuffer).
+    deterministic: through gsr_backward_batch_channels_det (every output bit-identical from call to call), with a scratch block for
+    lists of `pairs` pairs per view (None: bounded from the binning arena's size).  _alloc: allocator of the outputs, as in
+    rasterize_gaussians_backward_batch."""
     device = means3D.device
     _require_hip(device)
     P = means3D.shape[0]
     V, H, W = int(dL_dout_color.shape[0]), int(dL_dout_color.shape[2]), int(dL_dout_color.shape[3])
     M = int(sh.shape[1]) if sh.numel() != 0 and sh.shape[0] != 0 else 0
     nx, x_per_view, xv, xs, xb = _extra_layout(extra, P, V, device)
-    grads = _grad_tensors(P, M, device, scales.numel() != 0)
+    grads = _grad_tensors(P, M, device, scales.numel() != 0, _alloc)
     n_out = P * 4 * (1 + V) if x_per_view == 2 else P * nx * (V if x_per_view else 1)
-    gx = (torch.empty if P != 0 else torch.zeros)((n_out,), dtype=_F32, device=device)
+    gx = ((_alloc or torch.empty) if P != 0 else torch.zeros)((n_out,), dtype=_F32, device=device)
     if P != 0:
         st = state if state is not None else extra_state(geomBuffer)
         if st is None:
@@ -804,10 +836,15 @@ def rasterize_gaussians_backward_channels_batch(background, means3D, radii, colo
                                                  viewmatrices, projmatrices, tan_fovx, tan_fovy, dL_dout_color, sh, degree, camposs, debug)
             xv, xs, xb = _extra_f32(xv, xs, xb, device)
             dx = _f32c(dL_dout_extra, device, "dL_dout_extra")
-            _check(lib.gsr_backward_batch_channels(
-                *_bwd_head(p, V, radii_c, _arena_args(geomBuffer, binningBuffer, imageBuffer), dpix, grads), nx, x_per_view,
-                xv.data_ptr(), _ptr(xs), xb.data_ptr(), st[0].data_ptr(), st[0].numel(), dx.data_ptr(), gx.data_ptr(),
-                _stream_handle(device)))
+            arenas = _arena_args(geomBuffer, binningBuffer, imageBuffer)
+            args = _bwd_head(p, V, radii_c, arenas, dpix, grads) + (
+                nx, x_per_view, xv.data_ptr(), _ptr(xs), xb.data_ptr(), st[0].data_ptr(), st[0].numel(), dx.data_ptr(), gx.data_ptr())
+            if deterministic:
+                CALLS["backward_channels_det"] += 1
+                scratch = det_channels_scratch(V, P, W, H, pairs, arenas[3], nx, x_per_view, device)
+                _check(lib.gsr_backward_batch_channels_det(*args, scratch.data_ptr(), scratch.numel(), _stream_handle(device)))
+            else:
+                _check(lib.gsr_backward_batch_channels(*args, _stream_handle(device)))
             del keep
     if x_per_view == 2:
         gx = (gx[:P * 4].reshape(P, 4), gx[P * 4:].reshape(V, P, 4))

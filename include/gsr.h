@@ -220,8 +220,7 @@ int gsr_backward_batch(const gsr_params* p, int V, const int* radii, const void*
  * and view (a 64-B slot per quadrant, the sort's ping-pong buffers and a flag word), i.e. 2.0 GB per view for lists of 7.3 M pairs
  * and 24 GB for 12 such views, of which only the entries the forward consumed (about 1.1 M per view there) are ever touched.
  *
- * gsr_backward_batch_channels has no deterministic counterpart (dL/d extra is accumulated with float atomics of its own): a
- * channels backward stays non-deterministic. */
+ * The channels backward has a deterministic counterpart of its own, gsr_backward_batch_channels_det below. */
 size_t gsr_backward_det_bytes(int V, int P, int W, int H, int64_t pairs);
 int gsr_backward_batch_det(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
                            size_t binning_bytes, const void* image, size_t image_bytes, const float* dL_dpix, float* dL_dmean2D,
@@ -243,6 +242,37 @@ int gsr_backward_batch_channels(const gsr_params* p, int V, const int* radii, co
                                 float* dL_dscale, float* dL_drot, int nx, int extra_per_view, const float* extra,
                                 const float* extra_view_scale, const float* bg_extra, const void* extra_state, size_t extra_state_bytes,
                                 const float* dL_dextra, float* dL_dextra_values, gsr_stream_t stream);
+
+/* Deterministic channels backward (opt-in): gsr_backward_batch_channels's arguments, outputs and refusals -- checked in the same
+ * order with the same texts: the arena's record, the pointers, the extra-state size -- plus a caller-owned scratch block, checked
+ * last (GSR_ERR_CAPACITY with the needed size and the arguments of the size query in the message).  The contract is
+ * gsr_backward_batch_det's, for all outputs including dL_dextra_values: for the same inputs, the same call shape (V, image size, nx,
+ * extra_per_view, moments mode, reference_lists), the same library build and the same device model every output is BIT-IDENTICAL
+ * from call to call and from process to process; not promised across different V, builds or device models.  The values are those of
+ * gsr_backward_batch_channels up to the order of float additions.  One kernel stores the colour / geometry sums (which carry the
+ * extras' share) AND dL/d extra of every (list entry, 8 x 8 quadrant) into slots of their own; no float atomic is issued anywhere.
+ * Order of the additions, for the gradient records and for dL/d extra alike: per view and Gaussian, the entries of the Gaussian in
+ * the view's lists by tile, then by depth inside the tile, then the quadrants 0, 1, 2, 3 of the tile; quadrants the kernel did not
+ * evaluate are left out; the running sum is kept in float64 and rounded to float32 ONCE per view.  Rows of dL_dextra_values that
+ * belong to one view (extra_per_view = 1; channels 4..7 of extra_per_view = 2) are that rounded value.  Rows the views share
+ * (extra_per_view = 0; channels 0..3 of extra_per_view = 2) are the per-view float32 values added for view 0, 1, .. V - 1 in
+ * float64 and rounded to float32 once more.  Rows of Gaussians that no evaluated entry reached are exactly zero.  Valid after
+ * gsr_forward_batch_channels_train with need_backward = 1, any number of times over one forward (not after gsr_forward_recolor), in
+ * all three moments modes.  No device->host read-back; the library allocates nothing on the device.
+ *
+ * gsr_backward_det_channels_bytes(V, P, W, H, pairs, nx, extra_per_view) is the size of the scratch block, a pure host function;
+ * `pairs` as for gsr_backward_det_bytes.  It is gsr_backward_det_bytes(V, P, W, H, pairs) plus the extras' slots -- 16 nx bytes per
+ * pair and view (64 B for nx = 4, 128 B for nx = 8: about 340 / 404 bytes per pair and view in all) -- plus the staging of the shared
+ * rows, 4 V P nx bytes (extra_per_view = 0) or 16 V P bytes (extra_per_view = 2).  0 for arguments gsr_backward_det_bytes answers
+ * with 0 and for an nx / extra_per_view pair the channels forward refuses. */
+size_t gsr_backward_det_channels_bytes(int V, int P, int W, int H, int64_t pairs, int nx, int extra_per_view);
+int gsr_backward_batch_channels_det(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
+                                    size_t binning_bytes, const void* image, size_t image_bytes, const float* dL_dpix, float* dL_dmean2D,
+                                    float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                                    float* dL_dscale, float* dL_drot, int nx, int extra_per_view, const float* extra,
+                                    const float* extra_view_scale, const float* bg_extra, const void* extra_state,
+                                    size_t extra_state_bytes, const float* dL_dextra, float* dL_dextra_values, void* det_scratch,
+                                    size_t det_scratch_bytes, gsr_stream_t stream);
 
 /* One view, the reference's argument shape (num_rendered is not needed: the lists' extent lives in the arenas). */
 int gsr_backward(const gsr_params* p, const int* radii, int64_t num_rendered, const void* geom, size_t geom_bytes,
@@ -295,7 +325,7 @@ int gsr_clock_probe_launch(void* dst16, int iters, gsr_stream_t stream);
 int gsr_wall_clock_khz(void);
 
 /* Device self-test of internal primitives (the matrix-core pixel contraction of the render backward, the ordered reduction of the
- * deterministic backward against a host sum in the same order, stable radix sort vs std::stable_sort).
+ * deterministic backward and that of the extra channels against host sums in the same order, stable radix sort vs std::stable_sort).
  * Allocates its own small buffers; not part of the hot path.  0 = pass. */
 int gsr_selftest(gsr_stream_t stream);
 
