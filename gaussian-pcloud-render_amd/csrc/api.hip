@@ -550,39 +550,21 @@ int gsr_forward_recolor(const gsr_params* p, int V, int colors_per_view, void* g
     return GSR_OK;
 }
 
-// per-view bytes of the deterministic backward's scratch for lists of `pairs` pairs
-static size_t det_view_bytes(int W, int H, int64_t pairs)
+// total bytes of a deterministic backward's scratch block for lists of up to `pairs` pairs per view (nx = 0: the colour backward)
+static size_t det_bytes(int V, int P, int W, int H, int64_t pairs, int nx, int extra_per_view)
 {
-    const int T = ((W + TILE_X - 1) / TILE_X) * ((H + TILE_Y - 1) / TILE_Y);
-    return align_up(det_view(nullptr, T, pairs).bytes, 256);
-}
-
-size_t gsr_backward_det_bytes(int V, int P, int W, int H, int64_t pairs)
-{
-    (void)P;   // (the sort's key bits follow P, its work space does not)
     if (V < 1 || W <= 0 || H <= 0) return 0;
-    if (pairs > 0xFFFFFFFFll) pairs = 0xFFFFFFFFll;
-    return (size_t)V * det_view_bytes(W, H, pairs) + 256;
+    const int T = ((W + TILE_X - 1) / TILE_X) * ((H + TILE_Y - 1) / TILE_Y);
+    return det_scratch(nullptr, V, P, T, pairs, nx, extra_per_view).bytes;
 }
 
-// per-view bytes of the deterministic channels backward's scratch: the colour block, then the extras' slots
-static size_t det_x_view_bytes(int W, int H, int64_t pairs, int nx)
-{
-    const int T = ((W + TILE_X - 1) / TILE_X) * ((H + TILE_Y - 1) / TILE_Y);
-    return align_up(det_x_view(nullptr, T, pairs, nx).bytes, 256);
-}
-// bytes of the staging of the rows the views share, behind the V view blocks
-static size_t det_x_stage_bytes(int V, int P, int nx, int extra_per_view)
-{
-    return align_up((size_t)V * (size_t)(P > 0 ? P : 0) * (size_t)det_x_shared_channels(nx, extra_per_view) * sizeof(float), 256);
-}
+// (P does not enter: the sort's key bits follow P, its work space does not)
+size_t gsr_backward_det_bytes(int V, int P, int W, int H, int64_t pairs) { return det_bytes(V, P, W, H, pairs, 0, 0); }
 
 size_t gsr_backward_det_channels_bytes(int V, int P, int W, int H, int64_t pairs, int nx, int extra_per_view)
 {
-    if (V < 1 || W <= 0 || H <= 0) return 0;
     if ((nx != 4 && nx != 8) || extra_per_view < 0 || extra_per_view > 2 || (extra_per_view == 2 && nx != 8)) return 0;
-    if (pairs > 0xFFFFFFFFll) pairs = 0xFFFFFFFFll;
-    return (size_t)V * det_x_view_bytes(W, H, pairs, nx) + det_x_stage_bytes(V, P, nx, extra_per_view) + 256;
+    return det_bytes(V, P, W, H, pairs, nx, extra_per_view);
 }
 
 // ---- the backward: one sequence behind gsr_backward, gsr_backward_batch, gsr_backward_batch_det, gsr_backward_batch_channels and
@@ -683,34 +665,19 @@ static int backward_impl(const gsr_params* p, int V, const int* radii, const voi
     }
     // deterministic: one slot per (consumed list entry, quadrant) in the caller's scratch block.  The block has to hold the
     // forward's lists: their largest per-view pair count from the arena's record, or -- no record -- the binning arena's capacity
-    DetView D{};
-    size_t d_stride = 0;
-    float *d_xpart = nullptr, *d_stage = nullptr;   // deterministic channels backward: view 0's extra slots, the shared rows' staging
-    size_t d_stage_bytes = 0;
-    int64_t n = list_pairs >= 0 ? list_pairs : B.b.cap;
-    if (n > B.b.cap) n = B.b.cap;
-    if (n < 1) n = 1;
-    if (det && x) {
-        const int nx = x->X.nx;
-        const size_t need = gsr_backward_det_channels_bytes(V, p->P, p->W, p->H, n, nx, x->layout);
-        if (!det->scratch || det->bytes < need)
-            return fail(GSR_ERR_CAPACITY, "[gsr] backward_channels_det: scratch block too small (%zu < %zu = "
-                        "gsr_backward_det_channels_bytes(%d, %d, %d, %d, %lld, %d, %d): the forward's lists hold up to %lld pairs per view)",
-                        det->bytes, need, V, p->P, p->W, p->H, (long long)n, nx, x->layout, (long long)n);
-        const DetXView DX = det_x_view(align256(det->scratch), T, n, nx);
-        D = DX.d;
-        d_xpart = DX.xpart;
-        d_stride = det_x_view_bytes(p->W, p->H, n, nx);
-        d_stage = reinterpret_cast<float*>(reinterpret_cast<char*>(align256(det->scratch)) + (size_t)V * d_stride);
-        d_stage_bytes = (size_t)V * (size_t)p->P * (size_t)det_x_shared_channels(nx, x->layout) * sizeof(float);
-    } else if (det) {
-        const size_t need = gsr_backward_det_bytes(V, p->P, p->W, p->H, n);
-        if (!det->scratch || det->bytes < need)
-            return fail(GSR_ERR_CAPACITY, "[gsr] backward_det: scratch block too small (%zu < %zu = gsr_backward_det_bytes(%d, %d, %d, %d, %lld): "
-                        "the forward's lists hold up to %lld pairs per view)", det->bytes, need, V, p->P, p->W, p->H, (long long)n,
-                        (long long)n);
-        D = det_view(align256(det->scratch), T, n);
-        d_stride = det_view_bytes(p->W, p->H, n);
+    DetScratch S{};
+    if (det) {
+        int64_t n = list_pairs >= 0 ? list_pairs : B.b.cap;
+        if (n > B.b.cap) n = B.b.cap;
+        if (n < 1) n = 1;
+        S = det_scratch(align256(det->scratch), V, p->P, T, n, x ? x->X.nx : 0, x ? x->layout : 0);
+        if (!det->scratch || det->bytes < S.bytes)
+            return x ? fail(GSR_ERR_CAPACITY, "[gsr] backward_channels_det: scratch block too small (%zu < %zu = "
+                            "gsr_backward_det_channels_bytes(%d, %d, %d, %d, %lld, %d, %d): the forward's lists hold up to %lld pairs per "
+                            "view)", det->bytes, S.bytes, V, p->P, p->W, p->H, (long long)n, x->X.nx, x->layout, (long long)n)
+                     : fail(GSR_ERR_CAPACITY, "[gsr] backward_det: scratch block too small (%zu < %zu = gsr_backward_det_bytes(%d, %d, %d, "
+                            "%d, %lld): the forward's lists hold up to %lld pairs per view)", det->bytes, S.bytes, V, p->P, p->W, p->H,
+                            (long long)n, (long long)n);
     }
     {
         ProfScope ps("bwd_items", L.stream);
@@ -720,7 +687,7 @@ static int backward_impl(const gsr_params* p, int V, const int* radii, const voi
         const size_t n_out = !x ? 0 : (size_t)p->P * (x->layout == 0 ? x->X.nx : x->layout == 1 ? V * x->X.nx : (1 + V) * 4);
         if (x && hipMemsetAsync(x->XG.grad, 0, n_out * sizeof(float), L.stream) != hipSuccess)
             return fail(GSR_ERR_HIP, "[gsr] memset failed: %s", hipGetErrorString(hipGetLastError()));
-        if (d_stage_bytes != 0 && hipMemsetAsync(d_stage, 0, d_stage_bytes, L.stream) != hipSuccess)
+        if (S.stage && hipMemsetAsync(S.stage, 0, (size_t)V * S.n_stage * sizeof(float), L.stream) != hipSuccess)
             return fail(GSR_ERR_HIP, "[gsr] memset failed: %s", hipGetErrorString(hipGetLastError()));
         if (int e = launch_bwd_items(L, B, T, p->P)) return e;
     }
@@ -728,33 +695,33 @@ static int backward_impl(const gsr_params* p, int V, const int* radii, const voi
     if (det) {
         {
             ProfScope ps("det_prepare", L.stream);
-            if (int e = launch_det_prepare(L, B, D, d_stride, B.b.val[res], T)) return e;
+            if (int e = launch_det_prepare(L, B, S, B.b.val[res], T)) return e;
         }
         {
             ProfScope ps("det_sort", L.stream);
-            if (int e = launch_det_sort(L, B, D, d_stride, p->P, &dres)) return e;
+            if (int e = launch_det_sort(L, B, S, p->P, &dres)) return e;
         }
     }
     {
         ProfScope ps("render_backward", L.stream);
-        const RenderBwdDet d{D.part, D.flags, D.slot_base, d_stride, (uint32_t)D.cap};
+        const RenderBwdDet d{S.d.part, S.d.flags, S.d.slot_base, S.stride, (uint32_t)S.d.cap};
         // (storing channels kernels: the extras' sums go to the scratch block's slots, not to the caller's output)
-        const ExtraGrads xg_slots{x ? x->XG.dL_dextra : nullptr, d_xpart, nullptr};
+        const ExtraGrads xg_slots{x ? x->XG.dL_dextra : nullptr, S.xpart, nullptr};
         if (int e = launch_render_backward(L, *p, B, B.b.val[res], G.dL_dpix, x ? &x->X : nullptr, !x ? nullptr : det ? &xg_slots : &x->XG,
                                            det ? &d : nullptr))
             return e;
     }
     if (det) {
         ProfScope ps("det_reduce", L.stream);
-        if (int e = launch_det_reduce(L, B, D, d_stride, dres)) return e;
+        if (int e = launch_det_reduce(L, B, S, dres)) return e;
     }
     if (det && x) {
         ProfScope ps("det_reduce_extra", L.stream);
-        if (int e = launch_det_reduce_extra(L, B, D, d_xpart, d_stride, dres, p->P, x->X.nx, x->layout, x->XG, d_stage)) return e;
+        if (int e = launch_det_reduce_extra(L, B, S, dres, p->P, x->X.nx, x->layout, x->XG)) return e;
     }
-    if (d_stage_bytes != 0) {
+    if (S.stage) {
         ProfScope ps("det_viewsum", L.stream);
-        if (int e = launch_det_viewsum(L, B, p->P, x->X.nx, x->layout, x->XG, d_stage)) return e;
+        if (int e = launch_det_viewsum(L, B, S, x->XG)) return e;
     }
     {
         ProfScope ps("preprocess_backward", L.stream);
@@ -956,10 +923,9 @@ int gsr_query(const gsr_params* p, int what, const void* geom, const void* binni
 int gsr_selftest(gsr_stream_t stream)
 {
     hipStream_t s = (hipStream_t)stream;
-    float* d = nullptr;
-    if (hipMalloc(&d, 256 * sizeof(float)) != hipSuccess) return fail(GSR_ERR_HIP, "[gsr] selftest: hipMalloc failed");
-    const int rm = selftest_mm(s, d);
-    (void)hipFree(d);
+    const DevBuf<float> d(256);
+    if (!d.p) return fail(GSR_ERR_HIP, "[gsr] selftest: hipMalloc failed");
+    const int rm = selftest_mm(s, d.p);
     if (rm != 0) return fail(GSR_ERR_HIP, "[gsr] selftest: matrix-core pixel contraction wrong at check %d", rm);
     const int rd = selftest_det_reduce(s);
     if (rd != 0) return fail(GSR_ERR_HIP, "[gsr] selftest: ordered reduction of the deterministic backward differs from the host sum at check %d", rd);
@@ -976,26 +942,15 @@ int gsr_selftest(gsr_stream_t stream)
         order[i] = (uint32_t)i;
     }
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hk[a] < hk[b]; });
-    uint32_t *k0, *k1, *v0, *v1, *hist, *tot;
-    const size_t nb = (size_t)sort_hist_stride(n);
-    if (hipMalloc(&k0, n * 4) != hipSuccess || hipMalloc(&k1, n * 4) != hipSuccess || hipMalloc(&v0, n * 4) != hipSuccess ||
-        hipMalloc(&v1, n * 4) != hipSuccess || hipMalloc(&hist, RADIX * nb * 4) != hipSuccess || hipMalloc(&tot, RADIX * 4) != hipSuccess)
-        return fail(GSR_ERR_HIP, "[gsr] selftest: hipMalloc failed");
-    (void)hipMemcpyAsync(k0, hk.data(), n * 4, hipMemcpyHostToDevice, s);
-    uint32_t* key[2] = {k0, k1};
-    uint32_t* val[2] = {v0, v1};
+    const DevBuf<uint32_t> k0(hk, s), k1(n), v0(n), v1(n), hist(RADIX * (size_t)sort_hist_stride(n)), tot(RADIX);
+    if (!k0.p || !k1.p || !v0.p || !v1.p || !hist.p || !tot.p) return fail(GSR_ERR_HIP, "[gsr] selftest: hipMalloc failed");
     int res = 0;
     const Launch L{s, 1};
-    const SortJob job{{k0, k1}, {v0, v1}, hist, tot, 0, nullptr, 0, n, 1};
-    int rc = launch_radix_sort_pairs(L, job, /*iota_vals=*/true, 12, &res);
+    const SortJob job{{k0.p, k1.p}, {v0.p, v1.p}, hist.p, tot.p, 0, nullptr, 0, n, 1};
+    if (int rc = launch_radix_sort_pairs(L, job, /*iota_vals=*/true, 12, &res)) return rc;
     std::vector<uint32_t> gk(n), gv(n);
-    if (rc == 0) {
-        (void)hipMemcpyAsync(gk.data(), key[res], n * 4, hipMemcpyDeviceToHost, s);
-        (void)hipMemcpyAsync(gv.data(), val[res], n * 4, hipMemcpyDeviceToHost, s);
-        if (hipStreamSynchronize(s) != hipSuccess) rc = GSR_ERR_HIP;
-    }
-    (void)hipFree(k0); (void)hipFree(k1); (void)hipFree(v0); (void)hipFree(v1); (void)hipFree(hist); (void)hipFree(tot);
-    if (rc != 0) return rc;
+    if (!(res ? k1 : k0).download(gk.data(), s) || !(res ? v1 : v0).download(gv.data(), s) || hipStreamSynchronize(s) != hipSuccess)
+        return GSR_ERR_HIP;
     for (int64_t i = 0; i < n; i++)
         if (gv[i] != order[i] || gk[i] != hk[order[i]]) return fail(GSR_ERR_HIP, "[gsr] selftest: radix sort differs from std::stable_sort at %lld", (long long)i);
     return GSR_OK;

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include <type_traits>
+#include <vector>
 
 #include "../../include/gsr.h"
 
@@ -322,27 +323,35 @@ inline DetView det_view(void* base, int T, int64_t cap)
     d.bytes = (size_t)(cur - reinterpret_cast<char*>(base));
     return d;
 }
-// The deterministic CHANNELS backward (gsr_backward_batch_channels_det) carves the same view block and, behind it, the extras' slots:
+// The whole scratch block of a deterministic backward: V view blocks at `stride` bytes, then the staging of the rows the views share.
+// The colour backward (nx = 0) has det_view's arrays per view; the CHANNELS backward (gsr_backward_batch_channels_det) carves, behind
+// them in every view block, the extras' slots
 //   xpart  [cap][4][nx]              dL/d extra of (consumed position, quadrant): nx floats (32 or 64 B per quadrant), written as one
 //                                    16-B store per quad of channels; the flag byte of `flags` covers both slot arrays
-// Behind the V view blocks lies the staging of the rows the views share (extra_per_view 0: [V][P][nx]; 2: [V][P][4]; 1: nothing): the
-// per-view sums, float32, which k_det_viewsum adds for v = 0 .. V - 1.
-struct DetXView {
-    DetView d;
-    float* xpart;
-    size_t bytes;
+// and behind the V view blocks the staging (extra_per_view 0: [V][P][nx]; 2: [V][P][4]; 1: nothing): the per-view sums, float32,
+// which k_det_viewsum adds for v = 0 .. V - 1.
+struct DetScratch {
+    DetView d;        // view 0's arrays
+    float* xpart;     // view 0's extra slots, NULL for the colour backward
+    float* stage;     // [V][n_stage], NULL when the views share no rows
+    size_t stride;    // bytes from a view's block to the next view's
+    size_t n_stage;   // floats per view of the staging: P * (channels whose rows the views share)
+    size_t bytes;     // what the size queries return: the V blocks, the staging and 256 B for aligning the caller's pointer
 };
-inline DetXView det_x_view(void* base, int T, int64_t cap, int nx)
+// base: 256-B aligned, or NULL for the sizes alone (the pointers then mean nothing)
+inline DetScratch det_scratch(void* base, int V, int P, int T, int64_t pairs, int nx, int extra_per_view)
 {
-    DetXView x;
-    x.d = det_view(base, T, cap);
-    char* cur = reinterpret_cast<char*>(base) + x.d.bytes;
-    carve(cur, x.xpart, (size_t)x.d.cap * 4 * (size_t)nx);
-    x.bytes = (size_t)(cur - reinterpret_cast<char*>(base));
-    return x;
+    DetScratch s;
+    s.d = det_view(base, T, pairs > 0xFFFFFFFFll ? 0xFFFFFFFFll : pairs);   // (consumed positions are 32-bit)
+    char* cur = reinterpret_cast<char*>(base) + s.d.bytes;
+    s.xpart = nullptr;
+    if (nx != 0) carve(cur, s.xpart, (size_t)s.d.cap * 4 * (size_t)nx);
+    s.stride = (size_t)(cur - reinterpret_cast<char*>(base));
+    s.n_stage = (size_t)(P > 0 ? P : 0) * (size_t)(nx == 0 || extra_per_view == 1 ? 0 : extra_per_view == 2 ? 4 : nx);
+    s.stage = s.n_stage != 0 ? reinterpret_cast<float*>(reinterpret_cast<char*>(base) + (size_t)V * s.stride) : nullptr;
+    s.bytes = (size_t)V * s.stride + align_up((size_t)V * s.n_stage * sizeof(float), 256) + 256;
+    return s;
 }
-// floats per Gaussian and view of the shared rows' staging
-inline int det_x_shared_channels(int nx, int extra_per_view) { return extra_per_view == 0 ? nx : extra_per_view == 2 ? 4 : 0; }
 // what k_render_backward's storing instantiations (render_bwd.hip) need of it: view 0's arrays and the stride to the next view's
 struct RenderBwdDet {
     float* part;
@@ -356,6 +365,21 @@ struct RenderBwdDet {
 struct Launch {
     hipStream_t stream;
     int debug;
+};
+
+// A device array of the self-tests, allocated and freed with its scope; p stays NULL when the allocation failed.  The copies are
+// asynchronous on `s`: the host side has to outlive the caller's hipStreamSynchronize.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n;
+    explicit DevBuf(size_t count) : n(count) { if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) p = nullptr; }
+    DevBuf(const std::vector<T>& h, hipStream_t s) : DevBuf(h.size()) { (void)upload(h.data(), s); }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { (void)hipFree(p); }
+    bool upload(const T* h, hipStream_t s) const { return p && hipMemcpyAsync(p, h, n * sizeof(T), hipMemcpyHostToDevice, s) == hipSuccess; }
+    bool download(T* h, hipStream_t s) const { return p && hipMemcpyAsync(h, p, n * sizeof(T), hipMemcpyDeviceToHost, s) == hipSuccess; }
 };
 
 // One batch of V views: the view-0 carving of each arena plus the byte stride to the next view's arena.
@@ -448,24 +472,24 @@ struct ExtraGrads {
 int launch_render_forward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, float* out_color,
                           bool with_ckpt, const ExtraChannels* X = nullptr);
 // D != NULL: the storing instantiations -- partial sums go to D's slots instead of into the gradient records; with extra channels
-// XG->grad is then view 0's extra slots (DetXView::xpart, D->stride bytes per view) and XG->grad_hi is not used
+// XG->grad is then view 0's extra slots (DetScratch::xpart, D->stride bytes per view) and XG->grad_hi is not used
 int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, const float* dL_dpix,
                            const ExtraChannels* X = nullptr, const ExtraGrads* XG = nullptr, const RenderBwdDet* D = nullptr);
 int backward_subquadrant_moments(int set);   // render_bwd.hip: set >= 0 stores; 1 = moments about the sub-quadrant centres
 int forward_half_views(int set);   // render_fwd.hip: set >= 0 stores; returns the views per submission up to which the half-quadrant forward runs
 int render_math(int set);           // render_fwd.hip: 0 / 1 stores, < 0 queries, > 1 is refused; returns the arithmetic mode of the inference forwards (0 exact, 1 fast)
 int selftest_mm(hipStream_t stream, float* d_scratch256);   // the matrix-core pixel contraction of the render backward
-// det_backward.hip: the steps of the deterministic backward around the storing render backward (D: view 0's scratch, d_stride apart)
-int launch_det_prepare(const Launch& L, const Batch& B, const DetView& D, size_t d_stride, const uint32_t* point_list, int T);
-int launch_det_sort(const Launch& L, const Batch& B, const DetView& D, size_t d_stride, int P, int* result_buffer);
-int launch_det_reduce(const Launch& L, const Batch& B, const DetView& D, size_t d_stride, int sorted_buffer);
+// det_backward.hip: the steps of the deterministic backward around the storing render backward, on the scratch plan S
+int launch_det_prepare(const Launch& L, const Batch& B, const DetScratch& S, const uint32_t* point_list, int T);
+int launch_det_sort(const Launch& L, const Batch& B, const DetScratch& S, int P, int* result_buffer);
+int launch_det_reduce(const Launch& L, const Batch& B, const DetScratch& S, int sorted_buffer);
 int selftest_det_reduce(hipStream_t stream);   // the ordered reduction against a host sum in the same order, bit for bit
 // the extras' ordered reduction: per view into the caller's per-view rows (XG.grad / grad_hi, layout extra_per_view) or, rows the
-// views share, into `stage` ([V][P][det_x_shared_channels], cleared by the caller); launch_det_viewsum then adds the staged rows
-// of the views, v = 0 .. V - 1, into XG.grad (nothing to do for extra_per_view = 1)
-int launch_det_reduce_extra(const Launch& L, const Batch& B, const DetView& D, const float* xpart, size_t d_stride, int sorted_buffer,
-                            int P, int nx, int extra_per_view, const ExtraGrads& XG, float* stage);
-int launch_det_viewsum(const Launch& L, const Batch& B, int P, int nx, int extra_per_view, const ExtraGrads& XG, const float* stage);
+// views share, into S.stage (cleared by the caller); launch_det_viewsum then adds the staged rows of the views, v = 0 .. V - 1,
+// into XG.grad (nothing to do when S.stage is NULL)
+int launch_det_reduce_extra(const Launch& L, const Batch& B, const DetScratch& S, int sorted_buffer, int P, int nx, int extra_per_view,
+                            const ExtraGrads& XG);
+int launch_det_viewsum(const Launch& L, const Batch& B, const DetScratch& S, const ExtraGrads& XG);
 int selftest_det_reduce_extra(hipStream_t stream);   // both kernels against host sums in the same order, bit for bit
 #ifdef GSR_STATS
 int debug_bwd_stats(unsigned long long* out8, int reset);   // instrumentation build only

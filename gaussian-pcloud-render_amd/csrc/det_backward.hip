@@ -22,10 +22,15 @@
 //   k_det_reduce_x  the same walk over the same sorted runs on the extra slots, per view, into the caller's per-view rows or the
 //                   staging of the rows the views share
 //   k_det_viewsum   the staged rows of the views added for v = 0 .. V - 1 in float64, rounded once
+// Where the arrays of all this live in the caller's scratch block is DetScratch (common.hpp).  The two reduce kernels keep a copy
+// of the walk each: as one inlined function (same additions, bit-identical results) k_det_reduce_x compiled to seven more
+// instructions per eight positions and measured 0.8 % slower (profiles/r14_det_reduce_walk.txt).  One fixture and one host sum
+// (det_fixture.hpp) check both copies.
 #include <algorithm>
 #include <vector>
 
 #include "common.hpp"
+#include "det_fixture.hpp"
 
 namespace gsr {
 
@@ -90,13 +95,14 @@ __global__ __launch_bounds__(256) void k_det_emit(int T, const uint2* __restrict
     }
 }
 
-int launch_det_prepare(const Launch& L, const Batch& B, const DetView& D, size_t d_stride, const uint32_t* point_list, int T)
+int launch_det_prepare(const Launch& L, const Batch& B, const DetScratch& S, const uint32_t* point_list, int T)
 {
+    const DetView& D = S.d;
     hipLaunchKernelGGL(k_det_prefix, dim3(B.V), dim3(1024), 0, L.stream, T, (const uint32_t*)B.iv.tile_need, B.iv_stride, D.slot_base,
-                       D.count, d_stride, (uint32_t)D.cap);
+                       D.count, S.stride, (uint32_t)D.cap);
     if (int e = check_launch(L, "det_prefix")) return e;
     hipLaunchKernelGGL(k_det_emit, dim3((unsigned)div_up(T, 4), B.V), dim3(256), 0, L.stream, T, (const uint2*)B.iv.ranges, B.iv_stride,
-                       point_list, B.b_stride, (const uint32_t*)D.slot_base, D.key[0], D.flags, d_stride, (uint32_t)D.cap);
+                       point_list, B.b_stride, (const uint32_t*)D.slot_base, D.key[0], D.flags, S.stride, (uint32_t)D.cap);
     return check_launch(L, "det_emit");
 }
 
@@ -108,9 +114,10 @@ static int id_bits(int P)
     return bits;
 }
 
-int launch_det_sort(const Launch& L, const Batch& B, const DetView& D, size_t d_stride, int P, int* result_buffer)
+int launch_det_sort(const Launch& L, const Batch& B, const DetScratch& S, int P, int* result_buffer)
 {
-    const SortJob job{{D.key[0], D.key[1]}, {D.val[0], D.val[1]}, D.hist, D.totals, d_stride, D.count, d_stride, D.cap, B.V};
+    const DetView& D = S.d;
+    const SortJob job{{D.key[0], D.key[1]}, {D.val[0], D.val[1]}, D.hist, D.totals, S.stride, D.count, S.stride, D.cap, B.V};
     return launch_radix_sort_pairs(L, job, /*iota_vals=*/true, id_bits(P), result_buffer);
 }
 
@@ -174,79 +181,6 @@ __global__ __launch_bounds__(256) void k_det_reduce(const uint32_t* __restrict__
         }
         grad_rec[(size_t)id * GRAD_REC_WORDS + c] = (float)acc;   // (words 9..15: sums of the slots' zero padding)
     }
-}
-
-int launch_det_reduce(const Launch& L, const Batch& B, const DetView& D, size_t d_stride, int sorted_buffer)
-{
-    int64_t blocks = div_up(D.cap, 16);
-    if (blocks > DET_REDUCE_BLOCKS) blocks = DET_REDUCE_BLOCKS;
-    hipLaunchKernelGGL(k_det_reduce, dim3((unsigned)blocks, B.V), dim3(256), 0, L.stream, (const uint32_t*)D.key[sorted_buffer],
-                       (const uint32_t*)D.val[sorted_buffer], (const uint32_t*)D.flags, (const float*)D.part, (const uint64_t*)D.count,
-                       d_stride, B.grad_rec, B.gr_stride);
-    return check_launch(L, "det_reduce");
-}
-
-// Self-test of k_det_reduce: random runs, random marks, random partial sums; the host adds the same floats in the same order.
-int selftest_det_reduce(hipStream_t stream)
-{
-    const int P = 997, n = 20011;
-    std::vector<uint32_t> hk(n), hv(n), hf(n);
-    std::vector<float> hp((size_t)n * 4 * DET_SLOT_WORDS), want((size_t)P * GRAD_REC_WORDS, -1.f), got(want.size());
-    uint32_t x = 2463534242u;
-    const auto rnd = [&]() { x ^= x << 13; x ^= x >> 17; x ^= x << 5; return x; };
-    // sorted keys with runs of 1..80 elements and gaps between the ids
-    int used = 0;
-    for (uint32_t id = rnd() % 3u; id < (uint32_t)P && used < n; id += 1u + rnd() % 3u) {
-        const int len = 1 + (int)(rnd() % 80u);
-        for (int j = 0; j < len && used < n; j++) hk[used++] = id;
-    }
-    // positions: a strided walk through [0, n) keeps them distinct; ascending inside a run, as the stable sort leaves them
-    for (int j = 0; j < used; j++) hv[j] = (uint32_t)(((uint64_t)j * 7919u) % (uint32_t)n);
-    for (int a = 0, b = 0; a < used; a = b) {
-        for (b = a; b < used && hk[b] == hk[a];) b++;
-        std::sort(hv.begin() + a, hv.begin() + b);
-    }
-    for (int j = 0; j < n; j++) {
-        const uint32_t r = rnd();
-        hf[j] = ((r & 1u) ? 0x01u : 0u) | ((r & 2u) ? 0x0100u : 0u) | ((r & 4u) ? 0x010000u : 0u) | ((r & 8u) ? 0x01000000u : 0u);
-    }
-    for (auto& v : hp) v = (float)((int)(rnd() % 2000001u) - 1000000) * 1.37e-4f * (float)(1u + rnd() % 1000u);
-    for (int a = 0, b = 0; a < used; a = b) {
-        for (int c = 0; c < GRAD_REC_WORDS; c++) {
-            double acc = 0.0;
-            for (b = a; b < used && hk[b] == hk[a]; b++)
-                for (int q = 0; q < 4; q++)
-                    if ((hf[hv[b]] >> (8 * q)) & 0xFFu) acc = acc + (double)hp[((size_t)hv[b] * 4 + q) * DET_SLOT_WORDS + c];
-            want[(size_t)hk[a] * GRAD_REC_WORDS + c] = (float)acc;
-        }
-    }
-    uint32_t *dk = nullptr, *dv = nullptr, *df = nullptr;
-    float *dp = nullptr, *dg = nullptr;
-    uint64_t* dn = nullptr;
-    const uint64_t hn = (uint64_t)used;
-    int rc = 0;
-    if (hipMalloc(&dk, n * 4) != hipSuccess || hipMalloc(&dv, n * 4) != hipSuccess || hipMalloc(&df, n * 4) != hipSuccess ||
-        hipMalloc(&dp, hp.size() * 4) != hipSuccess || hipMalloc(&dg, want.size() * 4) != hipSuccess || hipMalloc(&dn, 16) != hipSuccess)
-        rc = -1;
-    if (rc == 0) {
-        std::fill(got.begin(), got.end(), -1.f);   // records of Gaussians without a run are not touched
-        (void)hipMemcpyAsync(dk, hk.data(), n * 4, hipMemcpyHostToDevice, stream);
-        (void)hipMemcpyAsync(dv, hv.data(), n * 4, hipMemcpyHostToDevice, stream);
-        (void)hipMemcpyAsync(df, hf.data(), n * 4, hipMemcpyHostToDevice, stream);
-        (void)hipMemcpyAsync(dp, hp.data(), hp.size() * 4, hipMemcpyHostToDevice, stream);
-        (void)hipMemcpyAsync(dg, got.data(), got.size() * 4, hipMemcpyHostToDevice, stream);
-        (void)hipMemcpyAsync(dn, &hn, 8, hipMemcpyHostToDevice, stream);
-        hipLaunchKernelGGL(k_det_reduce, dim3(37, 1), dim3(256), 0, stream, (const uint32_t*)dk, (const uint32_t*)dv, (const uint32_t*)df,
-                           (const float*)dp, (const uint64_t*)dn, (size_t)0, dg, (size_t)0);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(got.data(), dg, got.size() * 4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipStreamSynchronize(stream) != hipSuccess)
-            rc = -1;
-    }
-    (void)hipFree(dk); (void)hipFree(dv); (void)hipFree(df); (void)hipFree(dp); (void)hipFree(dg); (void)hipFree(dn);
-    if (rc != 0) return rc;
-    for (size_t j = 0; j < want.size(); j++)
-        if (__builtin_memcmp(&got[j], &want[j], 4) != 0) return 1 + (int)j;
-    return 0;
 }
 
 // ---- the extras' ordered reduction (gsr_backward_batch_channels_det) -------------------------------------------------------------
@@ -321,132 +255,135 @@ __global__ __launch_bounds__(256) void k_det_viewsum(const float* __restrict__ s
     out[i] = (float)acc;
 }
 
-template <int NX>
-static void launch_reduce_x(dim3 grid, hipStream_t stream, const DetView& D, int sorted_buffer, const float* xpart, size_t d_stride,
-                            float* dst_lo, size_t lo_vstride, uint32_t n_lo, float* dst_hi, size_t hi_vstride)
+static dim3 reduce_grid(const DetView& D, int V)
 {
-    hipLaunchKernelGGL(k_det_reduce_x<NX>, grid, dim3(256), 0, stream, (const uint32_t*)D.key[sorted_buffer],
-                       (const uint32_t*)D.val[sorted_buffer], (const uint32_t*)D.flags, xpart, (const uint64_t*)D.count, d_stride, dst_lo,
-                       lo_vstride, n_lo, dst_hi, hi_vstride);
+    const int64_t blocks = div_up(D.cap, 16);
+    return dim3((unsigned)(blocks < DET_REDUCE_BLOCKS ? blocks : DET_REDUCE_BLOCKS), V);
 }
 
-int launch_det_reduce_extra(const Launch& L, const Batch& B, const DetView& D, const float* xpart, size_t d_stride, int sorted_buffer,
-                            int P, int nx, int extra_per_view, const ExtraGrads& XG, float* stage)
+int launch_det_reduce(const Launch& L, const Batch& B, const DetScratch& S, int sorted_buffer)
 {
-    const size_t n_stage = (size_t)P * (size_t)det_x_shared_channels(nx, extra_per_view);
-    // (the caller has cleared `stage`: a Gaussian without a run in a view adds nothing to that view's sum)
-    int64_t blocks = div_up(D.cap, 16);
-    if (blocks > DET_REDUCE_BLOCKS) blocks = DET_REDUCE_BLOCKS;
-    const dim3 grid((unsigned)blocks, B.V);
+    const DetView& D = S.d;
+    hipLaunchKernelGGL(k_det_reduce, reduce_grid(D, B.V), dim3(256), 0, L.stream, (const uint32_t*)D.key[sorted_buffer],
+                       (const uint32_t*)D.val[sorted_buffer], (const uint32_t*)D.flags, (const float*)D.part, (const uint64_t*)D.count,
+                       S.stride, B.grad_rec, B.gr_stride);
+    return check_launch(L, "det_reduce");
+}
+
+template <int NX>
+static void launch_reduce_x(dim3 grid, hipStream_t stream, const DetScratch& S, int sorted_buffer, float* dst_lo, size_t lo_vstride,
+                            uint32_t n_lo, float* dst_hi, size_t hi_vstride)
+{
+    const DetView& D = S.d;
+    hipLaunchKernelGGL(k_det_reduce_x<NX>, grid, dim3(256), 0, stream, (const uint32_t*)D.key[sorted_buffer],
+                       (const uint32_t*)D.val[sorted_buffer], (const uint32_t*)D.flags, (const float*)S.xpart, (const uint64_t*)D.count,
+                       S.stride, dst_lo, lo_vstride, n_lo, dst_hi, hi_vstride);
+}
+
+int launch_det_reduce_extra(const Launch& L, const Batch& B, const DetScratch& S, int sorted_buffer, int P, int nx, int extra_per_view,
+                            const ExtraGrads& XG)
+{
+    // (the caller has cleared S.stage: a Gaussian without a run in a view adds nothing to that view's sum)
+    const dim3 grid = reduce_grid(S.d, B.V);
     // layout 0: every channel staged; 1: every channel into the caller's rows of the view; 2: 0..3 staged, 4..7 into the caller's
-    float* lo = extra_per_view == 1 ? XG.grad : stage;
-    const size_t lo_vs = extra_per_view == 1 ? (size_t)P * (size_t)nx : n_stage;
+    float* lo = extra_per_view == 1 ? XG.grad : S.stage;
+    const size_t lo_vs = extra_per_view == 1 ? (size_t)P * (size_t)nx : S.n_stage;
     const uint32_t n_lo = extra_per_view == 2 ? 4u : (uint32_t)nx;
     float* hi = extra_per_view == 2 ? XG.grad_hi : nullptr;
     const size_t hi_vs = extra_per_view == 2 ? (size_t)P * 4 : 0;
-    if (nx == 4) launch_reduce_x<4>(grid, L.stream, D, sorted_buffer, xpart, d_stride, lo, lo_vs, n_lo, hi, hi_vs);
-    else launch_reduce_x<8>(grid, L.stream, D, sorted_buffer, xpart, d_stride, lo, lo_vs, n_lo, hi, hi_vs);
+    if (nx == 4) launch_reduce_x<4>(grid, L.stream, S, sorted_buffer, lo, lo_vs, n_lo, hi, hi_vs);
+    else launch_reduce_x<8>(grid, L.stream, S, sorted_buffer, lo, lo_vs, n_lo, hi, hi_vs);
     return check_launch(L, "det_reduce_extra");
 }
 
-int launch_det_viewsum(const Launch& L, const Batch& B, int P, int nx, int extra_per_view, const ExtraGrads& XG, const float* stage)
+int launch_det_viewsum(const Launch& L, const Batch& B, const DetScratch& S, const ExtraGrads& XG)
 {
-    const size_t n_stage = (size_t)P * (size_t)det_x_shared_channels(nx, extra_per_view);
-    if (n_stage == 0) return GSR_OK;
-    hipLaunchKernelGGL(k_det_viewsum, dim3((unsigned)div_up((int64_t)n_stage, 256)), dim3(256), 0, L.stream, stage, n_stage, B.V, XG.grad);
+    if (!S.stage) return GSR_OK;
+    hipLaunchKernelGGL(k_det_viewsum, dim3((unsigned)div_up((int64_t)S.n_stage, 256)), dim3(256), 0, L.stream, (const float*)S.stage,
+                       S.n_stage, B.V, XG.grad);
     return check_launch(L, "det_viewsum");
 }
 
-// Self-test of the extras' reduction: random runs, marks and values as in selftest_det_reduce, eight channels in the split layout
-// (0..3 staged, 4..7 into per-view rows) and four channels unsplit; then k_det_viewsum over three views of random staged rows.
-// The host adds the same floats in the same order.
+// ---- self-tests --------------------------------------------------------------------------------------------------------------
+// The fixture (det_fixture.hpp) on the device, as the single view of a scratch plan: `values` stands for the slots of either kind.
+struct DetFixtureDev {
+    const uint64_t n = DetFixture::N;
+    DevBuf<uint32_t> key, val, flags;
+    DevBuf<float> values;
+    DevBuf<uint64_t> count;
+    DetFixtureDev(const DetFixture& F, hipStream_t s) : key(F.key, s), val(F.val, s), flags(F.flags, s), values(F.values, s), count(1)
+    {
+        (void)count.upload(&n, s);
+    }
+    bool ok() const { return key.p && val.p && flags.p && values.p && count.p; }
+    DetScratch plan() const
+    {
+        DetScratch S{};
+        S.d.key[0] = key.p; S.d.val[0] = val.p; S.d.flags = flags.p; S.d.count = count.p;
+        S.d.part = S.xpart = values.p;
+        return S;
+    }
+};
+
+// 0 when the arrays agree bit for bit, else base + the first index at which they differ
+static int first_difference(const std::vector<float>& got, const std::vector<float>& want, int base)
+{
+    for (size_t j = 0; j < want.size(); j++)
+        if (__builtin_memcmp(&got[j], &want[j], 4) != 0) return base + (int)j;
+    return 0;
+}
+
+// k_det_reduce on the fixture against the host's sums in the same order; records of Gaussians without a run are not touched (-1)
+int selftest_det_reduce(hipStream_t stream)
+{
+    static_assert(GRAD_REC_WORDS == DET_SLOT_WORDS, "a slot is laid out like a record");
+    const DetFixture F;
+    const std::vector<float> want = F.sums(DET_SLOT_WORDS);
+    std::vector<float> got(want.size(), -1.f);
+    const DetFixtureDev dev(F, stream);
+    const DevBuf<float> rec(got, stream);
+    if (!dev.ok() || !rec.p) return -1;
+    const DetScratch S = dev.plan();
+    hipLaunchKernelGGL(k_det_reduce, dim3(37, 1), dim3(256), 0, stream, (const uint32_t*)S.d.key[0], (const uint32_t*)S.d.val[0],
+                       (const uint32_t*)S.d.flags, (const float*)S.d.part, (const uint64_t*)S.d.count, (size_t)0, rec.p, (size_t)0);
+    if (hipGetLastError() != hipSuccess || !rec.download(got.data(), stream) || hipStreamSynchronize(stream) != hipSuccess) return -1;
+    return first_difference(got, want, 1);
+}
+
+// The extras' reduction on the same fixture: eight channels in the split layout (0..3 staged, 4..7 into per-view rows) and four
+// channels unsplit; then k_det_viewsum over three views of random staged rows.  The host adds the same floats in the same order.
 int selftest_det_reduce_extra(hipStream_t stream)
 {
-    const int P = 997, n = 20011, V = 3;
-    std::vector<uint32_t> hk(n), hv(n), hf(n);
-    std::vector<float> hp((size_t)n * 4 * 8), hs((size_t)V * P * 4);
-    uint32_t x = 88172645u;
-    const auto rnd = [&]() { x ^= x << 13; x ^= x >> 17; x ^= x << 5; return x; };
-    int used = 0;
-    for (uint32_t id = rnd() % 3u; id < (uint32_t)P && used < n; id += 1u + rnd() % 3u) {
-        const int len = 1 + (int)(rnd() % 80u);
-        for (int j = 0; j < len && used < n; j++) hk[used++] = id;
+    const int P = DetFixture::P, V = 3;
+    DetFixture F;
+    const std::vector<float> want8 = F.sums(8), want4 = F.sums(4);
+    std::vector<float> wlo((size_t)P * 4), whi(wlo), wantv(wlo), hs((size_t)V * P * 4);   // want8's halves: the rows of channels 0..3 and 4..7
+    for (size_t j = 0; j < wlo.size(); j++) {
+        wlo[j] = want8[j / 4 * 8 + j % 4];
+        whi[j] = want8[j / 4 * 8 + 4 + j % 4];
     }
-    for (int j = 0; j < used; j++) hv[j] = (uint32_t)(((uint64_t)j * 7919u) % (uint32_t)n);
-    for (int a = 0, b = 0; a < used; a = b) {
-        for (b = a; b < used && hk[b] == hk[a];) b++;
-        std::sort(hv.begin() + a, hv.begin() + b);
-    }
-    for (int j = 0; j < n; j++) {
-        const uint32_t r = rnd();
-        hf[j] = ((r & 1u) ? 0x01u : 0u) | ((r & 2u) ? 0x0100u : 0u) | ((r & 4u) ? 0x010000u : 0u) | ((r & 8u) ? 0x01000000u : 0u);
-    }
-    const auto val = [&]() { return (float)((int)(rnd() % 2000001u) - 1000000) * 1.37e-4f * (float)(1u + rnd() % 1000u); };
-    for (auto& v : hp) v = val();
-    for (auto& v : hs) v = val();
-    // want8: [P][8] (the test keeps lo and hi rows side by side), want4: [P][4] read from the same block as [n][4][4]; -1 = untouched
-    std::vector<float> want8((size_t)P * 8, -1.f), want4((size_t)P * 4, -1.f), wantv((size_t)P * 4);
-    for (int a = 0, b = 0; a < used; a = b) {
-        for (int nx = 4; nx <= 8; nx += 4)
-            for (int c = 0; c < nx; c++) {
-                double acc = 0.0;
-                for (b = a; b < used && hk[b] == hk[a]; b++)
-                    for (int q = 0; q < 4; q++)
-                        if ((hf[hv[b]] >> (8 * q)) & 0xFFu) acc = acc + (double)hp[((size_t)hv[b] * 4 + q) * nx + c];
-                (nx == 8 ? want8 : want4)[(size_t)hk[a] * nx + c] = (float)acc;
-            }
-    }
+    for (auto& v : hs) v = F.value();
     for (size_t i = 0; i < wantv.size(); i++) {
         double acc = 0.0;
         for (int v = 0; v < V; v++) acc = acc + (double)hs[(size_t)v * wantv.size() + i];
         wantv[i] = (float)acc;
     }
-    uint32_t *dk = nullptr, *dv = nullptr, *df = nullptr;
-    float *dp = nullptr, *dlo = nullptr, *dhi = nullptr, *d4 = nullptr, *ds = nullptr, *dvs = nullptr;
-    uint64_t* dn = nullptr;
-    const uint64_t hn = (uint64_t)used;
-    const size_t row4 = (size_t)P * 4 * sizeof(float);
     std::vector<float> glo((size_t)P * 4, -1.f), ghi(glo), g4(glo), gv(glo);
-    int rc = 0;
-    if (hipMalloc(&dk, n * 4) != hipSuccess || hipMalloc(&dv, n * 4) != hipSuccess || hipMalloc(&df, n * 4) != hipSuccess ||
-        hipMalloc(&dp, hp.size() * 4) != hipSuccess || hipMalloc(&dlo, row4) != hipSuccess || hipMalloc(&dhi, row4) != hipSuccess ||
-        hipMalloc(&d4, row4) != hipSuccess || hipMalloc(&ds, hs.size() * 4) != hipSuccess || hipMalloc(&dvs, row4) != hipSuccess ||
-        hipMalloc(&dn, 16) != hipSuccess)
-        rc = -1;
-    if (rc == 0) {
-        (void)hipMemcpyAsync(dk, hk.data(), n * 4, hipMemcpyHostToDevice, stream);
-        (void)hipMemcpyAsync(dv, hv.data(), n * 4, hipMemcpyHostToDevice, stream);
-        (void)hipMemcpyAsync(df, hf.data(), n * 4, hipMemcpyHostToDevice, stream);
-        (void)hipMemcpyAsync(dp, hp.data(), hp.size() * 4, hipMemcpyHostToDevice, stream);
-        (void)hipMemcpyAsync(ds, hs.data(), hs.size() * 4, hipMemcpyHostToDevice, stream);
-        (void)hipMemcpyAsync(dn, &hn, 8, hipMemcpyHostToDevice, stream);
-        (void)hipMemcpyAsync(dlo, glo.data(), row4, hipMemcpyHostToDevice, stream);
-        (void)hipMemcpyAsync(dhi, glo.data(), row4, hipMemcpyHostToDevice, stream);
-        (void)hipMemcpyAsync(d4, glo.data(), row4, hipMemcpyHostToDevice, stream);
-        DetView D{};
-        D.key[0] = dk; D.val[0] = dv; D.flags = df; D.count = dn;
-        launch_reduce_x<8>(dim3(37, 1), stream, D, 0, dp, 0, dlo, 0, 4u, dhi, 0);
-        launch_reduce_x<4>(dim3(41, 1), stream, D, 0, dp, 0, d4, 0, 4u, nullptr, 0);
-        hipLaunchKernelGGL(k_det_viewsum, dim3((unsigned)div_up((int64_t)P * 4, 256)), dim3(256), 0, stream, (const float*)ds,
-                           (size_t)P * 4, V, dvs);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(glo.data(), dlo, row4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipMemcpyAsync(ghi.data(), dhi, row4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipMemcpyAsync(g4.data(), d4, row4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipMemcpyAsync(gv.data(), dvs, row4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
-            rc = -1;
-    }
-    (void)hipFree(dk); (void)hipFree(dv); (void)hipFree(df); (void)hipFree(dp); (void)hipFree(dlo); (void)hipFree(dhi); (void)hipFree(d4);
-    (void)hipFree(ds); (void)hipFree(dvs); (void)hipFree(dn);
-    if (rc != 0) return rc;
-    for (int g = 0; g < P; g++)
-        for (int c = 0; c < 4; c++) {
-            const size_t j = (size_t)g * 4 + c;
-            if (__builtin_memcmp(&glo[j], &want8[(size_t)g * 8 + c], 4) != 0) return 1 + (int)j;
-            if (__builtin_memcmp(&ghi[j], &want8[(size_t)g * 8 + 4 + c], 4) != 0) return 100001 + (int)j;
-            if (__builtin_memcmp(&g4[j], &want4[j], 4) != 0) return 200001 + (int)j;
-            if (__builtin_memcmp(&gv[j], &wantv[j], 4) != 0) return 300001 + (int)j;
-        }
-    return 0;
+    const DetFixtureDev dev(F, stream);
+    const DevBuf<float> dlo(glo, stream), dhi(glo, stream), d4(glo, stream), ds(hs, stream), dvs(gv.size());
+    if (!dev.ok() || !dlo.p || !dhi.p || !d4.p || !ds.p || !dvs.p) return -1;
+    const DetScratch S = dev.plan();
+    launch_reduce_x<8>(dim3(37, 1), stream, S, 0, dlo.p, 0, 4u, dhi.p, 0);
+    launch_reduce_x<4>(dim3(41, 1), stream, S, 0, d4.p, 0, 4u, nullptr, 0);
+    hipLaunchKernelGGL(k_det_viewsum, dim3((unsigned)div_up((int64_t)P * 4, 256)), dim3(256), 0, stream, (const float*)ds.p, (size_t)P * 4,
+                       V, dvs.p);
+    if (hipGetLastError() != hipSuccess || !dlo.download(glo.data(), stream) || !dhi.download(ghi.data(), stream) ||
+        !d4.download(g4.data(), stream) || !dvs.download(gv.data(), stream) || hipStreamSynchronize(stream) != hipSuccess)
+        return -1;
+    if (int r = first_difference(glo, wlo, 1)) return r;
+    if (int r = first_difference(ghi, whi, 100001)) return r;
+    if (int r = first_difference(g4, want4, 200001)) return r;
+    return first_difference(gv, wantv, 300001);
 }
 
 }  // namespace gsr

@@ -250,20 +250,19 @@ def last_list_pairs(V):
     return int(max(pairs))
 
 
-def det_scratch(V, P, W, H, pairs, binning_bytes, device):
-    """the scratch block of one deterministic backward.  pairs None: the lists' extent is not known here; (bytes of a view's
-    binning arena) / 16 is an upper bound of what the arena holds (the library checks the size against the lists it remembers)"""
+def det_scratch(V, P, W, H, pairs, binning_bytes, device, nx=0, extra_per_view=0):
+    """the scratch block of one deterministic backward; nx != 0: of the channels backward (gsr_backward_det_channels_bytes).
+    pairs None: the lists' extent is not known here; (bytes of a view's binning arena) / 16 is an upper bound of what the arena
+    holds (the library checks the size against the lists it remembers)"""
     if pairs is None:
         pairs = max(1, int(binning_bytes) // max(1, V) // 16)
-    return torch.empty((int(lib.gsr_backward_det_bytes(V, P, W, H, int(pairs))),), dtype=torch.uint8, device=device)
+    n = (lib.gsr_backward_det_channels_bytes(V, P, W, H, int(pairs), nx, extra_per_view) if nx
+         else lib.gsr_backward_det_bytes(V, P, W, H, int(pairs)))
+    return torch.empty((int(n),), dtype=torch.uint8, device=device)
 
 
 def det_channels_scratch(V, P, W, H, pairs, binning_bytes, nx, extra_per_view, device):
-    """the scratch block of one deterministic channels backward (gsr_backward_det_channels_bytes); pairs None: as in det_scratch"""
-    if pairs is None:
-        pairs = max(1, int(binning_bytes) // max(1, V) // 16)
-    return torch.empty((int(lib.gsr_backward_det_channels_bytes(V, P, W, H, int(pairs), nx, extra_per_view)),), dtype=torch.uint8,
-                       device=device)
+    return det_scratch(V, P, W, H, pairs, binning_bytes, device, nx, extra_per_view)
 
 
 # ---- binning-arena capacity -----------------------------------------------------------------------------------------
