@@ -956,6 +956,100 @@ int gsr_selftest(gsr_stream_t stream)
     return GSR_OK;
 }
 
+// Test probe of sort.hip: launch_radix_sort_pairs on the caller's arrays, in work buffers of its own (freed on every path, like the
+// self-test's).  The caller says which kernels run (key width, block size, depth control); nothing is decided silently here.
+int gsr_sort_probe(const void* keys, const uint32_t* vals, size_t stride, const uint64_t* n_dev, size_t n_stride, int V, int64_t cap,
+                   int end_bit, int flags, void* keys_out, uint32_t* vals_out, uint32_t* ctl_out, gsr_stream_t stream)
+{
+    const bool key16 = (flags & GSR_SORT_KEY16) != 0, small = (flags & GSR_SORT_SMALL_BLOCKS) != 0, depth = (flags & GSR_SORT_DEPTH_CTL) != 0;
+    if (flags & ~(GSR_SORT_KEY16 | GSR_SORT_SMALL_BLOCKS | GSR_SORT_DEPTH_CTL)) return fail(GSR_ERR_INVALID, "[gsr] sort probe: unknown flags 0x%x", flags);
+    if (!keys || !keys_out || !vals_out) return fail(GSR_ERR_INVALID, "[gsr] sort probe: NULL keys or outputs");
+    if (V < 1) return fail(GSR_ERR_INVALID, "[gsr] sort probe: view count %d", V);
+    if (cap < 0 || cap > ((int64_t)1 << 30)) return fail(GSR_ERR_INVALID, "[gsr] sort probe: capacity %lld", (long long)cap);
+    if (end_bit < 1 || end_bit > 32) return fail(GSR_ERR_INVALID, "[gsr] sort probe: end_bit %d is not in 1..32", end_bit);
+    if (key16 && end_bit > 16) return fail(GSR_ERR_INVALID, "[gsr] sort probe: 16-bit keys have no bit %d", end_bit - 1);
+    if (depth && (end_bit != 32 || key16 || vals != nullptr))
+        return fail(GSR_ERR_INVALID, "[gsr] sort probe: depth control sorts 32 bits of uint32_t keys with index values");
+    if (depth && !ctl_out) return fail(GSR_ERR_INVALID, "[gsr] sort probe: depth control needs ctl_out");
+    if (small && (key16 || end_bit % RADIX_BITS != 0))
+        return fail(GSR_ERR_INVALID, "[gsr] sort probe: small blocks take uint32_t keys and whole 8-bit digits");
+    const size_t ksz = key16 ? 2 : 4;
+    if (V > 1 && (stride % 256 != 0 || stride < (size_t)cap * 4))
+        return fail(GSR_ERR_INVALID, "[gsr] sort probe: view stride %zu (a multiple of 256, at least 4 * cap)", stride);
+    if (n_dev && V > 1 && (n_stride == 0 || n_stride % 8 != 0)) return fail(GSR_ERR_INVALID, "[gsr] sort probe: count stride %zu", n_stride);
+    if (cap == 0) return GSR_OK;
+
+    hipStream_t s = (hipStream_t)stream;
+    const int tile = small ? RS_TILE_SMALL : RS_TILE;
+    const size_t nblk_pad = (size_t)sort_hist_stride(cap, tile);
+    // one stride serves every array of a SortJob: the caller's when the count matrix fits it (the views then sit at the caller's
+    // alignment), else the count matrix's size
+    const size_t need = std::max(align_up((size_t)cap * 4, 256), (size_t)RADIX * nblk_pad * 4);
+    const size_t S = (V > 1 && stride >= need) ? stride : need;
+    const size_t words = (size_t)V * S / 4;
+    const DevBuf<uint32_t> k0(words), k1(words), v0(words), v1(words), hist(words), tot(words), mm(words), ctl(words);
+    if (!k0.p || !k1.p || !v0.p || !v1.p || !hist.p || !tot.p || !mm.p || !ctl.p) return fail(GSR_ERR_HIP, "[gsr] sort probe: hipMalloc failed");
+    const auto hip_fail = [&](const char* what) {
+        (void)hipStreamSynchronize(s);
+        (void)hipGetLastError();
+        return fail(GSR_ERR_HIP, "[gsr] sort probe: %s failed", what);
+    };
+    if (hipMemsetAsync(ctl.p, 0, words * 4, s) != hipSuccess) return hip_fail("memset");
+    for (int v = 0; v < V; v++) {
+        if (hipMemcpyAsync((char*)k0.p + v * S, (const char*)keys + v * stride, (size_t)cap * ksz, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+            (vals && hipMemcpyAsync((char*)v0.p + v * S, (const char*)vals + v * stride, (size_t)cap * 4, hipMemcpyDeviceToDevice, s) != hipSuccess))
+            return hip_fail("copy in");
+    }
+    SortJob job{{k0.p, k1.p}, {v0.p, v1.p}, hist.p, tot.p, S, n_dev, n_stride, cap, V};
+    job.small_blocks = small;
+    if (depth) { job.blk_minmax = mm.p; job.sortctl = ctl.p; }
+    int res = 0;
+    const Launch L{s, 1};
+    if (int rc = launch_radix_sort_pairs(L, job, /*iota_vals=*/vals == nullptr, end_bit, &res, key16)) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    std::vector<uint32_t> hctl((size_t)V * 4, 0u);
+    if (depth) {
+        for (int v = 0; v < V; v++)
+            if (hipMemcpyAsync(&hctl[4 * (size_t)v], (const char*)ctl.p + v * S, 16, hipMemcpyDeviceToHost, s) != hipSuccess) return hip_fail("control words");
+        if (hipStreamSynchronize(s) != hipSuccess) return hip_fail("sort");
+    }
+    for (int v = 0; v < V; v++) {
+        int buf = res;
+        if (depth) {   // (base, bits, passes, 0) like GSR_Q_DEPTH_SORT; a view's result is where ITS pass count left it
+            hctl[4 * (size_t)v + 2] = depth_sort_passes(hctl[4 * (size_t)v + SORTCTL_BITS]);
+            hctl[4 * (size_t)v + 3] = 0u;
+            buf = (int)(hctl[4 * (size_t)v + 2] & 1u);
+        }
+        if (hipMemcpyAsync((char*)keys_out + v * stride, (const char*)job.key[buf] + v * S, (size_t)cap * ksz, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+            hipMemcpyAsync((char*)vals_out + v * stride, (const char*)job.val[buf] + v * S, (size_t)cap * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return hip_fail("copy out");
+    }
+    if (depth && hipMemcpyAsync(ctl_out, hctl.data(), (size_t)V * 16, hipMemcpyHostToDevice, s) != hipSuccess) return hip_fail("control words");
+    if (hipStreamSynchronize(s) != hipSuccess) return hip_fail("sort");
+    return GSR_OK;
+}
+
+// Test probe of binning.hip: k_tile_ranges on the caller's sorted keys and device counts, straight into the caller's ranges.
+int gsr_tile_ranges_probe(const void* keys, size_t stride, const uint64_t* n_dev, size_t n_stride, int V, int64_t cap, int T, int key16,
+                          uint32_t* ranges, gsr_stream_t stream)
+{
+    if (!keys || !n_dev || !ranges) return fail(GSR_ERR_INVALID, "[gsr] tile ranges probe: NULL");
+    if (V < 1) return fail(GSR_ERR_INVALID, "[gsr] tile ranges probe: view count %d", V);
+    if (cap < 0 || cap > 0xFFFFFFFFll) return fail(GSR_ERR_INVALID, "[gsr] tile ranges probe: capacity %lld", (long long)cap);
+    if (T < 1 || (key16 && T > 65536)) return fail(GSR_ERR_INVALID, "[gsr] tile ranges probe: %d tiles", T);
+    if (V > 1 && (stride % 16 != 0 || stride < (size_t)cap * (key16 ? 2 : 4) || n_stride == 0 || n_stride % 8 != 0))
+        return fail(GSR_ERR_INVALID, "[gsr] tile ranges probe: view strides %zu / %zu", stride, n_stride);
+    hipStream_t s = (hipStream_t)stream;
+    const Launch L{s, 1};
+    if (int rc = launch_tile_ranges_raw(L, V, n_dev, n_stride, cap, keys, stride, reinterpret_cast<uint2*>(ranges), (size_t)T * sizeof(uint2), T, key16 != 0)) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    return GSR_OK;
+}
+
 int gsr_clock_probe_launch(void* dst16, int iters, gsr_stream_t stream)
 {
     if (!dst16 || iters < 1) return fail(GSR_ERR_INVALID, "[gsr] clock probe: bad argument");

@@ -409,16 +409,23 @@ __global__ __launch_bounds__(256) void k_tile_ranges(const uint64_t* __restrict_
     ranges[t] = first < last ? make_uint2(first, last) : make_uint2(0u, 0u);
 }
 
+// counters: view 0's pair count (word CNT_NUM_RENDERED of a view's counters); every array at its own byte stride per view
+int launch_tile_ranges_raw(const Launch& L, int V, const uint64_t* counters, size_t g_stride, int64_t cap, const void* sorted_keys,
+                           size_t b_stride, uint2* ranges, size_t iv_stride, int T, bool key16)
+{
+    const dim3 grid((unsigned)div_up(T, RANGE_TILES_PER_WG), V);
+    if (key16)
+        hipLaunchKernelGGL(k_tile_ranges<uint16_t>, grid, dim3(256), 0, L.stream, counters, g_stride, cap,
+                           (const uint16_t*)sorted_keys, b_stride, ranges, iv_stride, T);
+    else
+        hipLaunchKernelGGL(k_tile_ranges<uint32_t>, grid, dim3(256), 0, L.stream, counters, g_stride, cap, (const uint32_t*)sorted_keys,
+                           b_stride, ranges, iv_stride, T);
+    return check_launch(L, "tile_ranges");
+}
+
 int launch_tile_ranges(const Launch& L, const Batch& B, const uint32_t* sorted_keys, int T, bool key16)
 {
-    const dim3 grid((unsigned)div_up(T, RANGE_TILES_PER_WG), B.V);
-    if (key16)
-        hipLaunchKernelGGL(k_tile_ranges<uint16_t>, grid, dim3(256), 0, L.stream, B.g.counters, B.g_stride, B.b.cap,
-                           (const uint16_t*)sorted_keys, B.b_stride, B.iv.ranges, B.iv_stride, T);
-    else
-        hipLaunchKernelGGL(k_tile_ranges<uint32_t>, grid, dim3(256), 0, L.stream, B.g.counters, B.g_stride, B.b.cap, sorted_keys,
-                           B.b_stride, B.iv.ranges, B.iv_stride, T);
-    return check_launch(L, "tile_ranges");
+    return launch_tile_ranges_raw(L, B.V, B.g.counters, B.g_stride, B.b.cap, sorted_keys, B.b_stride, B.iv.ranges, B.iv_stride, T, key16);
 }
 
 // ---- render launch order: tiles by descending work estimate (128 quarter-octave buckets) -------------

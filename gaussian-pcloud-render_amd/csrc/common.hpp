@@ -444,6 +444,8 @@ inline bool tile_keys16(int T) { return T <= 65536; }
 // binning.hip
 int launch_duplicate(const Launch& L, int P, const Batch& B, int gridx, bool key16, uint64_t* host_land);
 int launch_tile_ranges(const Launch& L, const Batch& B, const uint32_t* sorted_keys, int T, bool key16);
+int launch_tile_ranges_raw(const Launch& L, int V, const uint64_t* counters, size_t g_stride, int64_t cap, const void* sorted_keys,
+                           size_t b_stride, uint2* ranges, size_t iv_stride, int T, bool key16);   // the same on bare arrays (gsr_tile_ranges_probe)
 int launch_tile_order(const Launch& L, const Batch& B, int T);
 int launch_bwd_items(const Launch& L, const Batch& B, int T, int P);
 // render_fwd.hip / render_bwd.hip

@@ -71,6 +71,8 @@ _DECL = {
     "gsr_set_render_math": (_int, [_int]),
     "gsr_get_profile": (_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _int]),
     "gsr_selftest": (_int, [_fp]),
+    "gsr_sort_probe": (_int, [_fp, _fp, _size, _fp, _size, _int, _i64, _int, _int, _fp, _fp, _fp, _fp]),
+    "gsr_tile_ranges_probe": (_int, [_fp, _size, _fp, _size, _int, _i64, _int, _int, _fp, _fp]),
     "gsr_d2h_count": (C.c_longlong, []),
     "gsr_clock_probe_launch": (_int, [_fp, _int, _fp]),
     "gsr_wall_clock_khz": (_int, []),
@@ -966,6 +968,53 @@ class ClockProbe:
 def selftest(device):
     with torch.cuda.device(device):
         _check(lib.gsr_selftest(_stream_handle(device)))
+
+
+SORT_KEY16, SORT_SMALL_BLOCKS, SORT_DEPTH_CTL = 1, 2, 4
+
+
+def sort_probe(keys, vals, cap, end_bit, V=1, stride=0, counts=None, small_blocks=False, depth_ctl=False):
+    """The library's radix sort on device arrays (tests; include/gsr.h gsr_sort_probe).  keys: contiguous int32 or int16 tensor
+    (the bit patterns of uint32_t / uint16_t keys) holding V views `stride` bytes apart; vals: int32 tensor laid out the same way,
+    or None for index values; counts: int64 tensor [V, k] whose column 0 holds the views' element counts, or None (cap each).
+    Returns (keys_out like keys, vals_out int32 with a view every `stride` bytes, ctl int32 [V, 4] or None)."""
+    _require_hip(keys.device)
+    if keys.dtype not in (torch.int32, torch.int16) or not keys.is_contiguous():
+        raise RuntimeError("sort_probe: keys are a contiguous int32 or int16 tensor")
+    flags = ((SORT_KEY16 if keys.dtype == torch.int16 else 0) | (SORT_SMALL_BLOCKS if small_blocks else 0)
+             | (SORT_DEPTH_CTL if depth_ctl else 0))
+    nbytes = (V - 1) * int(stride) + int(cap) * 4
+    if keys.numel() * keys.element_size() < (V - 1) * int(stride) + int(cap) * keys.element_size() or \
+            (vals is not None and (vals.dtype != torch.int32 or not vals.is_contiguous() or vals.numel() * 4 < nbytes)):
+        raise RuntimeError("sort_probe: arrays shorter than V views of cap elements")
+    if counts is not None and (counts.dtype != torch.int64 or counts.dim() != 2 or counts.shape[0] != V or not counts.is_contiguous()):
+        raise RuntimeError("sort_probe: counts are a contiguous int64 tensor [V, k]")
+    keys_out = torch.zeros_like(keys)
+    vals_out = torch.zeros(max(1, (nbytes + 3) // 4), dtype=torch.int32, device=keys.device)
+    ctl = torch.zeros((V, 4), dtype=torch.int32, device=keys.device) if depth_ctl else None
+    with torch.cuda.device(keys.device):
+        _check(lib.gsr_sort_probe(keys.data_ptr(), _ptr(vals), int(stride), _ptr(counts),
+                                  counts.shape[1] * 8 if counts is not None else 0, V, int(cap), int(end_bit), flags,
+                                  keys_out.data_ptr(), vals_out.data_ptr(), _ptr(ctl), _stream_handle(keys.device)))
+    return keys_out, vals_out, ctl
+
+
+def tile_ranges_probe(keys, counts, cap, T, V=1, stride=0):
+    """The tile-range search on sorted device keys (tests; include/gsr.h gsr_tile_ranges_probe).  keys: contiguous int32 or int16
+    tensor, V views `stride` bytes apart; counts: int64 tensor [V, k], column 0 = the views' key counts.  Returns int32 [V, T, 2]."""
+    _require_hip(keys.device)
+    if keys.dtype not in (torch.int32, torch.int16) or not keys.is_contiguous():
+        raise RuntimeError("tile_ranges_probe: keys are a contiguous int32 or int16 tensor")
+    if keys.numel() < ((V - 1) * int(stride)) // keys.element_size() + int(cap):
+        raise RuntimeError("tile_ranges_probe: keys shorter than V views of cap elements")
+    if counts.dtype != torch.int64 or counts.dim() != 2 or counts.shape[0] != V or not counts.is_contiguous():
+        raise RuntimeError("tile_ranges_probe: counts are a contiguous int64 tensor [V, k]")
+    ranges = torch.full((V, max(1, int(T)), 2), -1, dtype=torch.int32, device=keys.device)
+    with torch.cuda.device(keys.device):
+        _check(lib.gsr_tile_ranges_probe(keys.data_ptr() if keys.numel() else None, int(stride), counts.data_ptr(), counts.shape[1] * 8,
+                                         V, int(cap), int(T), int(keys.dtype == torch.int16), ranges.data_ptr(),
+                                         _stream_handle(keys.device)))
+    return ranges
 
 
 def set_backward_moments(mode):

@@ -329,6 +329,31 @@ int gsr_wall_clock_khz(void);
  * Allocates its own small buffers; not part of the hot path.  0 = pass. */
 int gsr_selftest(gsr_stream_t stream);
 
+/* Test probes of the pair-list machinery (tests only; they allocate, synchronise and are not part of the hot path).
+ *
+ * gsr_sort_probe runs the library's stable radix sort on bits [0, end_bit) of V independent problems of DEVICE arrays: view v's keys
+ * (uint32_t, or uint16_t with GSR_SORT_KEY16), values and outputs start v * stride bytes behind the view-0 pointers.  vals NULL: the
+ * value of element i is i.  n_dev NULL: every view holds cap elements; else view v holds min(*(n_dev + v * n_stride bytes), cap).
+ * The inputs are copied into work buffers of the call and never modified.  keys_out / vals_out receive cap elements per view from
+ * the ping-pong buffer the sort's own rule names; only the first min(count, cap) mean anything.  Key bits at and above end_bit do
+ * not take part in the order and come back intact.
+ * GSR_SORT_SMALL_BLOCKS: the half-size sort blocks (uint32_t keys, end_bit a multiple of 8).  GSR_SORT_DEPTH_CTL: the depth sort's
+ * control words (32 bits of uint32_t keys, index values): keys equal to 0xFFFFFFFF are culled entries whose place is immaterial, the
+ * passes above the visible keys' span are skipped, and ctl_out (device, uint32 [V][4]) receives per view: key base, key bits compared,
+ * passes run, 0 -- view v's result is read from buffer (passes run & 1).  A combination the sort has no kernel for is refused with
+ * GSR_ERR_INVALID before any device call, never replaced by another kernel.  cap == 0: OK, nothing is touched. */
+#define GSR_SORT_KEY16 1
+#define GSR_SORT_SMALL_BLOCKS 2
+#define GSR_SORT_DEPTH_CTL 4
+int gsr_sort_probe(const void* keys, const uint32_t* vals, size_t stride, const uint64_t* n_dev, size_t n_stride, int V, int64_t cap,
+                   int end_bit, int flags, void* keys_out, uint32_t* vals_out, uint32_t* ctl_out, gsr_stream_t stream);
+
+/* gsr_tile_ranges_probe runs the tile-range search on V views of sorted DEVICE keys (tile ids < T; uint16_t when key16): view v has
+ * min(*(n_dev + v * n_stride bytes), cap) keys at keys + v * stride bytes.  ranges (device, uint32 [V][T][2]) receives (first, one
+ * past last) list position per tile, (0, 0) for a tile without keys.  Every tile is written.  The call waits for the kernel. */
+int gsr_tile_ranges_probe(const void* keys, size_t stride, const uint64_t* n_dev, size_t n_stride, int V, int64_t cap, int T, int key16,
+                          uint32_t* ranges, gsr_stream_t stream);
+
 /* Number of device->host read-backs the library has made in this process: exactly one per forward call -- the 32-byte
  * per-view counter block (num_rendered, trap and stall flags), which the pair-emission kernel stores into mapped host
  * memory and the host reads after ONE event wait, once the whole frame is enqueued -- and none per backward.  There is no

@@ -123,6 +123,48 @@ def test_c_abi_rejects_bad_arguments_without_a_gpu():
     assert N.lib.gsr_mark_visible(0, None, None, None, None, None) == 0
 
 
+def test_probes_reject_bad_arguments_without_a_gpu():
+    """The sort and tile-range probes refuse what the sort has no kernel for before any HIP call (the pointers are never followed)."""
+    from diff_gaussian_rasterization import _native as N
+    K16, SMALL, DEPTH = N.SORT_KEY16, N.SORT_SMALL_BLOCKS, N.SORT_DEPTH_CTL
+    A, B, Cc, D = 0x1000, 0x2000, 0x3000, 0x4000   # stand-ins for device arrays
+
+    def sort(keys=A, vals=None, stride=0, n_dev=None, n_stride=0, V=1, cap=100, end_bit=32, flags=0, kout=B, vout=Cc, ctl=None):
+        rc = N.lib.gsr_sort_probe(keys, vals, stride, n_dev, n_stride, V, cap, end_bit, flags, kout, vout, ctl, None)
+        return rc, N.lib.gsr_last_error()
+
+    for kw, msg in (
+            (dict(keys=None), b"NULL"), (dict(kout=None), b"NULL"), (dict(vout=None), b"NULL"),
+            (dict(V=0), b"view count"), (dict(V=-3), b"view count"), (dict(cap=-1), b"capacity"),
+            (dict(end_bit=0), b"end_bit"), (dict(end_bit=33), b"end_bit"), (dict(end_bit=-8), b"end_bit"),
+            (dict(flags=K16, end_bit=17), b"16-bit keys"), (dict(flags=K16, end_bit=32), b"16-bit keys"),
+            (dict(flags=DEPTH, end_bit=24, ctl=D), b"depth control"), (dict(flags=DEPTH | K16, end_bit=16, ctl=D), b"depth control"),
+            (dict(flags=DEPTH, vals=D, ctl=D), b"depth control"), (dict(flags=DEPTH), b"ctl_out"),
+            (dict(flags=SMALL | K16, end_bit=16), b"small blocks"), (dict(flags=SMALL, end_bit=13), b"small blocks"),
+            (dict(flags=SMALL, end_bit=12), b"small blocks"), (dict(flags=SMALL | DEPTH, end_bit=31, ctl=D), b"depth control"),
+            (dict(flags=8), b"unknown flags"),
+            (dict(V=2, stride=0), b"view stride"), (dict(V=2, stride=300), b"view stride"), (dict(V=2, stride=256), b"view stride"),
+            (dict(V=2, stride=512, n_dev=D, n_stride=0), b"count stride"), (dict(V=2, stride=512, n_dev=D, n_stride=12), b"count stride")):
+        rc, err = sort(**kw)
+        assert rc == -1 and msg in err, (kw, err)
+    # cap == 0: nothing to sort, nothing touched -- with every combination a kernel exists for
+    for kw in (dict(), dict(flags=K16, end_bit=16), dict(flags=SMALL, end_bit=24), dict(flags=DEPTH, ctl=D), dict(flags=DEPTH | SMALL, ctl=D),
+               dict(V=4, stride=256, n_dev=D, n_stride=64), dict(vals=D, end_bit=1)):
+        assert sort(cap=0, **kw)[0] == 0, kw
+    assert sort(cap=0, keys=None)[0] == -1 and sort(cap=0, flags=SMALL, end_bit=20)[0] == -1   # (still refused when empty)
+
+    def ranges(keys=A, stride=0, n_dev=B, n_stride=0, V=1, cap=100, T=10, key16=0, out=Cc):
+        rc = N.lib.gsr_tile_ranges_probe(keys, stride, n_dev, n_stride, V, cap, T, key16, out, None)
+        return rc, N.lib.gsr_last_error()
+
+    for kw, msg in ((dict(keys=None), b"NULL"), (dict(n_dev=None), b"NULL"), (dict(out=None), b"NULL"), (dict(V=0), b"view count"),
+                    (dict(cap=-1), b"capacity"), (dict(cap=1 << 32), b"capacity"), (dict(T=0), b"tiles"), (dict(T=-5), b"tiles"),
+                    (dict(T=65537, key16=1), b"tiles"), (dict(V=2, stride=100, n_stride=8), b"view strides"),
+                    (dict(V=2, stride=512, n_stride=0), b"view strides"), (dict(V=2, stride=512, n_stride=4), b"view strides")):
+        rc, err = ranges(**kw)
+        assert rc == -1 and msg in err, (kw, err)
+
+
 def test_forward_batch_rejects_bad_arguments_without_a_gpu():
     from diff_gaussian_rasterization import _native as N
     p = N.GsrParams()
