@@ -240,6 +240,9 @@ struct FrameRecord {
                                  // -1: unknown, a recolor on an arena without a record)
     int64_t list_pairs = -1;     // largest per-view pair count of that forward's lists (a recolor carries it on; -1: unknown): what the
                                  // scratch of a deterministic backward has to hold slots for
+    int math = 0;                // arithmetic of the call that last wrote the colour saves (0 exact, 1 fast): the forward, or a recolor --
+                                 // it rewrites final_T and n_contrib of every pixel and, through the same kernel, every slice-boundary
+                                 // state and accumulated colour a backward reads.  The render backward runs the same mode.
     FrameRecord() = default;
     FrameRecord(int kind_, const gsr_params* p, int V_) : kind(kind_), need_backward(p->need_backward != 0), V(V_), P(p->P), W(p->W), H(p->H) {}
 };
@@ -301,9 +304,11 @@ static int forward_impl(const gsr_params* p, int V, void* geom, size_t geom_byte
         if (!p->need_backward) Xs.state = XStateView{nullptr, nullptr, 0};
         X = &Xs;
     }
+    const bool fast = forward_fast_math(p->need_backward != 0, X != nullptr && X->nx > 0);
     {
         FrameRecord r(X ? 1 : 0, p, V);
         r.fwd_need_backward = r.need_backward;
+        r.math = fast ? 1 : 0;
         if (X) {
             r.nx = X->nx;
             r.layout = X->values_hi ? 2 : X->view_stride ? 1 : 0;
@@ -378,7 +383,7 @@ static int forward_impl(const gsr_params* p, int V, void* geom, size_t geom_byte
             }
             {
                 ProfScope ps("render_forward", L.stream);
-                if (int e = launch_render_forward(L, *p, B, B.b.val[res], out_color, p->need_backward != 0, X)) return e;
+                if (int e = launch_render_forward(L, *p, B, B.b.val[res], out_color, p->need_backward != 0, fast, X)) return e;
             }
         }
         return GSR_OK;
@@ -523,10 +528,12 @@ int gsr_forward_recolor(const gsr_params* p, int V, int colors_per_view, void* g
     if (!out_color || !p->bg || !binning) return fail(GSR_ERR_INVALID, "[gsr] recolor: NULL pointer");
     Batch B;
     if (int e = make_batch(p, V, geom, geom_bytes, image, image_bytes, const_cast<void*>(binning), binning_bytes, false, B)) return e;
+    const bool fast = forward_fast_math(p->need_backward != 0, false);
     {
         // a need_backward recolor rewrites the colour saves only: the gradient records and the SH clamp mask of the other Gaussians
         // exist (and were cleared) only if the forward under it had need_backward too
         FrameRecord prev, r(2, p, V);
+        r.math = fast ? 1 : 0;
         if (find_frame(geom, prev)) {   // (no record: both stay -1, unknown)
             r.fwd_need_backward = prev.fwd_need_backward;
             r.list_pairs = prev.list_pairs;
@@ -545,7 +552,7 @@ int gsr_forward_recolor(const gsr_params* p, int V, int colors_per_view, void* g
         ProfScope ps("render_forward", L.stream);
         // need_backward: the slice-boundary state and the accumulated colour are rewritten for the new colours (and k_recolor
         // refreshed the SH clamp mask), so a backward afterwards differentiates this render
-        if (int e = launch_render_forward(L, *p, B, B.b.val[res], out_color, p->need_backward != 0)) return e;
+        if (int e = launch_render_forward(L, *p, B, B.b.val[res], out_color, p->need_backward != 0, fast)) return e;
     }
     return GSR_OK;
 }
@@ -597,15 +604,18 @@ static int check_bwd_pointers(const gsr_params* p, const int* radii, const void*
 // Colour backward (x == NULL): without a record (an arena whose forward ran before the record table was last dropped, at more than
 // 4096 arenas) the call goes ahead as it always did: refusing it would break a valid backward, and the caller's contract (gsr.h) is
 // unchanged.  Channels backward: the record has to be that of a channels forward with need_backward = 1 into this extra-state
-// block, with the same channels, layout and sizes.  list_pairs: the record's (-1: none).
-static int check_bwd_frame(const void* geom, const gsr_params* p, int V, const BwdExtra* x, int64_t* list_pairs)
+// block, with the same channels, layout and sizes.  list_pairs: the record's (-1: none).  math: the arithmetic the saves were written
+// in, from the record; without one, the training switch in force (the caller then has to keep it where the forward had it).
+static int check_bwd_frame(const void* geom, const gsr_params* p, int V, const BwdExtra* x, int64_t* list_pairs, int* math)
 {
     FrameRecord r;
     *list_pairs = -1;
+    *math = x ? 0 : train_math(-1);
     if (!find_frame(geom, r))
         return x ? fail(GSR_ERR_INVALID, "[gsr] backward_channels: no forward on this geometry arena (run gsr_forward_batch_channels_train first)")
                  : GSR_OK;
     *list_pairs = r.list_pairs;
+    *math = r.math;
     const bool same = r.V == V && r.P == p->P && r.W == p->W && r.H == p->H;
     if (x) {
         if (r.kind == 2)
@@ -647,7 +657,8 @@ static int backward_impl(const gsr_params* p, int V, const int* radii, const voi
     int64_t list_pairs = -1;
     if (!x)
         if (int e = check_bwd_pointers(p, radii, binning, G)) return e;
-    if (int e = check_bwd_frame(geom, p, V, x, &list_pairs)) return e;
+    int math = 0;
+    if (int e = check_bwd_frame(geom, p, V, x, &list_pairs, &math)) return e;
     if (x)
         if (int e = check_bwd_pointers(p, radii, binning, G)) return e;
     Batch B;
@@ -708,7 +719,7 @@ static int backward_impl(const gsr_params* p, int V, const int* radii, const voi
         // (storing channels kernels: the extras' sums go to the scratch block's slots, not to the caller's output)
         const ExtraGrads xg_slots{x ? x->XG.dL_dextra : nullptr, S.xpart, nullptr};
         if (int e = launch_render_backward(L, *p, B, B.b.val[res], G.dL_dpix, x ? &x->X : nullptr, !x ? nullptr : det ? &xg_slots : &x->XG,
-                                           det ? &d : nullptr))
+                                           det ? &d : nullptr, !x && math == 1))
             return e;
     }
     if (det) {
@@ -1107,6 +1118,7 @@ long long gsr_d2h_count(void) { return gsr::g_d2h_count.load(); }
 int gsr_set_forward_half_views(int views) { return gsr::forward_half_views(views); }
 int gsr_set_backward_moments(int mode) { return gsr::backward_subquadrant_moments(mode); }
 int gsr_set_render_math(int mode) { return gsr::render_math(mode); }
+int gsr_set_train_math(int mode) { return gsr::train_math(mode); }
 
 int gsr_last_list_pairs(int64_t* out, int V)
 {

@@ -471,15 +471,22 @@ struct ExtraGrads {
     float* grad;              // like values: [P][nx] / [V][P][nx] (view_stride) / split: [P][4] ...
     float* grad_hi;           // ... and [V][P][4] (hi_view_stride)
 };
+// fast: the RenderFast kernels (render_math.hpp); the caller decides with forward_fast_math and, for a with_ckpt call, notes it in the
+// arena's record, because the backward has to run the same arithmetic
 int launch_render_forward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, float* out_color,
-                          bool with_ckpt, const ExtraChannels* X = nullptr);
+                          bool with_ckpt, bool fast, const ExtraChannels* X = nullptr);
 // D != NULL: the storing instantiations -- partial sums go to D's slots instead of into the gradient records; with extra channels
 // XG->grad is then view 0's extra slots (DetScratch::xpart, D->stride bytes per view) and XG->grad_hi is not used
 int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, const float* dL_dpix,
-                           const ExtraChannels* X = nullptr, const ExtraGrads* XG = nullptr, const RenderBwdDet* D = nullptr);
+                           const ExtraChannels* X = nullptr, const ExtraGrads* XG = nullptr, const RenderBwdDet* D = nullptr,
+                           bool fast = false);   // fast: the RenderBwdFast colour kernels (X == NULL only), for saves of a fast forward
 int backward_subquadrant_moments(int set);   // render_bwd.hip: set >= 0 stores; 1 = moments about the sub-quadrant centres
 int forward_half_views(int set);   // render_fwd.hip: set >= 0 stores; returns the views per submission up to which the half-quadrant forward runs
 int render_math(int set);           // render_fwd.hip: 0 / 1 stores, < 0 queries, > 1 is refused; returns the arithmetic mode of the inference forwards (0 exact, 1 fast)
+int train_math(int set);            // render_fwd.hip: the same for the colour forwards that save for a backward (need_backward = 1)
+// which arithmetic a render forward runs: the inference switch without saves, the training switch with them; a channels forward that
+// saves stays exact (the channels backward has no fast variant)
+bool forward_fast_math(bool with_ckpt, bool channels);
 int selftest_mm(hipStream_t stream, float* d_scratch256);   // the matrix-core pixel contraction of the render backward
 // det_backward.hip: the steps of the deterministic backward around the storing render backward, on the scratch plan S
 int launch_det_prepare(const Launch& L, const Batch& B, const DetScratch& S, const uint32_t* point_list, int T);

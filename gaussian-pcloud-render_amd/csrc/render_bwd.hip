@@ -350,6 +350,21 @@ __device__ __forceinline__ RenderBwdDet bwd_det(const RenderBwdX&, const RenderB
 // entry -- goes to the entry's extra slot xpart[(position * 4 + quadrant) * NX + 4 * channel quad] with ONE 16-B store, zeros
 // included, under exactly the condition the colour flush marks the (position, quadrant) under: a marked slot is whole in both arrays.
 // RenderBwdX::grad is view 0's xpart there (RenderBwdDet::stride bytes per view); grad_hi is not used.
+// The FAST colour kernels of the training arithmetic (gsr_set_train_math; render_math.hpp), k_render_backward<MODE, 0, RenderBwdFast>
+// (atomic flush) and k_render_backward<MODE, 0, RenderBwdDet, RenderBwdFast> (storing flush): the backward of a forward that ran the
+// RenderFast kernels.  The staging lane folds the conic exactly as that forward's does (after the footprint test and the MODE 2
+// far-splat compare, which read the unfolded record from registers), the pixels evaluate p2, G = 2^p2 and alpha with the forward's own
+// functions, so the hit decisions are the ones that wrote n_contrib, and the flush unfolds the two conic terms it shifts the moments
+// with.  Everything else -- T / (1 - alpha), the recurrences, the contraction, both flushes -- is the one text.  Again the switch is
+// the TYPE of a trailing kernel argument; there is no fast channels kernel.
+struct RenderBwdFast {
+    uint32_t mode;   // 1 (never read: the type is the switch)
+};
+__device__ __forceinline__ RenderBwdX bwd_x(const RenderBwdFast&) { return RenderBwdX{}; }
+__device__ __forceinline__ RenderBwdDet bwd_det(const RenderBwdFast&) { return RenderBwdDet{}; }
+__device__ __forceinline__ RenderBwdX bwd_x(const RenderBwdDet&, const RenderBwdFast&) { return RenderBwdX{}; }
+__device__ __forceinline__ RenderBwdDet bwd_det(const RenderBwdDet& d, const RenderBwdFast&) { return d; }
+template <typename... XS> constexpr bool bwd_is_fast = (std::is_same<XS, RenderBwdFast>::value || ...);
 template <typename... XS> constexpr bool bwd_is_det = (std::is_same<XS, RenderBwdDet>::value || ...);
 // (the storing channels kernels: with four channels the slot addressing fits the channels kernel's three waves per SIMD; with eight
 // it spilled inside the flush there, so those three instantiations take two waves per SIMD and stay free of scratch)
@@ -363,7 +378,9 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
     RenderBwdDet det{};
     if constexpr (DET) det = bwd_det(xs...);
     constexpr bool SUBQ = MODE == 1;
+    constexpr bool FAST = bwd_is_fast<XS...>;
     static_assert(NX == 0 || NX == 4 || NX == 8, "extra channels come in quads");
+    static_assert(!FAST || NX == 0, "the channels backward has no fast variant");
     // Work items are (tile, chunk of BWD_CHUNK consumed list entries), one quadrant per wave; which ones a workgroup takes: see the
     // item loop.  XCD-aware either way: workgroup b runs on XCD b % 8 (each XCD has its own L2) and the four quadrant waves of an item
     // run on one XCD at about the same time, so the item's list slice and Splat records are fetched into that L2 once instead of
@@ -425,7 +442,9 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
     const uint32_t mm_cA = mm_g < 3u ? (mm_j < 4u ? 2u + mm_g : mm_c2) : (mm_j >= 12u ? 6u : mm_j >= 8u ? 5u : 7u);
     const uint32_t mm_cB = mm_g < 3u ? (mm_j < 4u ? mm_c2 : 2u + mm_g) : (mm_j >= 12u ? 5u : mm_j >= 8u ? 6u : 7u);
     const uint32_t mm_offP = mm_g == 0 ? 8u : 12u, mm_offQ = mm_g == 0 ? 12u : 16u;   // conic A|B resp. B|C
-    const float mm_dd = -(mm_g == 0 ? (float)(0.5 * a.W) : (float)(0.5 * a.H));
+    // (fast kernels: times -ln 2, the rounded factor of the conic's unfolding, render_math.hpp)
+    const float mm_dd = FAST ? unfold_scale(-(mm_g == 0 ? (float)(0.5 * a.W) : (float)(0.5 * a.H)))
+                             : -(mm_g == 0 ? (float)(0.5 * a.W) : (float)(0.5 * a.H));
     WALK_T(tw0);
     WALK_STAT(unsigned long long tw_wait = 0, tw_setup = 0, tw_stage = 0, tw_eval = 0, n_groups = 0, n_items_done = 0;)
   // Which items a workgroup takes.  STATIC (a.dynamic == 0; the launch has a quartet of workgroups per eight items or more): quartet
@@ -626,12 +645,19 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
             if constexpr (DET) { if (lane < 4) stage[((nsurv - 1) >> 2) * QUAD_WORDS + 40 + lane] = __builtin_bit_cast(float, 0xFFFFFFFFu); }
             if (touch) {
                 float* p = stage + (slot >> 2) * QUAD_WORDS + (slot & 3u);
+                if constexpr (FAST) {
+                    p[0] = c0.x; p[4] = c0.y; p[20] = c1.y;
+                } else {
                 p[0] = c0.x; p[4] = c0.y; p[8] = c0.z; p[12] = c0.w; p[16] = c1.x; p[20] = c1.y;
+                }
                 uint32_t id_st = id_cur;
                 if constexpr (MODE == 2) {
                     const float bx = c0.x - mm_sx, by = c0.y - mm_sy;
                     const float mq = (c0.z * bx) * bx + 2.f * (c0.w * bx) * by + (c1.x * by) * by;
                     id_st |= mq > SUBQ_M ? 0x80000000u : 0u;
+                }
+                if constexpr (FAST) {   // the fast forward's fold, once per surviving entry, after the compare that reads the unfolded record
+                    p[8] = fold_square_term(c0.z); p[12] = fold_cross_term(c0.w); p[16] = fold_square_term(c1.x);
                 }
                 p[24] = c1.z; p[28] = c1.w; p[32] = c2b; p[36] = __builtin_bit_cast(float, id_st);
                 if constexpr (DET) p[40] = __builtin_bit_cast(float, (uint32_t)f_lane);
@@ -697,12 +723,23 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
                 const f32x2 X = {ex[k], ex[k + 1]}, Y = {ey[k], ey[k + 1]}, A2 = {eA[k], eA[k + 1]};
                 const f32x2 B2 = {eB[k], eB[k + 1]}, C2 = {eC[k], eC[k + 1]}, O2 = {eo[k], eo[k + 1]};
                 const f32x2 dx = X - pixf_x, dy = Y - pixf_y;
-                const f32x2 power = -0.5f * (A2 * dx * dx + C2 * dy * dy) - B2 * dx * dy;
-                const f32x2 G = exp_nonpos2(power);
-                const f32x2 al = O2 * G;
-                Gs[k] = G.x; Gs[k + 1] = G.y;
-                alphas[k] = fminf(0.99f, al.x);
-                alphas[k + 1] = fminf(0.99f, al.y);
+                // (fast kernels: A2, B2, C2 are the conic folded at staging and `power` is p2 = power log2 e, of the same sign)
+                f32x2 power;
+                if constexpr (FAST) {
+                    f32x2 G;
+                    power = power2_fast(A2, B2, C2, dx, dy);
+                    const f32x2 al = alpha_fast_g2(O2, power, G);
+                    Gs[k] = G.x; Gs[k + 1] = G.y;
+                    alphas[k] = al.x;
+                    alphas[k + 1] = al.y;
+                } else {
+                    power = -0.5f * (A2 * dx * dx + C2 * dy * dy) - B2 * dx * dy;
+                    const f32x2 G = exp_nonpos2(power);
+                    const f32x2 al = O2 * G;
+                    Gs[k] = G.x; Gs[k + 1] = G.y;
+                    alphas[k] = fminf(0.99f, al.x);
+                    alphas[k + 1] = fminf(0.99f, al.y);
+                }
                 hits[k] = (ef[k] < last_contributor) && !(power.x > 0.0f) && !(alphas[k] < 1.0f / 255.0f);
                 hits[k + 1] = (ef[k + 1] < last_contributor) && !(power.y > 0.0f) && !(alphas[k + 1] < 1.0f / 255.0f);
                 any_lane_hit = any_lane_hit || hits[k] || hits[k + 1];
@@ -780,7 +817,13 @@ __global__ __launch_bounds__(64) void k_render_backward(RenderBwdArgs a, XS... x
             // per-entry constants and targets first: their LDS round trips pass while the matrix pipe works
             const uint32_t gq1 = (uint32_t)(quad > 0 ? quad - 1 : 0);   // the batch's second group, if it has one, was evaluated just now
             const float* e = stage + (mm_gb ? gq1 : gq0) * QUAD_WORDS + mm_k4;
-            const float eX = e[0], eY = e[4], cP = e[mm_offP], cQ = e[mm_offQ], cO = e[20];
+            const float eX = e[0], eY = e[4];
+            float cP = e[mm_offP], cQ = e[mm_offQ];
+            const float cO = e[20];
+            if constexpr (FAST) {   // the staged rows hold the folded conic, A' | B' for mean2D.x, B' | C' for mean2D.y; -ln 2 is in mm_dd
+                cP = mm_g == 0 ? unfold_twice(cP) : cP;
+                cQ = mm_g == 0 ? cQ : unfold_twice(cQ);
+            }
             uint32_t idA = __builtin_bit_cast(uint32_t, stage[gq0 * QUAD_WORDS + 36u + mm_k4]);
             uint32_t idB = __builtin_bit_cast(uint32_t, stage[gq1 * QUAD_WORDS + 36u + mm_k4]);
             uint32_t posA = 0, posB = 0;   // storing flush: list positions of this lane's entries (0xFFFFFFFF: no entry)
@@ -959,7 +1002,7 @@ static void launch_bwd_kernel(dim3 grid, hipStream_t stream, const RenderBwdArgs
 }
 
 int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, const float* dL_dpix,
-                           const ExtraChannels* X, const ExtraGrads* XG, const RenderBwdDet* D)
+                           const ExtraChannels* X, const ExtraGrads* XG, const RenderBwdDet* D, bool fast)
 {
     RenderBwdArgs a;
     a.ranges = B.iv.ranges;
@@ -1002,11 +1045,16 @@ int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B,
         else launch_bwd_kernel<8>(grid, L.stream, a, x);
         return check_launch(L, "render_backward_channels");
     }
+    // fast: the arenas' saves were written by the fast forward kernels (api.hip: the arena's record says so), and only a backward that
+    // takes that forward's decisions fits them
+    const RenderBwdFast F{1u};
     if (D != nullptr) {
-        launch_bwd_kernel<0>(grid, L.stream, a, *D);
+        if (fast) launch_bwd_kernel<0>(grid, L.stream, a, *D, F);
+        else launch_bwd_kernel<0>(grid, L.stream, a, *D);
         return check_launch(L, "render_backward_det");
     }
-    launch_bwd_kernel<0>(grid, L.stream, a);
+    if (fast) launch_bwd_kernel<0>(grid, L.stream, a, F);
+    else launch_bwd_kernel<0>(grid, L.stream, a);
     return check_launch(L, "render_backward");
 }
 

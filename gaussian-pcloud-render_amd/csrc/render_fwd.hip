@@ -583,8 +583,30 @@ int render_math(int set)
     return v;
 }
 
+// arithmetic of the colour forwards that DO save for a backward (need_backward = 1; the backward then runs the matching fast kernels,
+// render_bwd.hip RenderBwdFast): GSR_TRAIN_MATH in the environment when the library is first used (0 exact, the default; 1 fast), or
+// gsr_set_train_math().  Same convention as render_math; neither switch moves the other.
+static std::atomic<int> g_train_math{-1};
+int train_math(int set)
+{
+    if (set == 0 || set == 1) g_train_math.store(set);
+    int v = g_train_math.load();
+    if (v < 0) {
+        const char* e = getenv("GSR_TRAIN_MATH");
+        v = (e && atoi(e) == 1) ? 1 : 0;
+        g_train_math.store(v);
+    }
+    return v;
+}
+
+bool forward_fast_math(bool with_ckpt, bool channels)
+{
+    if (!with_ckpt) return render_math(-1) == 1;
+    return !channels && train_math(-1) == 1;
+}
+
 int launch_render_forward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, float* out_color,
-                          bool with_ckpt, const ExtraChannels* X)
+                          bool with_ckpt, bool fast, const ExtraChannels* X)
 {
     RenderArgs a;
     a.ranges = B.iv.ranges;
@@ -605,9 +627,9 @@ int launch_render_forward(const Launch& L, const gsr_params& p, const Batch& B, 
     a.extra_hi = nullptr; a.extra_hi_vstride = 0;
     a.xckpt = nullptr; a.xaccum = nullptr; a.x_stride = 0;
     const dim3 grid((unsigned)div_up(T, 8) * 32u * (unsigned)B.V);
-    // a permission, not a demand: a forward that saves for a backward runs the exact kernels whatever the switch says (the backward
-    // re-evaluates alpha in exact arithmetic against this forward's T, C and n_contrib)
-    const bool fast = !with_ckpt && render_math(-1) == 1;
+    // `fast` is forward_fast_math's answer: the inference switch for a forward that saves nothing, the training switch for a colour
+    // forward that does (the fast kernels carry the checkpoint stores like the exact ones; the backward re-evaluates alpha in the
+    // arithmetic of the forward that wrote T, C and n_contrib)
     const RenderFast F{1u};
     if (X != nullptr && X->nx > 0) {
         a.extra = X->values; a.extra_scale = X->view_scale; a.bg_extra = X->bg; a.out_extra = X->out; a.extra_vstride = X->view_stride;

@@ -1,9 +1,10 @@
-// render_math.hpp -- the per-(pixel, entry) arithmetic of the forward render kernels, in its two modes (gsr_set_render_math):
+// render_math.hpp -- the per-(pixel, entry) arithmetic of the render kernels, in its two modes (gsr_set_render_math for forwards that
+// save nothing; gsr_set_train_math for forwards that save for a backward, and for the render backward that follows them):
 //
 //   exact (0, the default)   the reference's operations one rounding at a time: power = -0.5 (A dx^2 + C dy^2) - B dx dy,
 //                            alpha = min(0.99, o exp(power)) with the bit-exact exp of exp_nonpos, C += (c alpha) T.  Images equal a
 //                            strict-order build of the reference bit for bit.
-//   fast (1, inference only) the same quantities in fewer instructions, every fusion written out (no contraction pragma, the build
+//   fast (1, opt-in)         the same quantities in fewer instructions, every fusion written out (no contraction pragma, the build
 //                            stays -ffp-contract=off): the staging lane folds -0.5 log2(e) / -log2(e) into the conic once per entry,
 //                            the pixels evaluate p2 = power log2(e) with two multiplies and two fused multiply-adds, alpha =
 //                            min(0.99, o 2^p2) with the hardware's v_exp_f32 and no range reduction, and the blend is w = alpha T once
@@ -105,6 +106,35 @@ GSR_HD V power2_fast(V Ap, V Bp, V Cp, V dx, V dy)
 // alpha = min(0.99, o 2^p2): one v_exp_f32, no range reduction, no ldexp (p2 <= 0 for every entry that counts; a result below 2^-126
 // is flushed to 0 and is six orders of magnitude under the 1/255 cut either way)
 GSR_HD float alpha_fast(float o, float p2) { return __builtin_fminf(0.99f, o * rm_exp2(p2)); }
+
+// The fast render backward (render_bwd.hip RenderBwdFast) needs G = 2^p2 on its own, for the G dL/dalpha weight, beside the alpha:
+// the same two operations as alpha_fast with the exponential handed out, so alpha, G and the hit decision are the fast forward's bit
+// for bit (tests/train_math_main.cpp pins it to alpha_fast).
+GSR_HD float alpha_fast_g(float o, float p2, float& G)
+{
+    G = rm_exp2(p2);
+    return __builtin_fminf(0.99f, o * G);
+}
+#if defined(__clang__)
+// two entries: the product is one packed multiply, rounding per component that of alpha_fast_g
+GSR_HD f32x2 alpha_fast_g2(f32x2 o, f32x2 p2, f32x2& G)
+{
+    G = f32x2{rm_exp2(p2.x), rm_exp2(p2.y)};
+    const f32x2 al = o * G;
+    return f32x2{__builtin_fminf(0.99f, al.x), __builtin_fminf(0.99f, al.y)};
+}
+#endif
+
+// The backward's flush shifts the moments to the splat centre with the UNFOLDED conic, and its staged rows hold the folded one (no
+// spare row for a second copy): A = (2 A') (-ln 2), B = B' (-ln 2) -- the doubling is exact, and the kernel applies the one rounded
+// factor -ln 2 to the per-lane constant that multiplies A Dx + B Dy (resp. B Dx + C Dy) anyway, so unfolding costs an add and a select
+// per lane and batch of eight entries.  unfold(fold(x)) is x within four roundings of 2^-24 (two products, two rounded constants); it
+// enters gradients held to tolerance only.
+constexpr float RM_NEG_LN2 = -0x1.62e43p-1f;
+GSR_HD float unfold_twice(float ACp) { return ACp + ACp; }             // A' and C': the part of their unfolding that is exact
+GSR_HD float unfold_scale(float v) { return v * RM_NEG_LN2; }         // the common factor
+GSR_HD float unfold_square_term(float ACp) { return unfold_scale(unfold_twice(ACp)); }
+GSR_HD float unfold_cross_term(float Bp) { return unfold_scale(Bp); }
 
 // C += c w with w = alpha T formed once per entry: one fused multiply-add per channel (packed for a channel pair)
 template <typename V>

@@ -23,6 +23,7 @@ from . import _native as _C
 from ._native import get_deterministic, set_deterministic  # noqa: F401  (the deterministic-backward switch)
 from ._native import get_deterministic_channels, set_deterministic_channels  # noqa: F401  (the deterministic channels backward's own switch)
 from ._native import get_render_math, set_render_math  # noqa: F401  (arithmetic mode of the inference forwards)
+from ._native import get_train_math, set_train_math  # noqa: F401  (arithmetic mode of the training forwards and their backward)
 
 
 def cpu_deep_copy_tuple(input_tuple):

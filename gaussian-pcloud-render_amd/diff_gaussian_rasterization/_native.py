@@ -69,6 +69,7 @@ _DECL = {
     "gsr_set_forward_half_views": (_int, [_int]),
     "gsr_set_backward_moments": (_int, [_int]),
     "gsr_set_render_math": (_int, [_int]),
+    "gsr_set_train_math": (_int, [_int]),
     "gsr_get_profile": (_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _int]),
     "gsr_selftest": (_int, [_fp]),
     "gsr_sort_probe": (_int, [_fp, _fp, _size, _fp, _size, _int, _i64, _int, _int, _fp, _fp, _fp, _fp]),
@@ -1028,26 +1029,44 @@ def set_backward_moments(mode):
 _RENDER_MATH = {"exact": 0, "fast": 1}
 
 
+def _math_mode(mode, what):
+    if isinstance(mode, str):
+        if mode not in _RENDER_MATH:
+            raise ValueError("%s is 'exact' or 'fast' (0 or 1), not %r" % (what, mode))
+        return _RENDER_MATH[mode]
+    m = int(mode)
+    if isinstance(mode, bool) or m not in (0, 1):
+        raise ValueError("%s is 'exact' or 'fast' (0 or 1), not %r" % (what, mode))
+    return m
+
+
 def set_render_math(mode):
     """Arithmetic of the inference forwards (need_backward = False): "exact" / 0 (default) bit-identical to the reference build,
     "fast" / 1 fewer instructions per (pixel, entry), within the 1e-4 contract of the exact mode except at threshold decisions,
     deterministic, not bit-identical to the reference; training forwards ignore it (include/gsr.h gsr_set_render_math,
     GSR_RENDER_MATH).  Process-wide.  Returns the name of the mode in force."""
-    if isinstance(mode, str):
-        if mode not in _RENDER_MATH:
-            raise ValueError("render math is 'exact' or 'fast' (0 or 1), not %r" % (mode,))
-        m = _RENDER_MATH[mode]
-    else:
-        m = int(mode)
-        if isinstance(mode, bool) or m not in (0, 1):
-            raise ValueError("render math is 'exact' or 'fast' (0 or 1), not %r" % (mode,))
-    lib.gsr_set_render_math(m)
+    lib.gsr_set_render_math(_math_mode(mode, "render math"))
     return get_render_math()
 
 
 def get_render_math():
     """"exact" or "fast": the arithmetic mode of the inference forwards in force"""
     return "fast" if int(lib.gsr_set_render_math(-1)) == 1 else "exact"
+
+
+def set_train_math(mode):
+    """Arithmetic of training calls (need_backward = True): "exact" / 0 (default), or "fast" / 1: the colour forwards run the fast
+    kernels of set_render_math("fast") and save from them, and the render backward that follows re-evaluates alpha with the same
+    functions -- it follows the forward that wrote the saves, not the switch at backward time.  Deterministic with itself, images
+    and gradients within the contract, not bit-identical to the reference; the extra-channel passes stay exact (include/gsr.h
+    gsr_set_train_math, GSR_TRAIN_MATH).  Independent of set_render_math.  Process-wide.  Returns the name of the mode in force."""
+    lib.gsr_set_train_math(_math_mode(mode, "train math"))
+    return get_train_math()
+
+
+def get_train_math():
+    """"exact" or "fast": the arithmetic mode of the training calls in force"""
+    return "fast" if int(lib.gsr_set_train_math(-1)) == 1 else "exact"
 
 
 def set_profiling(on):

@@ -204,8 +204,8 @@ int gsr_backward_batch(const gsr_params* p, int V, const int* radii, const void*
 /* Deterministic colour backward (opt-in; replaces rasterize_points.cu:117-196 like gsr_backward_batch, and with it the reference's own
  * float atomics, backward.cu:523-554, whose order of arrival makes its gradients differ in their last bits from run to run; the
  * reference has no repeatable path).  gsr_backward_batch's arguments, outputs and refusals, plus a caller-owned scratch block.
- * For the same inputs, the same call shape (V, image size, moments mode, reference_lists), the same library build and the same
- * device model, every gradient is BIT-IDENTICAL from call to call and from process to process: whichever workgroup takes which work
+ * For the same inputs, the same call shape (V, image size, moments mode, reference_lists), the same arithmetic mode (gsr_set_train_math:
+ * that of the forward or recolor that wrote the saves), the same library build and the same device model, every gradient is BIT-IDENTICAL from call to call and from process to process: whichever workgroup takes which work
  * unit, whatever runs beside it.  It is NOT promised across different V (the list slices and their start states differ), builds or
  * device models.  The values are those of gsr_backward_batch up to the order of float additions: the same partial sums per (list
  * entry, 8 x 8 quadrant), stored into slots of their own instead of added with atomics, then added per Gaussian in a fixed order --
@@ -387,9 +387,32 @@ int gsr_set_backward_moments(int mode);
  * as shipped, compiled with FMA contraction, differs from its strict build in the same way).  What it does not promise: bit-identity
  * with any build of the reference.  The mode is a permission, not a demand: it applies to forwards that save nothing for a backward
  * (need_backward = 0: gsr_forward_batch, gsr_forward_batch_channels, gsr_forward_batch_channels_train, gsr_forward_stage2,
- * gsr_forward_recolor); a forward with need_backward = 1 runs the exact kernels whatever the switch says, and every backward is
- * untouched.  mode < 0 only queries; a value above 1 is refused and changes nothing.  Returns the value in force. */
+ * gsr_forward_recolor); a forward with need_backward = 1 does not look at this switch (its arithmetic is gsr_set_train_math's, exact
+ * by default), and no backward does.  mode < 0 only queries; a value above 1 is refused and changes nothing.  Returns the value in
+ * force. */
 int gsr_set_render_math(int mode);
+
+/* Arithmetic of TRAINING calls: the colour forwards that save for a backward, and the render backward that follows them
+ * (GSR_TRAIN_MATH in the environment, read when the library is first used).  0 (DEFAULT) exact, 1 fast; the calling convention is
+ * gsr_set_render_math's (mode < 0 only queries; a value above 1 is refused and changes nothing; returns the value in force).  The two
+ * switches are independent: neither setter changes the other's value, and a call looks at exactly one of them.
+ *   Forwards.  With need_backward = 1, gsr_forward_batch (both forward kernels), gsr_forward_stage2 and gsr_forward_recolor run the
+ * fast kernels of gsr_set_render_math(1) -- the same images, final_T and n_contrib bit for bit as an inference call in that mode --
+ * and write the saves (slice-boundary states, accumulated colour) from them.  With need_backward = 0 only gsr_set_render_math counts.
+ * gsr_forward_batch_channels_train with need_backward = 1 stays exact under both switches: the channels backward has no fast variant
+ * (gsr_backward_batch_channels and gsr_backward_batch_channels_det are untouched).
+ *   Backwards.  gsr_backward_batch, gsr_backward and gsr_backward_batch_det follow the FORWARD, not the switch: the library's record
+ * of the geometry arena holds the arithmetic of the call that last wrote the saves (the forward, or a need_backward recolor, which
+ * rewrites all of them), and the render backward re-evaluates p2, G = 2^p2, alpha and the three-part hit test with that forward's own
+ * functions, so its decisions are the ones that wrote n_contrib, whatever the switch says at backward time.  An arena without a
+ * record (the table is dropped once it holds more than 4096 arenas) takes the switch in force at the backward: keep it where the
+ * forward had it.
+ *   What the fast mode promises: it is deterministic with itself (gsr_backward_batch_det stays bit-identical from call to call);
+ * radii, num_rendered, lists and ranges are the exact mode's; images lie within the contract's 1e-4 of the exact mode's except at
+ * threshold decisions (see gsr_set_render_math); gradients are those of the image it rendered, as accurate against a float64
+ * evaluation of the same sums as the exact mode's (profiles/r15_train_math.txt).  What it does not promise: bit-identity with any
+ * build of the reference, and anything for the channels backward. */
+int gsr_set_train_math(int mode);
 
 const char* gsr_last_error(void);
 const char* gsr_version(void);
