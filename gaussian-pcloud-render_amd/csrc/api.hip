@@ -194,21 +194,29 @@ static inline void* align256(void* p) { return (void*)(((uintptr_t)p + 255) & ~(
 
 // Carve the caller's three allocations into V per-view arenas.  binning may be NULL (count-only forward).  with_grad: the
 // V gradient-record blocks that follow the V geometry arenas are part of the geometry allocation (need_backward calls).
-static int make_batch(const gsr_params* p, int V, void* geom, size_t geom_bytes, void* image, size_t image_bytes, void* binning,
-                      size_t binning_bytes, bool with_grad, Batch& B)
+// the geometry half of make_batch, all gsr_backward_cameras needs: the V geometry arenas and the gradient records behind them
+static int make_geom_batch(const gsr_params* p, int V, void* geom, size_t geom_bytes, bool with_grad, Batch& B)
 {
     B.V = V;
-    const size_t G = geom_view(nullptr, p->P).bytes, I = image_view(nullptr, p->W, p->H).bytes;
+    const size_t G = geom_view(nullptr, p->P).bytes;
     const size_t GR = with_grad ? grad_rec_bytes(p->P) : 0;
     if (!geom || geom_bytes < (size_t)V * (G + GR) + 256)
         return fail(GSR_ERR_CAPACITY, "[gsr] geom arena too small (%zu < %zu%s)", geom_bytes, (size_t)V * (G + GR) + 256,
                     with_grad ? ", need_backward" : "");
-    if (!image || image_bytes < (size_t)V * I + 256)
-        return fail(GSR_ERR_CAPACITY, "[gsr] image arena too small (%zu < %zu)", image_bytes, (size_t)V * I + 256);
     B.g = geom_view(align256(geom), p->P);
     B.g_stride = G;
     B.grad_rec = with_grad ? reinterpret_cast<float*>(reinterpret_cast<char*>(align256(geom)) + (size_t)V * G) : nullptr;
     B.gr_stride = GR;
+    return GSR_OK;
+}
+
+static int make_batch(const gsr_params* p, int V, void* geom, size_t geom_bytes, void* image, size_t image_bytes, void* binning,
+                      size_t binning_bytes, bool with_grad, Batch& B)
+{
+    const size_t I = image_view(nullptr, p->W, p->H).bytes;
+    if (int e = make_geom_batch(p, V, geom, geom_bytes, with_grad, B)) return e;
+    if (!image || image_bytes < (size_t)V * I + 256)
+        return fail(GSR_ERR_CAPACITY, "[gsr] image arena too small (%zu < %zu)", image_bytes, (size_t)V * I + 256);
     B.iv = image_view(align256(image), p->W, p->H);
     B.iv_stride = I;
     if (binning) {
@@ -243,6 +251,8 @@ struct FrameRecord {
     int math = 0;                // arithmetic of the call that last wrote the colour saves (0 exact, 1 fast): the forward, or a recolor --
                                  // it rewrites final_T and n_contrib of every pixel and, through the same kernel, every slice-boundary
                                  // state and accumulated colour a backward reads.  The render backward runs the same mode.
+    int bwd_done = 0;            // a backward has run since this record was written (every forward and recolor writes a fresh one):
+                                 // the gradient records hold its sums, which is what gsr_backward_cameras reads
     FrameRecord() = default;
     FrameRecord(int kind_, const gsr_params* p, int V_) : kind(kind_), need_backward(p->need_backward != 0), V(V_), P(p->P), W(p->W), H(p->H) {}
 };
@@ -740,6 +750,14 @@ static int backward_impl(const gsr_params* p, int V, const int* radii, const voi
                                                G.dL_dsh, G.dL_dscale, G.dL_drot))
             return e;
     }
+    {
+        // the records now hold this backward's per-view sums: gsr_backward_cameras may follow
+        FrameRecord r;
+        if (find_frame(geom, r)) {
+            r.bwd_done = 1;
+            note_frame(geom, r);
+        }
+    }
     return GSR_OK;
 }
 
@@ -810,6 +828,50 @@ int gsr_backward(const gsr_params* p, const int* radii, int64_t R, const void* g
     (void)R;   // the lists' extent lives in the arenas; kept for symmetry with the reference's backward(P, D, M, R, ...)
     return gsr_backward_batch(p, 1, radii, geom, geom_bytes, binning, binning_bytes, image, image_bytes, dL_dpix, dL_dmean2D,
                               dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream);
+}
+
+// ---- camera gradients: a reduction over the gradient records the last backward on the arenas left (camera_bwd.hip) ----
+size_t gsr_camera_grad_bytes(int V, int P)
+{
+    if (V < 1 || V > MAX_VIEWS || P < 0) return 0;
+    return align_up(camera_slab_bytes(V, P), 256) + 256;   // (+ 256 for aligning the caller's pointer)
+}
+
+int gsr_backward_cameras(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, float* dL_dviewmatrix,
+                         float* dL_dprojmatrix, float* dL_dcampos, void* scratch, size_t scratch_bytes, gsr_stream_t stream)
+{
+    if (int e = check_params(p, V)) return e;
+    if (p->P == 0) return GSR_OK;
+    if (!radii || !geom || !dL_dviewmatrix || !dL_dprojmatrix || !dL_dcampos || !scratch)
+        return fail(GSR_ERR_INVALID, "[gsr] backward_cameras: a required pointer is NULL");
+    if (scratch_bytes < gsr_camera_grad_bytes(V, p->P))
+        return fail(GSR_ERR_CAPACITY, "[gsr] backward_cameras: scratch block too small (%zu < %zu = gsr_camera_grad_bytes(%d, %d))",
+                    scratch_bytes, gsr_camera_grad_bytes(V, p->P), V, p->P);
+    FrameRecord r;
+    if (find_frame(geom, r)) {   // (no record: the call goes ahead, like a colour backward)
+        if (!r.need_backward)
+            return fail(GSR_ERR_INVALID, "[gsr] backward_cameras: the last %s on this geometry arena had need_backward = 0: there are "
+                        "no gradient records", r.kind == 2 ? "gsr_forward_recolor" : "forward");
+        if (!r.bwd_done)
+            return fail(GSR_ERR_INVALID, "[gsr] backward_cameras: no backward has run since the last forward or recolor on this geometry "
+                        "arena (the gradient records are empty; run one of the gsr_backward entries first)");
+        if (r.V != V || r.P != p->P || r.W != p->W || r.H != p->H)
+            return fail(GSR_ERR_INVALID, "[gsr] backward_cameras: V = %d, P = %d, %d x %d, but the last forward or recolor on this "
+                        "geometry arena had V = %d, P = %d, %d x %d", V, p->P, p->W, p->H, r.V, r.P, r.W, r.H);
+    }
+    Batch B;
+    if (int e = make_geom_batch(p, V, const_cast<void*>(geom), geom_bytes, true, B)) return e;
+    const Launch L{(hipStream_t)stream, p->debug};
+    double* slab = reinterpret_cast<double*>(align256(scratch));
+    {
+        ProfScope ps("camera_partials", L.stream);
+        if (int e = launch_camera_partials(L, *p, B, radii, slab)) return e;
+    }
+    {
+        ProfScope ps("camera_sum", L.stream);
+        if (int e = launch_camera_sum(L, V, p->P, p->shs != nullptr, slab, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos)) return e;
+    }
+    return GSR_OK;
 }
 
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,

@@ -515,6 +515,20 @@ int launch_preprocess_backward(const Launch& L, const gsr_params& p, const Batch
                                float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
                                float* dL_dscale, float* dL_drot);
 
+// camera_bwd.hip: dL/d viewmatrix, projmatrix, campos from the per-view gradient records a backward left.
+// Two launches: every workgroup of k_camera_partials sums the 27 live entries over its CAM_ROWS Gaussians of one view in float64
+// and stores them, padded to CAM_SLAB_WORDS doubles, into the caller's slab [V][camera_blocks(P)][CAM_SLAB_WORDS]; k_camera_sum
+// (one workgroup per view) adds a view's partials in block order and writes its 35 floats.
+constexpr int CAM_THREADS = 256;                  // both kernels
+constexpr int CAM_G = 4;                          // Gaussians per thread of k_camera_partials
+constexpr int CAM_ROWS = CAM_THREADS * CAM_G;     // Gaussians per workgroup
+constexpr int CAM_TERMS = 27;                     // 12 view + 12 proj + 3 campos entries the forward reads
+constexpr int CAM_SLAB_WORDS = 32;                // doubles per partial: 256 B
+inline int camera_blocks(int P) { return (int)div_up(P > 0 ? P : 1, CAM_ROWS); }
+inline size_t camera_slab_bytes(int V, int P) { return (size_t)V * (size_t)camera_blocks(P) * CAM_SLAB_WORDS * sizeof(double); }
+int launch_camera_partials(const Launch& L, const gsr_params& p, const Batch& B, const int* radii, double* slab);
+int launch_camera_sum(const Launch& L, int V, int P, int with_campos, const double* slab, float* dL_dview, float* dL_dproj, float* dL_dcampos);
+
 // device helper: clear [p, p + bytes) (16-B aligned, multiple of 16) with the calling grid's threads
 __device__ __forceinline__ void zero_region(char* p, size_t bytes, size_t gtid, size_t nthreads)
 {

@@ -260,7 +260,7 @@ def _pack_views(settings_list, device):
     return view, proj, cam
 
 
-def _stack_views(settings_list, device):
+def _check_views_agree(settings_list):
     s0 = settings_list[0]
     for s in settings_list[1:]:
         if (s.image_height, s.image_width, s.tanfovx, s.tanfovy, s.scale_modifier, s.sh_degree, s.prefiltered) != (
@@ -268,6 +268,10 @@ def _stack_views(settings_list, device):
                 not _same_background(s.bg, s0.bg):
             raise Exception("rasterize_views: the views of a batch must share image size, tan(fov), background, scale "
                             "modifier, SH degree and the prefiltered flag")
+
+
+def _stack_views(settings_list, device):
+    _check_views_agree(settings_list)
     _C._require_hip(device)
     keys = [_tkey(t) for s in settings_list for t in (s.viewmatrix, s.projmatrix, s.campos)]
     if not _VIEW_CACHE_ON or any(k is None for k in keys):
@@ -331,6 +335,74 @@ def rasterize_views(means3D, means2D, opacities, settings_list, shs=None, colors
     shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales, rotations, cov3D_precomp)
     return _RasterizeGaussiansViews.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                           list(settings_list))
+
+
+class _RasterizeGaussiansViewsCameras(torch.autograd.Function):
+    """_RasterizeGaussiansViews with the cameras as autograd inputs: view / proj [V,4,4] and cam [V,3] on the device instead of the
+    settings' own matrix fields.  The same native calls, so images and cloud gradients are those of rasterize_views bit for bit;
+    the camera gradients come from one more call after the colour backward (C ABI gsr_backward_cameras)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, view, proj, cam,
+                settings_list):
+        rs = settings_list[0]
+        _check_views_agree(settings_list)
+        device = means3D.device
+        _C._require_hip(device)
+        ctx.cam_shapes = (tuple(view.shape), tuple(proj.shape), tuple(cam.shape))
+        view, proj, cam = (_C._f32c(view, device, "viewmatrices"), _C._f32c(proj, device, "projmatrices"),
+                           _C._f32c(cam, device, "campos"))
+        need_backward = any(ctx.needs_input_grad)
+        counts, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians_batch(
+            rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj,
+            rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree, cam, rs.prefiltered,
+            any(s.debug for s in settings_list), need_backward=need_backward)
+        ctx.raster_settings = rs
+        ctx.opacity_shape = tuple(opacities.shape)
+        ctx.det_pairs = _C.last_list_pairs(len(counts)) if means3D.shape[0] != 0 and _C.deterministic_active() else None
+        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
+                              imgBuffer, view, proj, cam)
+        ctx.mark_non_differentiable(radii)
+        return color, radii
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _):
+        rs = ctx.raster_settings
+        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer, view, proj,
+         cam) = ctx.saved_tensors
+        grads = _C.rasterize_gaussians_backward_batch(
+            rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj, rs.tanfovx,
+            rs.tanfovy, grad_out_color, sh, rs.sh_degree, cam, geomBuffer, binningBuffer, imgBuffer, rs.debug,
+            deterministic=_C.deterministic_active(), pairs=ctx.det_pairs)
+        g_cam = (None, None, None)
+        if any(ctx.needs_input_grad[8:11]):
+            # the gradient records of the backward above are still in the arenas: one reduction over them per view
+            g = _C.backward_cameras(rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view,
+                                    proj, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree, cam, geomBuffer,
+                                    rs.debug)
+            g_cam = tuple(t.reshape(shape) if need else None
+                          for t, shape, need in zip(g, ctx.cam_shapes, ctx.needs_input_grad[8:11]))
+        return _input_grads(grads, ctx, sh, colors_precomp, scales, rotations, cov3Ds_precomp, *g_cam, None)
+
+
+def rasterize_views_cameras(means3D, means2D, opacities, settings_list, viewmatrices, projmatrices, campos, shs=None,
+                            colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None):
+    """rasterize_views with differentiable cameras (pose refinement): viewmatrices / projmatrices [V,4,4] (transposed like the
+    settings' fields) and campos [V,3], on the device, are autograd inputs and take the place of the settings' own matrix fields,
+    which are ignored; settings_list supplies V and the fields the views share.  Returns (colors [V,3,H,W], radii [V,P]): the images
+    and the cloud's gradients of rasterize_views with the same matrices, bit for bit.  The camera gradients follow the conventions of
+    include/gsr.h gsr_backward_cameras: depth order, culling and tile lists are not differentiated, projmatrix rows the rasterizer
+    never reads get zeros, campos gets a gradient through the SH view direction only."""
+    if len(settings_list) == 0:
+        raise Exception("rasterize_views_cameras: empty settings list")
+    _check_sources(shs, colors_precomp, scales, rotations, cov3D_precomp)
+    V = len(settings_list)
+    if viewmatrices.numel() != 16 * V or projmatrices.numel() != 16 * V or campos.numel() != 3 * V:
+        raise Exception("rasterize_views_cameras: viewmatrices and projmatrices must be [V,4,4] and campos [V,3] for the V views of "
+                        "settings_list")
+    shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales, rotations, cov3D_precomp)
+    return _RasterizeGaussiansViewsCameras.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                                                 viewmatrices, projmatrices, campos, list(settings_list))
 
 
 class _RasterizeGaussiansViewsChannels(torch.autograd.Function):

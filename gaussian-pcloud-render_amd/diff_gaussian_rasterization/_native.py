@@ -63,6 +63,8 @@ _DECL = {
     "gsr_backward_batch_channels": (_int, _BWD + [_int, _int, _fp, _fp, _fp, _fp, _size, _fp, _fp, _fp]),
     "gsr_backward_batch_channels_det": (_int, _BWD + [_int, _int, _fp, _fp, _fp, _fp, _size, _fp, _fp, _fp, _size, _fp]),
     "gsr_backward": (_int, [_pp, _fp, _i64] + _ARENAS + [_fp] * 9 + [_fp]),
+    "gsr_camera_grad_bytes": (_size, [_int, _int]),
+    "gsr_backward_cameras": (_int, [_pp, _int, _fp, _fp, _size, _fp, _fp, _fp, _fp, _size, _fp]),
     "gsr_mark_visible": (_int, [_int, _fp, _fp, _fp, _fp, _fp]),
     "gsr_query": (_int, [_pp, _int, _fp, _fp, _size, _fp, _i64, _fp, _size, _fp]),
     "gsr_set_profiling": (None, [_int]),
@@ -210,8 +212,8 @@ def set_reference_lists(on):
 # bit-identical gradients from call to call and from process to process for the same inputs and call shape (not across different
 # numbers of views per call), for a scratch block per backward and the time of a sort and an ordered reduction.
 _DETERMINISTIC = [{"0": False, "1": True}.get(os.environ.get("GSR_DETERMINISTIC", "").strip())]
-# backwards issued through each entry (tests): the colour ones, and the deterministic channels backward
-CALLS = dict(backward=0, backward_det=0, backward_channels_det=0)
+# backwards issued through each entry (tests): the colour ones, the deterministic channels backward, and the camera gradients
+CALLS = dict(backward=0, backward_det=0, backward_channels_det=0, backward_cameras=0)
 
 
 def set_deterministic(flag):
@@ -853,6 +855,39 @@ def rasterize_gaussians_backward_channels_batch(background, means3D, radii, colo
     else:
         gx = gx.reshape((V, P, nx) if x_per_view else (P, nx))
     return grads + (gx,)
+
+
+def camera_scratch(V, P, device):
+    """the scratch block of one backward_cameras call (gsr_camera_grad_bytes)"""
+    return torch.empty((int(lib.gsr_camera_grad_bytes(V, P)),), dtype=torch.uint8, device=device)
+
+
+def backward_cameras(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices,
+                     tan_fovx, tan_fovy, image_height, image_width, sh, degree, camposs, geomBuffer, debug=False, _out=None,
+                     _scratch=None):
+    """Camera gradients of the last backward on `geomBuffer` (C ABI gsr_backward_cameras): the arguments of that backward, radii
+    [V,P].  Returns (dL_dviewmatrices [V,4,4], dL_dprojmatrices [V,4,4], dL_dcamposs [V,3]), the gradients of the matrices as
+    stored.  _out / _scratch: the three outputs and the scratch block (tests hand over prefilled ones; default: fresh tensors)."""
+    device = means3D.device
+    _require_hip(device)
+    P, V = means3D.shape[0], viewmatrices.numel() // 16
+    new = torch.empty if P != 0 else torch.zeros
+    out = _out if _out is not None else (new((V, 4, 4), dtype=_F32, device=device), new((V, 4, 4), dtype=_F32, device=device),
+                                         new((V, 3), dtype=_F32, device=device))
+    if P != 0:
+        CALLS["backward_cameras"] += 1
+        with _on_device(device):
+            # (opacity lives in the geom arena; the pointer only has to be non-NULL: means3D stands in)
+            p, keep = _params(background, means3D, colors, means3D, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
+                              projmatrices, tan_fovx, tan_fovy, int(image_height), int(image_width), sh, degree, camposs, False, debug,
+                              True)
+            scratch = _scratch if _scratch is not None else camera_scratch(V, P, device)
+            radii_c = radii.contiguous()
+            _check(lib.gsr_backward_cameras(C.byref(p), V, radii_c.data_ptr(), geomBuffer.data_ptr(), geomBuffer.numel(),
+                                            out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), scratch.data_ptr(),
+                                            scratch.numel(), _stream_handle(device)))
+            del keep
+    return out
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,

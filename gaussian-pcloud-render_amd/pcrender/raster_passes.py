@@ -27,6 +27,7 @@ import torch.nn.functional as F
 
 from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
 from diff_gaussian_rasterization import rasterize_views as _rasterize_views_call
+from diff_gaussian_rasterization import rasterize_views_cameras as _rasterize_views_cameras
 from diff_gaussian_rasterization import rasterize_views_channels as _rasterize_views_channels
 from diff_gaussian_rasterization import _native
 
@@ -107,6 +108,28 @@ def rasterize_views(means3D_list, opacity_list, scales_list, rotations_list, H_c
                 opacities=opacity_i, scales=scales, rotations=rotations_list[i], cov3D_precomp=None)
             frames.append(img)
     return _finish(frames, batchsize, num_q, h, w, super_sample_rate)
+
+
+def rasterize_views_posed(means3D, opacities, scales, rotations, H_c2w, h, w, fov, bg=None, shs=None, colors_precomp=None,
+                          sh_degree=1, super_sample_rate=2):
+    """ONE cloud seen from q poses that may be optimised: H_c2w [q,4,4] on the cloud's device, possibly requiring grad.  The
+    settings' matrices are built on the device inside the autograd graph (camera.raster_settings_tensors), the q views go through
+    one differentiable call (diff_gaussian_rasterization.rasterize_views_cameras), and the frames are finished like
+    rasterize_views': (1, q, h, w, 3).  After loss.backward(), H_c2w.grad holds the pose gradient next to the cloud's gradients.
+    The Gaussians are taken as given (no scale factor), exactly one of shs / colors_precomp."""
+    device = means3D.device
+    num_q = H_c2w.shape[0]
+    a = _camera.raster_settings_tensors(H_c2w.to(device=device, dtype=torch.float32), w, h, fov, super_sample_rate)
+    bg_d = torch.zeros(3, device=device) if bg is None else bg.to(device)
+    view, proj, cam = a["viewmatrix"], a["projmatrix"], a["campos"]
+    sts = [GaussianRasterizationSettings(
+        image_height=a["image_height"], image_width=a["image_width"], tanfovx=a["tanfovx"], tanfovy=a["tanfovy"], bg=bg_d,
+        scale_modifier=1.0, viewmatrix=view[j].detach(), projmatrix=proj[j].detach(), sh_degree=sh_degree, campos=cam[j].detach(),
+        prefiltered=False, debug=False) for j in range(num_q)]
+    means2D = torch.zeros_like(means3D, dtype=torch.float32, requires_grad=True, device=device) + 0
+    imgs, _ = _rasterize_views_cameras(means3D, means2D, opacities, sts, view, proj, cam, shs=shs, colors_precomp=colors_precomp,
+                                       scales=scales, rotations=rotations)
+    return _finish(imgs, 1, num_q, h, w, super_sample_rate)
 
 
 def pcgc_rescale(xyz, offset=512, factor=256):

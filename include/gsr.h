@@ -281,6 +281,38 @@ int gsr_backward(const gsr_params* p, const int* radii, int64_t num_rendered, co
                  float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
                  float* dL_drot, gsr_stream_t stream);
 
+/* Camera gradients: dL/d viewmatrix, dL/d projmatrix and dL/d campos of every view, for pose refinement.  A separate call that runs
+ * AFTER a backward on the same arenas -- gsr_backward_batch, gsr_backward_batch_det, gsr_backward, gsr_backward_batch_channels or
+ * gsr_backward_batch_channels_det -- with that backward's p, V and radii; it differentiates what that backward differentiated (after
+ * a channels backward the mean2D and conic sums carry the extras' share, so the result is that of colour plus channels).  It reads
+ * the per-view gradient records the backward left behind the geometry arenas, pushes them through the projection chain to the camera
+ * operands and adds over the Gaussians of each view; the backward's own outputs are not needed and nothing in
+ * the arenas is changed, so the call may be repeated.
+ *   dL_dviewmatrix, dL_dprojmatrix  [V][16] in the flattening of viewmatrix / projmatrix themselves
+ *   dL_dcampos                      [V][3]: through the SH view direction; +0 with colors_precomp and at SH degree 0
+ * All 35 floats of every view are written.  The entries the forward never reads are written as +0: viewmatrix[3, 7, 11, 15] and
+ * projmatrix[2, 6, 10, 14] (preprocess uses rows 0, 1, 3 of the projection only).  A view in which nothing is visible gets 35 zeros.
+ * Conventions: the reference's backward treats the frustum clamp of the view-space mean (|x / z| > 1.3 tanfov) as dL/dt_x = 0 (t_y
+ * likewise) with the clamped t_x, t_y as constants in dL/dt_z; the camera gradient keeps that convention, so that
+ *   sum_i dL_dmean3D[i][j] = sum_v ( sum_k view[k + 4j] dL_dview[12 + k] + sum_{k in 0,1,3} proj[k + 4j] dL_dproj[12 + k] - dL_dcampos[j] )
+ * holds (a translation of the cloud is a translation of every camera).  Depth order, culling, radii and the tile lists are not
+ * differentiated (piecewise constant), nor are tanfovx / tanfovy (intrinsics reach the image through projmatrix).
+ * Every per-Gaussian term is evaluated in float32 and added in float64 in a fixed order (Gaussian index inside a thread, a fixed tree
+ * over the workgroup, the workgroups' partial sums by index in a second launch), rounded to float32 once: no atomics, so the result
+ * is a function of the records alone -- bit-reproducible after gsr_backward_batch_det / _channels_det, and the same bits again when
+ * the call is repeated over one backward.  No device->host read-back; the library allocates nothing on the device.
+ *
+ * scratch: caller-owned, at least gsr_camera_grad_bytes(V, P) bytes (a pure host function: 256 B per 1024 Gaussians and view, a
+ * positive multiple of 256 that does not decrease with V or P; 0 for V < 1, V > 256 or P < 0); every word read is written first.
+ * Checks, in this order: the parameters (as every entry); P == 0 -> GSR_OK, nothing written; a NULL radii, geom, output or scratch
+ * -> GSR_ERR_INVALID; a scratch block that is too small -> GSR_ERR_CAPACITY with the needed size in the message; then the arena's
+ * record -> GSR_ERR_INVALID when the last forward or recolor on `geom` had need_backward = 0, when no backward has run since it, or
+ * when V, P, W or H differ from it (the outputs are then untouched).  An arena without a record is not checked. */
+size_t gsr_camera_grad_bytes(int V, int P);
+int gsr_backward_cameras(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes,
+                         float* dL_dviewmatrix /* [V][16] */, float* dL_dprojmatrix /* [V][16] */, float* dL_dcampos /* [V][3] */,
+                         void* scratch, size_t scratch_bytes, gsr_stream_t stream);
+
 /* Pairs in the lists of the calling thread's last forward call, per view (out[V], HOST array): what a binning arena has to
  * hold.  Equal to num_rendered with reference_lists = 1. */
 int gsr_last_list_pairs(int64_t* out, int V);
