@@ -5,8 +5,9 @@
 // the Gaussians of ONE view.  Notation of preprocess_bwd.hip's header; m = (x, y, z, 1) the mean, r_k = (view[k], view[4+k],
 // view[8+k]) the rows of the view rotation, t_k = r_k . mean + view[12+k]:
 //
-//   conic      da, db, dc, dm0, dm1 and dt = (dtx, dty, dtz) exactly as k_preprocess_backward forms them -- the Dn != 0 guard, dtx = 0
-//              (dty = 0) where the frustum clamp was active, tx and ty taken as constants in dtz: the reference's convention.
+//   conic      da, db, dc, dm0, dm1 and dt = (dtx, dty, dtz) by k_preprocess_backward's expressions -- dtx = 0 (dty = 0) where the
+//              frustum clamp was active, tx and ty taken as constants in dtz: the reference's convention (its Dn != 0 guard
+//              answers a float32 overflow of det^2 that float64 does not have).
 //              m0 = J00 r0 + J02 r2, m1 = J11 r1 + J12 r2, so
 //                  dL/dr0 += J00 dm0 + dtx mean      dL/dr1 += J11 dm1 + dty mean      dL/dr2 += J02 dm0 + J12 dm1 + dtz mean
 //                  dL/dview[12+k] += dt_k
@@ -16,7 +17,11 @@
 //
 // view[3, 7, 11, 15] and proj[2, 6, 10, 14] are never read by the forward: their gradients are written as +0.
 //
-// Every term is evaluated in float32 (one rounding per written operation, like the rest of the library) and ADDED in float64, in an
+// The conic chain (3D covariance -> a, b, c -> da, db, dc -> dL/dr_k, dL/dt) is evaluated in float64 from the float32 inputs and
+// records: for a splat next to the camera its terms cancel several hundredfold, and in float32 one such splat put a whole view's
+// dL/dviewmatrix several 1e-4 of its largest entry off (the randomised sweep, tests/test_gpu_camera_fuzz.py, cases 0, 40, 47).  The
+// frustum-clamp decisions stay the forward's float32 ones.  The mean2D and SH terms are evaluated in float32 (one rounding per
+// written operation, like the rest of the library).  Every term is ADDED in float64, in an
 // order that depends on nothing but the sizes: a thread's Gaussians by ascending index, a butterfly over the wave's 64 lanes, the
 // four waves through LDS, the workgroups' partials by ascending block index in a second launch.  No atomics, no hand-off between
 // workgroups: the result does not depend on when which workgroup runs.
@@ -90,51 +95,73 @@ __global__ __launch_bounds__(CAM_THREADS) void k_camera_partials(CamArgs a)
         const float4 rec0 = *reinterpret_cast<const float4*>(recp);
         const float4 rec1 = *reinterpret_cast<const float4*>(recp + 4);
         const V3 mean = v3(a.means3D[3 * idx], a.means3D[3 * idx + 1], a.means3D[3 * idx + 2]);
-        float S6[6];
+        // ---- conic -> (a, b, c) -> rows of M -> view rows, in DOUBLE from the float32 inputs.  A splat next to the camera and beyond
+        // the frustum clamp has a c / det of 40 .. 170 and a conic gradient that cancels several hundredfold in da / db / dc: in
+        // float32 its term alone was off by up to 1e-3 of itself, a few 1e-4 of the whole view's gradient (tests/test_gpu_camera_fuzz.py).
+        // Only the clamp decisions are the forward's float32 ones (cov2d_project): that is the function the forward evaluated.
+        double S[6];
         if (a.cov3D_precomp) {
 #pragma unroll
-            for (int i = 0; i < 6; i++) S6[i] = a.cov3D_precomp[6 * (size_t)idx + i];
+            for (int i = 0; i < 6; i++) S[i] = (double)a.cov3D_precomp[6 * (size_t)idx + i];
         } else {
-            const V3 sc = v3(a.scales[3 * idx], a.scales[3 * idx + 1], a.scales[3 * idx + 2]);
-            const float4 q = *reinterpret_cast<const float4*>(a.rotations + 4 * (size_t)idx);
-            cov3d_from_scale_rot(sc, a.scale_modifier, q, S6, nullptr);
+            const float4 q4 = *reinterpret_cast<const float4*>(a.rotations + 4 * (size_t)idx);
+            const double r = q4.x, x = q4.y, y = q4.z, z = q4.w, md = (double)a.scale_modifier;
+            const double s0 = md * (double)a.scales[3 * idx], s1 = md * (double)a.scales[3 * idx + 1], s2 = md * (double)a.scales[3 * idx + 2];
+            const double v0 = s0 * s0, v1 = s1 * s1, v2 = s2 * s2;
+            // R from the raw quaternion (quat_to_cols), Sigma = R diag(s^2) R^T
+            const double R00 = 1.0 - 2.0 * (y * y + z * z), R01 = 2.0 * (x * y - r * z), R02 = 2.0 * (x * z + r * y);
+            const double R10 = 2.0 * (x * y + r * z), R11 = 1.0 - 2.0 * (x * x + z * z), R12 = 2.0 * (y * z - r * x);
+            const double R20 = 2.0 * (x * z - r * y), R21 = 2.0 * (y * z + r * x), R22 = 1.0 - 2.0 * (x * x + y * y);
+            S[0] = R00 * R00 * v0 + R01 * R01 * v1 + R02 * R02 * v2;
+            S[1] = R00 * R10 * v0 + R01 * R11 * v1 + R02 * R12 * v2;
+            S[2] = R00 * R20 * v0 + R01 * R21 * v1 + R02 * R22 * v2;
+            S[3] = R10 * R10 * v0 + R11 * R11 * v1 + R12 * R12 * v2;
+            S[4] = R10 * R20 * v0 + R11 * R21 * v1 + R12 * R22 * v2;
+            S[5] = R20 * R20 * v0 + R21 * R21 * v1 + R22 * R22 * v2;
         }
-        const Cov2D c = cov2d_project(mean, fx, fy, a.tanfovx, a.tanfovy, S6, view);
-        const bool clamp_x = c.txtz < -c.limx || c.txtz > c.limx, clamp_y = c.tytz < -c.limy || c.tytz > c.limy;
-        const V3 m0 = v3(c.T.m[0][0], c.T.m[0][1], c.T.m[0][2]), m1 = v3(c.T.m[1][0], c.T.m[1][1], c.T.m[1][2]);
-        const float ca = c.cov.m[0][0] + 0.3f, cb = c.cov.m[0][1], cc = c.cov.m[1][1] + 0.3f;
-
-        // ---- conic -> (a, b, c) -> rows of M (k_preprocess_backward's expressions)
-        const float gA = rec0.z, gB = rec0.w, gC = rec1.x;
-        const float det = ca * cc - cb * cb;
-        const float Dn = 1.0f / ((det * det) + 0.0000001f);
-        float da = 0.f, db = 0.f, dc = 0.f;
-        if (Dn != 0) {
-            da = Dn * (-cc * cc * gA + 2 * cb * cc * gB + (det - ca * cc) * gC);
-            dc = Dn * (-ca * ca * gC + 2 * ca * cb * gB + (det - ca * cc) * gA);
-            db = Dn * 2 * (cb * cc * gA - (det + 2 * cb * cb) * gB + ca * cb * gC);
+        const float limx = 1.3f * a.tanfovx, limy = 1.3f * a.tanfovy;
+        const V3 tf = xform_point_4x3(mean, view);     // the forward's float32 view-space mean: its clamp decisions
+        const float txtz_f = tf.x / tf.z, tytz_f = tf.y / tf.z;
+        const bool clamp_x = txtz_f < -limx || txtz_f > limx, clamp_y = tytz_f < -limy || tytz_f > limy;
+        const double mx = mean.x, my = mean.y, mz = mean.z, fxd = fx, fyd = fy;
+        const double r0[3] = {view[0], view[4], view[8]}, r1[3] = {view[1], view[5], view[9]}, r2[3] = {view[2], view[6], view[10]};
+        const double tz = r2[0] * mx + r2[1] * my + r2[2] * mz + (double)view[14];
+        const double iz = 1.0 / tz, iz2 = iz * iz, iz3 = iz2 * iz;      // (one float64 division here, one for Dn: they are the slow part)
+        const double txz = (r0[0] * mx + r0[1] * my + r0[2] * mz + (double)view[12]) * iz;
+        const double tyz = (r1[0] * mx + r1[1] * my + r1[2] * mz + (double)view[13]) * iz;
+        const double tx = fmin((double)limx, fmax(-(double)limx, txz)) * tz, ty = fmin((double)limy, fmax(-(double)limy, tyz)) * tz;
+        const double J00 = fxd * iz, J02 = -(fxd * tx) * iz2, J11 = fyd * iz, J12 = -(fyd * ty) * iz2;
+        double m0[3], m1[3], u[3], w[3], dm0[3], dm1[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) { m0[j] = J00 * r0[j] + J02 * r2[j]; m1[j] = J11 * r1[j] + J12 * r2[j]; }
+        u[0] = S[0] * m0[0] + S[1] * m0[1] + S[2] * m0[2]; u[1] = S[1] * m0[0] + S[3] * m0[1] + S[4] * m0[2];
+        u[2] = S[2] * m0[0] + S[4] * m0[1] + S[5] * m0[2];
+        w[0] = S[0] * m1[0] + S[1] * m1[1] + S[2] * m1[2]; w[1] = S[1] * m1[0] + S[3] * m1[1] + S[4] * m1[2];
+        w[2] = S[2] * m1[0] + S[4] * m1[1] + S[5] * m1[2];
+        const double ca = (m0[0] * u[0] + m0[1] * u[1] + m0[2] * u[2]) + (double)0.3f;
+        const double cb = m0[0] * w[0] + m0[1] * w[1] + m0[2] * w[2];
+        const double cc = (m1[0] * w[0] + m1[1] * w[1] + m1[2] * w[2]) + (double)0.3f;
+        const double gA = rec0.z, gB = rec0.w, gC = rec1.x;
+        const double det = ca * cc - cb * cb;
+        const double Dn = 1.0 / ((det * det) + (double)0.0000001f);
+        const double da = Dn * (-cc * cc * gA + 2 * cb * cc * gB + (det - ca * cc) * gC);
+        const double dc = Dn * (-ca * ca * gC + 2 * ca * cb * gB + (det - ca * cc) * gA);
+        const double db = Dn * 2 * (cb * cc * gA - (det + 2 * cb * cb) * gB + ca * cb * gC);
+#pragma unroll
+        for (int j = 0; j < 3; j++) { dm0[j] = (2 * da) * u[j] + db * w[j]; dm1[j] = (2 * dc) * w[j] + db * u[j]; }
+        const double dJ00 = r0[0] * dm0[0] + r0[1] * dm0[1] + r0[2] * dm0[2], dJ02 = r2[0] * dm0[0] + r2[1] * dm0[1] + r2[2] * dm0[2];
+        const double dJ11 = r1[0] * dm1[0] + r1[1] * dm1[1] + r1[2] * dm1[2], dJ12 = r2[0] * dm1[0] + r2[1] * dm1[1] + r2[2] * dm1[2];
+        const double dtx = clamp_x ? 0.0 : -fxd * iz2 * dJ02;
+        const double dty = clamp_y ? 0.0 : -fyd * iz2 * dJ12;
+        const double dtz = -(fxd * dJ00 + fyd * dJ11) * iz2 + 2 * (fxd * tx * dJ02 + fyd * ty * dJ12) * iz3;
+        const double md3[3] = {mx, my, mz};
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            acc[j] += J00 * dm0[j] + dtx * md3[j];
+            acc[3 + j] += J11 * dm1[j] + dty * md3[j];
+            acc[6 + j] += (J02 * dm0[j] + J12 * dm1[j]) + dtz * md3[j];
         }
-        const V3 u = v3(S6[0] * m0.x + S6[1] * m0.y + S6[2] * m0.z, S6[1] * m0.x + S6[3] * m0.y + S6[4] * m0.z,
-                        S6[2] * m0.x + S6[4] * m0.y + S6[5] * m0.z);
-        const V3 w = v3(S6[0] * m1.x + S6[1] * m1.y + S6[2] * m1.z, S6[1] * m1.x + S6[3] * m1.y + S6[4] * m1.z,
-                        S6[2] * m1.x + S6[4] * m1.y + S6[5] * m1.z);
-        const V3 dm0 = (2 * da) * u + db * w, dm1 = (2 * dc) * w + db * u;
-        const V3 r0 = v3(view[0], view[4], view[8]), r1 = v3(view[1], view[5], view[9]), r2 = v3(view[2], view[6], view[10]);
-        const float dJ00 = dot3(r0, dm0), dJ02 = dot3(r2, dm0), dJ11 = dot3(r1, dm1), dJ12 = dot3(r2, dm1);
-        const V3 t = c.t;
-        const float iz = 1.f / t.z, iz2 = iz * iz, iz3 = iz2 * iz;
-        const float dtx = clamp_x ? 0.f : -fx * iz2 * dJ02;
-        const float dty = clamp_y ? 0.f : -fy * iz2 * dJ12;
-        const float dtz = -(fx * dJ00 + fy * dJ11) * iz2 + 2 * (fx * t.x * dJ02 + fy * t.y * dJ12) * iz3;
-        // the Jacobian entries as the forward builds them (cov2d_project)
-        const float J00 = fx / t.z, J02 = -(fx * t.x) / (t.z * t.z), J11 = fy / t.z, J12 = -(fy * t.y) / (t.z * t.z);
-        const V3 dr0 = J00 * dm0 + dtx * mean;
-        const V3 dr1 = J11 * dm1 + dty * mean;
-        const V3 dr2 = (J02 * dm0 + J12 * dm1) + dtz * mean;
-        acc[0] += (double)dr0.x; acc[1] += (double)dr0.y; acc[2] += (double)dr0.z;
-        acc[3] += (double)dr1.x; acc[4] += (double)dr1.y; acc[5] += (double)dr1.z;
-        acc[6] += (double)dr2.x; acc[7] += (double)dr2.y; acc[8] += (double)dr2.z;
-        acc[9] += (double)dtx; acc[10] += (double)dty; acc[11] += (double)dtz;
+        acc[9] += dtx; acc[10] += dty; acc[11] += dtz;
 
         // ---- mean2D -> the three rows of proj the perspective divide reads
         {

@@ -297,7 +297,8 @@ int gsr_backward(const gsr_params* p, const int* radii, int64_t num_rendered, co
  *   sum_i dL_dmean3D[i][j] = sum_v ( sum_k view[k + 4j] dL_dview[12 + k] + sum_{k in 0,1,3} proj[k + 4j] dL_dproj[12 + k] - dL_dcampos[j] )
  * holds (a translation of the cloud is a translation of every camera).  Depth order, culling, radii and the tile lists are not
  * differentiated (piecewise constant), nor are tanfovx / tanfovy (intrinsics reach the image through projmatrix).
- * Every per-Gaussian term is evaluated in float32 and added in float64 in a fixed order (Gaussian index inside a thread, a fixed tree
+ * The terms through the 2D covariance are evaluated in float64 from the float32 inputs and records (a splat next to the camera makes
+ * them cancel several hundredfold), the others in float32; every per-Gaussian term is added in float64 in a fixed order (Gaussian index inside a thread, a fixed tree
  * over the workgroup, the workgroups' partial sums by index in a second launch), rounded to float32 once: no atomics, so the result
  * is a function of the records alone -- bit-reproducible after gsr_backward_batch_det / _channels_det, and the same bits again when
  * the call is repeated over one backward.  No device->host read-back; the library allocates nothing on the device.

@@ -9,28 +9,12 @@ import torch
 
 import camera_cases as CC
 import util
+from camera_sweep import _args, _bits, _cameras, _prefilled, _t
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 TALLY = dict(exits=0, live=0, worst=0.0)      # over the cases held to the arbiter in this file
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _args(scenes, dev):
-    """rasterize_gaussians_batch arguments for views of one cloud, given as oracle Scenes"""
-    s = scenes[0]
-    e = torch.empty(0)
-    a = lambda x: e if x is None else _t(x, dev)  # noqa: E731
-    vm = _t(np.stack([x.viewmatrix.reshape(4, 4) for x in scenes]), dev)
-    pm = _t(np.stack([x.projmatrix.reshape(4, 4) for x in scenes]), dev)
-    cp = _t(np.stack([x.campos.reshape(3) for x in scenes]), dev)
-    return [a(s.bg), a(s.means3D), a(s.colors_precomp), a(s.opacities.reshape(-1, 1)), a(s.scales), a(s.rotations),
-            float(s.scale_modifier), a(s.cov3D_precomp), vm, pm, s.tanfovx, s.tanfovy, s.H, s.W, a(s.shs),
-            int(s.sh_degree) if s.shs is not None else 0, cp, False, False]
 
 
 def _forward(N, args, need_backward=True):
@@ -44,29 +28,6 @@ def _backward(N, args, run, dpix, deterministic=False):
                                              args[10], args[11], dpix, args[14], args[15], args[16], geom, binning, img, False,
                                              deterministic=deterministic)
     return g
-
-
-def _prefilled(N, V, P, dev):
-    out = (torch.full((V, 4, 4), float("nan"), device=dev), torch.full((V, 4, 4), float("nan"), device=dev),
-           torch.full((V, 3), float("nan"), device=dev))
-    scratch = torch.full((int(N.lib.gsr_camera_grad_bytes(V, P)),), 255, dtype=torch.uint8, device=dev)
-    return out, scratch
-
-
-def _cameras(N, args, radii, geom, V=None):
-    """one gsr_backward_cameras call into NaN-filled outputs with a 0xFF-filled scratch block: per view dict of numpy arrays"""
-    dev = args[1].device
-    V = args[8].shape[0] if V is None else V
-    out, scratch = _prefilled(N, V, args[1].shape[0], dev)
-    N.backward_cameras(args[0], args[1], radii[:V], args[2], args[4], args[5], args[6], args[7], args[8][:V], args[9][:V], args[10],
-                       args[11], args[12], args[13], args[14], args[15], args[16][:V], geom, _out=out, _scratch=scratch)
-    dv, dp, dc = (o.cpu().numpy() for o in out)
-    assert np.isfinite(dv).all() and np.isfinite(dp).all() and np.isfinite(dc).all(), "an output was left unwritten"
-    return [dict(dL_dviewmatrix=dv[v].reshape(16), dL_dprojmatrix=dp[v].reshape(16), dL_dcampos=dc[v]) for v in range(V)]
-
-
-def _bits(cams):
-    return b"".join(np.ascontiguousarray(c[n]).tobytes() for c in cams for n, _, _ in CC.TENSORS)
 
 
 def _hold(cams, ref, tag):
