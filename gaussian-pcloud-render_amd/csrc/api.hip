@@ -874,6 +874,38 @@ int gsr_backward_cameras(const gsr_params* p, int V, const int* radii, const voi
     return GSR_OK;
 }
 
+// ---- density-control statistics and per-view shares: the other reader of the gradient records (view_stats.hip) ----
+int gsr_backward_view_stats(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, int accumulate,
+                            float* grad_norm_sum, int* visible_views, int* max_radius, float* dL_dmean2D_views,
+                            float* dL_dcolor_views, float* dL_dopacity_views, gsr_stream_t stream)
+{
+    if (int e = check_params(p, V)) return e;
+    if (p->P == 0) return GSR_OK;
+    if (!radii || !geom) return fail(GSR_ERR_INVALID, "[gsr] backward_view_stats: a required pointer is NULL");
+    if (!grad_norm_sum && !visible_views && !max_radius && !dL_dmean2D_views && !dL_dcolor_views && !dL_dopacity_views)
+        return fail(GSR_ERR_INVALID, "[gsr] backward_view_stats: all six outputs are NULL: nothing to write");
+    if (((uintptr_t)dL_dmean2D_views & 7u) != 0)
+        return fail(GSR_ERR_INVALID, "[gsr] backward_view_stats: dL_dmean2D_views is not 8-byte aligned (its rows leave as 8-B stores)");
+    FrameRecord r;
+    if (find_frame(geom, r)) {   // (no record: the call goes ahead, like gsr_backward_cameras)
+        if (!r.need_backward)
+            return fail(GSR_ERR_INVALID, "[gsr] backward_view_stats: the last %s on this geometry arena had need_backward = 0: there are "
+                        "no gradient records", r.kind == 2 ? "gsr_forward_recolor" : "forward");
+        if (!r.bwd_done)
+            return fail(GSR_ERR_INVALID, "[gsr] backward_view_stats: no backward has run since the last forward or recolor on this "
+                        "geometry arena (the gradient records are empty; run one of the gsr_backward entries first)");
+        if (r.V != V || r.P != p->P || r.W != p->W || r.H != p->H)
+            return fail(GSR_ERR_INVALID, "[gsr] backward_view_stats: V = %d, P = %d, %d x %d, but the last forward or recolor on this "
+                        "geometry arena had V = %d, P = %d, %d x %d", V, p->P, p->W, p->H, r.V, r.P, r.W, r.H);
+    }
+    Batch B;
+    if (int e = make_geom_batch(p, V, const_cast<void*>(geom), geom_bytes, true, B)) return e;
+    const Launch L{(hipStream_t)stream, p->debug};
+    ProfScope ps("view_stats", L.stream);
+    return launch_view_stats(L, p->P, B, radii, accumulate, grad_norm_sum, visible_views, max_radius, dL_dmean2D_views,
+                             dL_dcolor_views, dL_dopacity_views);
+}
+
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,
                      gsr_stream_t stream)
 {

@@ -529,6 +529,11 @@ inline size_t camera_slab_bytes(int V, int P) { return (size_t)V * (size_t)camer
 int launch_camera_partials(const Launch& L, const gsr_params& p, const Batch& B, const int* radii, double* slab);
 int launch_camera_sum(const Launch& L, int V, int P, int with_campos, const double* slab, float* dL_dview, float* dL_dproj, float* dL_dcampos);
 
+// view_stats.hip: density-control statistics over the views and the per-view shares of dL/d mean2D, colour
+// and opacity, from the same records.  One launch, one thread per Gaussian; every output pointer may be NULL (not all of them).
+int launch_view_stats(const Launch& L, int P, const Batch& B, const int* radii, int accumulate, float* grad_norm_sum,
+                      int* visible_views, int* max_radius, float* dL_dmean2D_views, float* dL_dcolor_views, float* dL_dopacity_views);
+
 // device helper: clear [p, p + bytes) (16-B aligned, multiple of 16) with the calling grid's threads
 __device__ __forceinline__ void zero_region(char* p, size_t bytes, size_t gtid, size_t nthreads)
 {

@@ -337,6 +337,79 @@ def rasterize_views(means3D, means2D, opacities, settings_list, shs=None, colors
                                           list(settings_list))
 
 
+class DensityStats:
+    """The running accumulators of adaptive density control (split / clone / prune) for a cloud of P Gaussians, fed by
+    rasterize_views_stats: per Gaussian, over every view of every backward since the last reset(),
+        grad_norm_sum  float32 [P]  sum of the norms of the screen-space gradient dL/dmean2D of each view (pixel units)
+        visible_views  int32   [P]  views in which the Gaussian was visible (radius > 0)
+        max_radius     int32   [P]  its largest screen radius
+    keep_view_grads: each backward also leaves its per-view gradients in `view_grads`, a dict of mean2D [V,P,2], color [V,P,3] and
+    opacity [V,P] (None until such a backward has run; replaced, not accumulated, by the next one)."""
+
+    def __init__(self, P, device, keep_view_grads=False):
+        self.P, self.device, self.keep_view_grads = int(P), torch.device(device), bool(keep_view_grads)
+        self.grad_norm_sum = torch.zeros((self.P,), dtype=torch.float32, device=self.device)
+        self.visible_views = torch.zeros((self.P,), dtype=torch.int32, device=self.device)
+        self.max_radius = torch.zeros((self.P,), dtype=torch.int32, device=self.device)
+        self.view_grads = None
+
+    def reset(self):
+        """Zero the three accumulators in place and drop the per-view gradients (after a densification step)."""
+        self.grad_norm_sum.zero_()
+        self.visible_views.zero_()
+        self.max_radius.zero_()
+        self.view_grads = None
+
+    def mean_grad(self):
+        """grad_norm_sum / max(visible_views, 1): the average screen-space gradient norm per view that saw the Gaussian."""
+        return self.grad_norm_sum / self.visible_views.clamp(min=1).to(torch.float32)
+
+
+class _RasterizeGaussiansViewsStats(torch.autograd.Function):
+    """_RasterizeGaussiansViews whose backward also feeds a DensityStats: the same native calls, so images, radii and gradients are
+    those of rasterize_views bit for bit, and one more call after the colour backward (C ABI gsr_backward_view_stats)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings_list, stats):
+        ctx.stats = stats
+        return _RasterizeGaussiansViews.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                                cov3Ds_precomp, settings_list)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _):
+        grads = _RasterizeGaussiansViews.backward(ctx, grad_out_color, _)
+        rs, st = ctx.raster_settings, ctx.stats
+        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, _b, _i, view, proj, cam) = ctx.saved_tensors
+        # the gradient records of the backward above are still in the arenas: one pass over them per Gaussian
+        g = _C.backward_view_stats(rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view,
+                                   proj, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree, cam, geomBuffer,
+                                   rs.debug, accumulate=True, grad_norm_sum=st.grad_norm_sum, visible_views=st.visible_views,
+                                   max_radius=st.max_radius, view_grads=st.keep_view_grads)
+        if st.keep_view_grads:
+            st.view_grads = dict(mean2D=g[0], color=g[1], opacity=g[2])
+        return grads + (None,)
+
+
+def rasterize_views_stats(means3D, means2D, opacities, settings_list, stats, shs=None, colors_precomp=None, scales=None,
+                          rotations=None, cov3D_precomp=None):
+    """rasterize_views for a training loop with adaptive density control: the same (colors [V,3,H,W], radii [V,P]) and the same
+    gradients, bit for bit, and every backward adds its views to `stats` (a DensityStats for this cloud): the sum over the views of
+    the NORM of each view's dL/dmean2D -- which the summed means2D.grad cannot give: gradients from opposite views cancel in it --,
+    the visibility count and the largest radius; with stats.keep_view_grads also the per-view dL/dmean2D, dL/dcolor, dL/dopacity.
+    Without an input that needs a gradient no backward runs and `stats` stays as it is."""
+    if len(settings_list) == 0:
+        raise Exception("rasterize_views_stats: empty settings list")
+    _check_sources(shs, colors_precomp, scales, rotations, cov3D_precomp)
+    if not isinstance(stats, DensityStats):
+        raise Exception("rasterize_views_stats: stats must be a DensityStats")
+    if stats.P != means3D.shape[0] or stats.grad_norm_sum.device != means3D.device:
+        raise Exception("rasterize_views_stats: stats was built for %d Gaussians on %s, the cloud has %d on %s"
+                        % (stats.P, stats.grad_norm_sum.device, means3D.shape[0], means3D.device))
+    shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales, rotations, cov3D_precomp)
+    return _RasterizeGaussiansViewsStats.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                                               list(settings_list), stats)
+
+
 class _RasterizeGaussiansViewsCameras(torch.autograd.Function):
     """_RasterizeGaussiansViews with the cameras as autograd inputs: view / proj [V,4,4] and cam [V,3] on the device instead of the
     settings' own matrix fields.  The same native calls, so images and cloud gradients are those of rasterize_views bit for bit;

@@ -65,6 +65,7 @@ _DECL = {
     "gsr_backward": (_int, [_pp, _fp, _i64] + _ARENAS + [_fp] * 9 + [_fp]),
     "gsr_camera_grad_bytes": (_size, [_int, _int]),
     "gsr_backward_cameras": (_int, [_pp, _int, _fp, _fp, _size, _fp, _fp, _fp, _fp, _size, _fp]),
+    "gsr_backward_view_stats": (_int, [_pp, _int, _fp, _fp, _size, _int, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "gsr_mark_visible": (_int, [_int, _fp, _fp, _fp, _fp, _fp]),
     "gsr_query": (_int, [_pp, _int, _fp, _fp, _size, _fp, _i64, _fp, _size, _fp]),
     "gsr_set_profiling": (None, [_int]),
@@ -212,8 +213,9 @@ def set_reference_lists(on):
 # bit-identical gradients from call to call and from process to process for the same inputs and call shape (not across different
 # numbers of views per call), for a scratch block per backward and the time of a sort and an ordered reduction.
 _DETERMINISTIC = [{"0": False, "1": True}.get(os.environ.get("GSR_DETERMINISTIC", "").strip())]
-# backwards issued through each entry (tests): the colour ones, the deterministic channels backward, and the camera gradients
-CALLS = dict(backward=0, backward_det=0, backward_channels_det=0, backward_cameras=0)
+# backwards issued through each entry (tests): the colour ones, the deterministic channels backward, the camera gradients and the
+# view statistics
+CALLS = dict(backward=0, backward_det=0, backward_channels_det=0, backward_cameras=0, backward_view_stats=0)
 
 
 def set_deterministic(flag):
@@ -888,6 +890,54 @@ def backward_cameras(background, means3D, radii, colors, scales, rotations, scal
                                             scratch.numel(), _stream_handle(device)))
             del keep
     return out
+
+
+def _stats_out(t, shape, dtype, device, name):
+    """an output of backward_view_stats handed over by the caller: the library writes into it in place"""
+    if t is None:
+        return None
+    if tuple(t.shape) != shape or t.dtype != dtype or t.device != device or not t.is_contiguous():
+        raise RuntimeError("backward_view_stats: %s must be a contiguous %s tensor of shape %s on %s (got %s %s on %s)"
+                           % (name, dtype, shape, device, t.dtype, tuple(t.shape), t.device))
+    return t
+
+
+def backward_view_stats(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
+                        projmatrices, tan_fovx, tan_fovy, image_height, image_width, sh, degree, camposs, geomBuffer, debug=False,
+                        accumulate=True, grad_norm_sum=None, visible_views=None, max_radius=None, view_grads=False, _out=None):
+    """Density-control statistics and per-view gradients of the last backward on `geomBuffer` (C ABI gsr_backward_view_stats): the
+    arguments of that backward, radii [V,P].  grad_norm_sum (float32 [P]), visible_views, max_radius (int32 [P]): the caller's
+    tensors, updated in place (accumulate) or overwritten; None: not computed.  view_grads: also return the per-view shares
+    (dL_dmean2D [V,P,2], dL_dcolor [V,P,3], dL_dopacity [V,P]), else None.  _out: the three share tensors, any of them None (tests
+    hand over prefilled ones and subsets; default with view_grads: three fresh tensors)."""
+    device = means3D.device
+    _require_hip(device)
+    P, V = means3D.shape[0], viewmatrices.numel() // 16
+    i32 = torch.int32
+    stats = (_stats_out(grad_norm_sum, (P,), _F32, device, "grad_norm_sum"), _stats_out(visible_views, (P,), i32, device, "visible_views"),
+             _stats_out(max_radius, (P,), i32, device, "max_radius"))
+    shapes = ((V, P, 2), (V, P, 3), (V, P))
+    if _out is not None:
+        shares = tuple(_stats_out(t, s, _F32, device, n) for t, s, n in zip(_out, shapes, ("dL_dmean2D_views", "dL_dcolor_views",
+                                                                                           "dL_dopacity_views")))
+    elif view_grads:
+        new = torch.empty if P != 0 else torch.zeros
+        shares = tuple(new(s, dtype=_F32, device=device) for s in shapes)
+    else:
+        shares = (None, None, None)
+    if P != 0:
+        CALLS["backward_view_stats"] += 1
+        with _on_device(device):
+            # (opacity lives in the geom arena; the pointer only has to be non-NULL: means3D stands in)
+            p, keep = _params(background, means3D, colors, means3D, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
+                              projmatrices, tan_fovx, tan_fovy, int(image_height), int(image_width), sh, degree, camposs, False, debug,
+                              True)
+            radii_c = radii.contiguous()
+            _check(lib.gsr_backward_view_stats(C.byref(p), V, radii_c.data_ptr(), geomBuffer.data_ptr(), geomBuffer.numel(),
+                                               int(bool(accumulate)), *[None if t is None else t.data_ptr() for t in stats + shares],
+                                               _stream_handle(device)))
+            del keep
+    return shares if (view_grads or _out is not None) else None
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,

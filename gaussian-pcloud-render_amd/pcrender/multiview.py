@@ -85,6 +85,16 @@ def reduce_gradients(grads, group=None):
     return grads
 
 
+def reduce_density_stats(stats, group=None):
+    """Combine the density-control accumulators (diff_gaussian_rasterization.DensityStats) of a shared cloud over ranks, in place:
+    the gradient-norm sums and visibility counts of the ranks' views add up, the largest radius is the largest over the ranks."""
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        dist.all_reduce(stats.grad_norm_sum, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(stats.visible_views, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(stats.max_radius, op=dist.ReduceOp.MAX, group=group)
+    return stats
+
+
 def render_views(render_one, n_views, dst=0, group=None, mode="collective"):
     """render_one(view_id) -> [3,H,W] tensor.  Renders this rank's shard, gathers every frame on `dst`."""
     if dist.is_available() and dist.is_initialized():

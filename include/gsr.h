@@ -173,7 +173,7 @@ int gsr_forward_stage2(const gsr_params* p, void* geom, size_t geom_bytes, void*
  * mask), so a backward afterwards -- called with the SAME colour inputs -- differentiates the LAST colours rendered; with
  * need_backward = 0 a backward after the recolor is not supported (gsr_backward_batch refuses it).  A backward after a
  * colors_per_view recolor is called with colors_precomp = the [V,P,3] colours and returns dL_dcolor [P,3] SUMMED over the views
- * (like every per-Gaussian gradient); the per-view shares are not separated. */
+ * (like every per-Gaussian gradient); gsr_backward_view_stats after that backward separates the per-view shares (dL_dcolor_views). */
 int gsr_forward_recolor(const gsr_params* p, int V, int colors_per_view, void* geom, size_t geom_bytes, const void* binning,
                         size_t binning_bytes, void* image, size_t image_bytes, float* out_color, gsr_stream_t stream);
 
@@ -313,6 +313,41 @@ size_t gsr_camera_grad_bytes(int V, int P);
 int gsr_backward_cameras(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes,
                          float* dL_dviewmatrix /* [V][16] */, float* dL_dprojmatrix /* [V][16] */, float* dL_dcampos /* [V][3] */,
                          void* scratch, size_t scratch_bytes, gsr_stream_t stream);
+
+/* Density-control statistics and per-view gradients of a view batch.  Every backward returns the per-Gaussian gradients SUMMED over
+ * the V views; adaptive density control (split / clone / prune) wants, per Gaussian, the sum over the views of the NORM of the
+ * screen-space gradient -- which is not the norm of the sum: gradients from opposite views cancel inside dL_dmean2D --, the number
+ * of views that saw the Gaussian and its largest screen radius; per-view appearance wants the colour and opacity gradients view by
+ * view.  A separate call that runs AFTER a backward on the same arenas -- gsr_backward_batch, gsr_backward_batch_det, gsr_backward,
+ * gsr_backward_batch_channels or gsr_backward_batch_channels_det, in either arithmetic mode -- with that backward's p, V and radii.
+ * It reads radii and the per-view gradient records the backward left behind the geometry arenas and changes
+ * nothing in the arenas, so it may be repeated, and may come before or after gsr_backward_cameras.  With (gx, gy) the record's
+ * mean2D words of Gaussian i in view v (pixel units, like dL_dmean2D):
+ *   grad_norm_sum[i] = sum_{v = 0 .. V-1} sqrt(gx^2 + gy^2): every term and the running sum in float64 from the float32 words, views
+ *                      ascending, rounded to float32 once; a view in which the Gaussian is invisible or unreached adds an exact zero
+ *   visible_views[i] = the number of views with radii[v][i] > 0
+ *   max_radius[i]    = max_v radii[v][i], 0 when the Gaussian is visible nowhere
+ * accumulate = 0 overwrites the three; accumulate != 0 updates the caller's running values in place, what a trainer keeps between two
+ * densification steps: grad_norm_sum[i] = float32(double(old) + sum), visible_views[i] += count, max_radius[i] = max(old, new).
+ *   dL_dmean2D_views [V][P][2], dL_dcolor_views [V][P][3], dL_dopacity_views [V][P]: the record's words of every Gaussian and view,
+ *   bit for bit, zeros where nothing was accumulated; ALWAYS overwritten (accumulate does not apply to them).
+ * Adding the shares in float32 for v = 0, 1, .. V-1, starting from +0, reproduces the backward's dL_dmean2D[:, 0:2], dL_dcolor and
+ * dL_dopacity bit for bit: that is the order in which the backward adds them.  After a colors_per_view recolor plus backward,
+ * dL_dcolor_views[v] is the gradient of view v's own colours.  After a channels backward the mean2D and opacity shares carry the extra
+ * channels' part, like the summed outputs.  Each of the six outputs may be NULL (not all of them); a call for the statistics alone
+ * reads 16 B of every record, one with grad_norm_sum = NULL and no shares reads radii only.  One kernel, one thread per Gaussian: no
+ * atomics, no scratch, no device->host read-back, no allocation; the result is a function of the records and radii alone --
+ * bit-reproducible after gsr_backward_batch_det / _channels_det, and the same bits again when the call is repeated.
+ * Checks, in this order: the parameters (as every entry); P == 0 -> GSR_OK, nothing written; a NULL radii or geom -> GSR_ERR_INVALID;
+ * all six outputs NULL -> GSR_ERR_INVALID; dL_dmean2D_views not 8-byte aligned -> GSR_ERR_INVALID (its rows leave as 8-byte stores);
+ * then the arena's record -> GSR_ERR_INVALID when the last forward or recolor on `geom` had need_backward = 0, when no backward has
+ * run since it, or when V, P, W or H differ from it (the outputs are then untouched; an arena without a record is not checked); then
+ * the size of the geometry allocation (GSR_ERR_CAPACITY). */
+int gsr_backward_view_stats(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, int accumulate,
+                            float* grad_norm_sum /* [P] or NULL */, int* visible_views /* [P] or NULL */,
+                            int* max_radius /* [P] or NULL */, float* dL_dmean2D_views /* [V][P][2] or NULL */,
+                            float* dL_dcolor_views /* [V][P][3] or NULL */, float* dL_dopacity_views /* [V][P] or NULL */,
+                            gsr_stream_t stream);
 
 /* Pairs in the lists of the calling thread's last forward call, per view (out[V], HOST array): what a binning arena has to
  * hold.  Equal to num_rendered with reference_lists = 1. */
