@@ -906,6 +906,39 @@ int gsr_backward_view_stats(const gsr_params* p, int V, const int* radii, const 
                              dL_dcolor_views, dL_dopacity_views);
 }
 
+// ---- per-Gaussian contribution statistics: a read-only walk of the forward's lists (contrib_stats.hip) ----
+int gsr_contrib_stats(const gsr_params* p, int V, const int* radii, const void* geom, size_t geom_bytes, const void* binning,
+                      size_t binning_bytes, const void* image, size_t image_bytes, const float* pixel_weights, int accumulate,
+                      float* weight_sum, float* weight_max, int* pixel_count, int* dominant_count, gsr_stream_t stream)
+{
+    (void)radii;   // a Gaussian that is invisible in a view is in none of its lists
+    if (int e = check_params(p, V)) return e;
+    if (p->P == 0) return GSR_OK;
+    if (!geom || !binning || !image) return fail(GSR_ERR_INVALID, "[gsr] contrib_stats: a required pointer is NULL");
+    if (!weight_sum && !weight_max && !pixel_count && !dominant_count)
+        return fail(GSR_ERR_INVALID, "[gsr] contrib_stats: all four outputs are NULL: nothing to write");
+    FrameRecord r;
+    if (find_frame(geom, r)) {   // (no record: the call goes ahead; the record is only read)
+        if (r.V != V || r.P != p->P || r.W != p->W || r.H != p->H)
+            return fail(GSR_ERR_INVALID, "[gsr] contrib_stats: V = %d, P = %d, %d x %d, but the last forward or recolor on this "
+                        "geometry arena had V = %d, P = %d, %d x %d", V, p->P, p->W, p->H, r.V, r.P, r.W, r.H);
+    }
+    Batch B;
+    if (int e = make_batch(p, V, const_cast<void*>(geom), geom_bytes, const_cast<void*>(image), image_bytes,
+                           const_cast<void*>(binning), binning_bytes, false, B))
+        return e;
+    const Launch L{(hipStream_t)stream, p->debug};
+    ProfScope ps("contrib_stats", L.stream);
+    if (!accumulate) {
+        void* const outs[4] = {weight_sum, weight_max, pixel_count, dominant_count};
+        for (void* o : outs)
+            if (o && hipMemsetAsync(o, 0, (size_t)p->P * 4, L.stream) != hipSuccess)
+                return fail(GSR_ERR_HIP, "[gsr] memset failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    return launch_contrib_stats(L, *p, B, B.b.val[sorted_buffer(tile_count(p))], pixel_weights, weight_sum, weight_max, pixel_count,
+                                dominant_count);
+}
+
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,
                      gsr_stream_t stream)
 {

@@ -534,6 +534,12 @@ int launch_camera_sum(const Launch& L, int V, int P, int with_campos, const doub
 int launch_view_stats(const Launch& L, int P, const Batch& B, const int* radii, int accumulate, float* grad_norm_sum,
                       int* visible_views, int* max_radius, float* dL_dmean2D_views, float* dL_dcolor_views, float* dL_dopacity_views);
 
+// contrib_stats.hip: per-Gaussian blend-weight statistics from one read-only walk of a forward's lists, always in
+// the exact arithmetic.  One launch; every output pointer may be NULL (not all of them); the outputs are accumulated into with atomics,
+// so the caller clears them first unless it keeps running values.
+int launch_contrib_stats(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, const float* pixel_weights,
+                         float* weight_sum, float* weight_max, int* pixel_count, int* dominant_count);
+
 // device helper: clear [p, p + bytes) (16-B aligned, multiple of 16) with the calling grid's threads
 __device__ __forceinline__ void zero_region(char* p, size_t bytes, size_t gtid, size_t nthreads)
 {

@@ -410,6 +410,73 @@ def rasterize_views_stats(means3D, means2D, opacities, settings_list, stats, shs
                                                list(settings_list), stats)
 
 
+class ContributionStats:
+    """The running accumulators of importance-based pruning and compaction for a cloud of P Gaussians, fed by
+    rasterize_views_contrib: per Gaussian, over every pixel of every view since the last reset(), with w = alpha T the blend weight
+    of the Gaussian at a pixel it contributes to,
+        weight_sum      float32 [P]  sum of w (times the pixel's weight, with a weight map)
+        weight_max      float32 [P]  largest w (times the pixel's weight)
+        pixel_count     int32   [P]  pixels it contributed to
+        dominant_count  int32   [P]  pixels at which its w was the largest
+    and pixels_seen, a Python int: V * H * W added per call, for normalising."""
+
+    def __init__(self, P, device):
+        self.P, self.device = int(P), torch.device(device)
+        self.weight_sum = torch.zeros((self.P,), dtype=torch.float32, device=self.device)
+        self.weight_max = torch.zeros((self.P,), dtype=torch.float32, device=self.device)
+        self.pixel_count = torch.zeros((self.P,), dtype=torch.int32, device=self.device)
+        self.dominant_count = torch.zeros((self.P,), dtype=torch.int32, device=self.device)
+        self.pixels_seen = 0
+
+    def reset(self):
+        """Zero the four accumulators in place and pixels_seen (after a pruning step)."""
+        self.weight_sum.zero_()
+        self.weight_max.zero_()
+        self.pixel_count.zero_()
+        self.dominant_count.zero_()
+        self.pixels_seen = 0
+
+    def mean_weight(self):
+        """weight_sum / max(pixel_count, 1): the average blend weight over the pixels the Gaussian contributed to."""
+        return self.weight_sum / self.pixel_count.clamp(min=1).to(torch.float32)
+
+
+def rasterize_views_contrib(means3D, means2D, opacities, settings_list, stats, pixel_weights=None, shs=None, colors_precomp=None,
+                            scales=None, rotations=None, cov3D_precomp=None):
+    """rasterize_views for an importance-pruning pass: the same (colors [V,3,H,W], radii [V,P]), bit for bit, under no_grad, and the
+    views' blend weights added to `stats` (a ContributionStats for this cloud) by one more native call on the forward's arenas
+    (C ABI gsr_contrib_stats).  pixel_weights: float32 [V,H,W] on the cloud's device, the weight of every pixel (a value that is not
+    > 0 masks its pixel out), or None for 1 everywhere."""
+    if len(settings_list) == 0:
+        raise Exception("rasterize_views_contrib: empty settings list")
+    _check_sources(shs, colors_precomp, scales, rotations, cov3D_precomp)
+    if not isinstance(stats, ContributionStats):
+        raise Exception("rasterize_views_contrib: stats must be a ContributionStats")
+    if stats.P != means3D.shape[0] or stats.weight_sum.device != means3D.device:
+        raise Exception("rasterize_views_contrib: stats was built for %d Gaussians on %s, the cloud has %d on %s"
+                        % (stats.P, stats.weight_sum.device, means3D.shape[0], means3D.device))
+    rs, V = settings_list[0], len(settings_list)
+    if pixel_weights is not None and (not isinstance(pixel_weights, torch.Tensor) or pixel_weights.dtype != torch.float32
+                                      or tuple(pixel_weights.shape) != (V, rs.image_height, rs.image_width)
+                                      or pixel_weights.device != means3D.device):
+        raise Exception("rasterize_views_contrib: pixel_weights must be a float32 tensor of shape [%d, %d, %d] on %s"
+                        % (V, rs.image_height, rs.image_width, means3D.device))
+    shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales, rotations, cov3D_precomp)
+    with torch.no_grad():
+        view, proj, cam = _stack_views(settings_list, means3D.device)
+        debug = any(s.debug for s in settings_list)
+        _counts, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians_batch(
+            rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3D_precomp, view, proj,
+            rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, shs, rs.sh_degree, cam, rs.prefiltered, debug,
+            need_backward=False)
+        _C.contrib_stats(rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3D_precomp, view, proj,
+                         rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, shs, rs.sh_degree, cam, geomBuffer, binningBuffer,
+                         imgBuffer, debug, accumulate=True, pixel_weights=pixel_weights, weight_sum=stats.weight_sum,
+                         weight_max=stats.weight_max, pixel_count=stats.pixel_count, dominant_count=stats.dominant_count)
+        stats.pixels_seen += V * int(rs.image_height) * int(rs.image_width)
+    return color, radii
+
+
 class _RasterizeGaussiansViewsCameras(torch.autograd.Function):
     """_RasterizeGaussiansViews with the cameras as autograd inputs: view / proj [V,4,4] and cam [V,3] on the device instead of the
     settings' own matrix fields.  The same native calls, so images and cloud gradients are those of rasterize_views bit for bit;

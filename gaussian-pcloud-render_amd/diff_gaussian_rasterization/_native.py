@@ -66,6 +66,7 @@ _DECL = {
     "gsr_camera_grad_bytes": (_size, [_int, _int]),
     "gsr_backward_cameras": (_int, [_pp, _int, _fp, _fp, _size, _fp, _fp, _fp, _fp, _size, _fp]),
     "gsr_backward_view_stats": (_int, [_pp, _int, _fp, _fp, _size, _int, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "gsr_contrib_stats": (_int, [_pp, _int, _fp] + _ARENAS + [_fp, _int, _fp, _fp, _fp, _fp, _fp]),
     "gsr_mark_visible": (_int, [_int, _fp, _fp, _fp, _fp, _fp]),
     "gsr_query": (_int, [_pp, _int, _fp, _fp, _size, _fp, _i64, _fp, _size, _fp]),
     "gsr_set_profiling": (None, [_int]),
@@ -214,8 +215,8 @@ def set_reference_lists(on):
 # numbers of views per call), for a scratch block per backward and the time of a sort and an ordered reduction.
 _DETERMINISTIC = [{"0": False, "1": True}.get(os.environ.get("GSR_DETERMINISTIC", "").strip())]
 # backwards issued through each entry (tests): the colour ones, the deterministic channels backward, the camera gradients and the
-# view statistics
-CALLS = dict(backward=0, backward_det=0, backward_channels_det=0, backward_cameras=0, backward_view_stats=0)
+# view statistics; and the contribution statistics, which follow a forward
+CALLS = dict(backward=0, backward_det=0, backward_channels_det=0, backward_cameras=0, backward_view_stats=0, contrib_stats=0)
 
 
 def set_deterministic(flag):
@@ -938,6 +939,51 @@ def backward_view_stats(background, means3D, radii, colors, scales, rotations, s
                                                _stream_handle(device)))
             del keep
     return shares if (view_grads or _out is not None) else None
+
+
+def _contrib_out(t, dtype, P, device, name):
+    """an output of contrib_stats handed over by the caller: the library accumulates into it in place"""
+    if t is None:
+        return None
+    if tuple(t.shape) != (P,) or t.dtype != dtype or t.device != device or not t.is_contiguous():
+        raise RuntimeError("contrib_stats: %s must be a contiguous %s tensor of shape %s on %s (got %s %s on %s)"
+                           % (name, dtype, (P,), device, t.dtype, tuple(t.shape), t.device))
+    return t
+
+
+def contrib_stats(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices,
+                  tan_fovx, tan_fovy, image_height, image_width, sh, degree, camposs, geomBuffer, binningBuffer, imageBuffer,
+                  debug=False, accumulate=True, pixel_weights=None, weight_sum=None, weight_max=None, pixel_count=None,
+                  dominant_count=None):
+    """Per-Gaussian contribution statistics of the last forward or recolor on the three arenas (C ABI gsr_contrib_stats): the
+    arguments of that forward, radii [V,P] or None.  weight_sum, weight_max (float32 [P]), pixel_count, dominant_count (int32 [P]):
+    the caller's tensors, updated in place (accumulate) or overwritten; None: not computed.  pixel_weights: float32 [V,H,W] on the
+    device or None."""
+    device = means3D.device
+    _require_hip(device)
+    P, V = means3D.shape[0], viewmatrices.numel() // 16
+    H, W = int(image_height), int(image_width)
+    i32 = torch.int32
+    outs = (_contrib_out(weight_sum, _F32, P, device, "weight_sum"), _contrib_out(weight_max, _F32, P, device, "weight_max"),
+            _contrib_out(pixel_count, i32, P, device, "pixel_count"), _contrib_out(dominant_count, i32, P, device, "dominant_count"))
+    if pixel_weights is not None and (tuple(pixel_weights.shape) != (V, H, W) or pixel_weights.dtype != _F32
+                                      or pixel_weights.device != device):
+        raise RuntimeError("contrib_stats: pixel_weights must be a %s tensor of shape %s on %s (got %s %s on %s)"
+                           % (_F32, (V, H, W), device, pixel_weights.dtype, tuple(pixel_weights.shape), pixel_weights.device))
+    if P != 0:
+        CALLS["contrib_stats"] += 1
+        with _on_device(device):
+            # (opacity lives in the geom arena; the pointer only has to be non-NULL: means3D stands in)
+            p, keep = _params(background, means3D, colors, means3D, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
+                              projmatrices, tan_fovx, tan_fovy, H, W, sh, degree, camposs, False, debug, False)
+            radii_c = None if radii is None else radii.contiguous()
+            pw = None if pixel_weights is None else pixel_weights.contiguous()
+            _check(lib.gsr_contrib_stats(C.byref(p), V, _ptr(radii_c), geomBuffer.data_ptr(), geomBuffer.numel(),
+                                         binningBuffer.data_ptr(), binningBuffer.numel(), imageBuffer.data_ptr(), imageBuffer.numel(),
+                                         _ptr(pw), int(bool(accumulate)), *[None if t is None else t.data_ptr() for t in outs],
+                                         _stream_handle(device)))
+            del keep, pw
+    return None
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,

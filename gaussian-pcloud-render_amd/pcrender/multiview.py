@@ -95,6 +95,20 @@ def reduce_density_stats(stats, group=None):
     return stats
 
 
+def reduce_contribution_stats(stats, group=None):
+    """Combine the contribution accumulators (diff_gaussian_rasterization.ContributionStats) of a shared cloud over ranks, in place:
+    the weight sums, the two pixel counts and pixels_seen of the ranks' views add up, the largest weight is the largest over the ranks."""
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        dist.all_reduce(stats.weight_sum, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(stats.pixel_count, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(stats.dominant_count, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(stats.weight_max, op=dist.ReduceOp.MAX, group=group)
+        seen = [None] * dist.get_world_size(group)
+        dist.all_gather_object(seen, int(stats.pixels_seen), group=group)
+        stats.pixels_seen = sum(seen)
+    return stats
+
+
 def render_views(render_one, n_views, dst=0, group=None, mode="collective"):
     """render_one(view_id) -> [3,H,W] tensor.  Renders this rank's shard, gathers every frame on `dst`."""
     if dist.is_available() and dist.is_initialized():

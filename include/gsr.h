@@ -349,6 +349,39 @@ int gsr_backward_view_stats(const gsr_params* p, int V, const int* radii, const 
                             float* dL_dcolor_views /* [V][P][3] or NULL */, float* dL_dopacity_views /* [V][P] or NULL */,
                             gsr_stream_t stream);
 
+/* Per-Gaussian contribution statistics of a view batch: what importance-based pruning and compaction rank a Gaussian by.  One
+ * read-only walk of the lists of the last forward (gsr_forward_batch, gsr_forward, the stage pair, a channels forward) or
+ * gsr_forward_recolor on the same arenas, with that call's V, P, W and H -- valid with either value of need_backward, before or after
+ * a backward, any number of times: it reads the projected splat records, the sorted tile lists and the ranges, and writes nothing
+ * into the arenas (not the consumed-entry counts, not the gradient records, none of a backward's saves).  It composites front to back
+ * exactly like the exact-mode forward: an entry with power > 0 or alpha < 1/255 is skipped, the entry with T (1 - alpha) < 1e-4 stops
+ * its pixel and is not blended, pixels outside the image do not exist.  The arithmetic is ALWAYS the exact mode's, whatever
+ * gsr_set_render_math and gsr_set_train_math say.  With T the transmittance in front of entry i at a pixel, w = alpha T its blend
+ * weight there, and m the pixel's weight -- pixel_weights[v][y][x], or 1 without a map; a value with !(m > 0) (zero, negative, NaN)
+ * is 0, and a pixel with m = 0 is left out of all four statistics (a mask):
+ *   weight_sum[i]     = the sum over the (view, pixel) contributions of Gaussian i of w m
+ *   weight_max[i]     = the largest w m among them (0 without a contribution)
+ *   pixel_count[i]    = their number, unweighted
+ *   dominant_count[i] = the number of (view, pixel) at which i has the largest unweighted w (strictly: the front-most entry wins a tie;
+ *                       a pixel nothing contributes to counts for nobody)
+ * radii ([V][P], may be NULL) is not read: a Gaussian with radii[v][i] == 0 is in no list of view v and gets zeros from it.
+ * accumulate = 0 clears the requested outputs first, on the stream; accumulate != 0 keeps the caller's running values: weight_sum and
+ * the two counts are added to, weight_max becomes the maximum of old and new (the old values are non-negative floats).  Each of the
+ * four outputs may be NULL (not all of them).  One kernel (contrib_stats.hip): an entry's per-pixel values are
+ * reduced inside the wave that walks the quadrant, then one atomic per statistic per (wave, entry).  weight_max, pixel_count and
+ * dominant_count are bit-reproducible -- a maximum and integer sums do not depend on the order --; weight_sum is NOT: float atomics
+ * add in the order the waves arrive (each result is the float32 sum of the same terms in some order).  No allocation, no
+ * device->host read-back, no host wait.
+ * Checks, in this order: the parameters (as every entry); P == 0 -> GSR_OK, nothing written; a NULL geom, binning or image ->
+ * GSR_ERR_INVALID; all four outputs NULL -> GSR_ERR_INVALID; then the arena's record -> GSR_ERR_INVALID when V, P, W or H differ from
+ * the last forward or recolor on `geom` (the outputs are then untouched; an arena without a record is not checked; the record is read,
+ * never written); then the sizes of the three allocations (GSR_ERR_CAPACITY). */
+int gsr_contrib_stats(const gsr_params* p, int V, const int* radii /* [V][P], may be NULL */, const void* geom, size_t geom_bytes,
+                      const void* binning, size_t binning_bytes, const void* image, size_t image_bytes,
+                      const float* pixel_weights /* [V][H][W] or NULL */, int accumulate, float* weight_sum /* [P] or NULL */,
+                      float* weight_max /* [P] or NULL */, int* pixel_count /* [P] or NULL */, int* dominant_count /* [P] or NULL */,
+                      gsr_stream_t stream);
+
 /* Pairs in the lists of the calling thread's last forward call, per view (out[V], HOST array): what a binning arena has to
  * hold.  Equal to num_rendered with reference_lists = 1. */
 int gsr_last_list_pairs(int64_t* out, int V);
