@@ -272,6 +272,40 @@ static bool find_frame(const void* geom, FrameRecord& r)
     r = it->second;
     return true;
 }
+// read-modify-write of an arena's record under one lock (no record: nothing happens)
+template <class F> static void update_frame(const void* geom, F change)
+{
+    std::lock_guard<std::mutex> lk(g_frames_mu);
+    const auto it = g_frames.find(geom);
+    if (it != g_frames.end()) change(it->second);
+}
+
+// The one check of an arena's record for the entries that run on the arenas of a finished forward or recolor: `who` (the entry's
+// name in the messages) needs the last forward / recolor to have saved for a backward (GATE_SAVES; saves_tail ends that message),
+// a backward to have run since (GATE_RECORDS), and always the same V, P, W, H -- asked in this order.  Without a record (an arena
+// whose forward ran before the record table was last dropped, at more than 4096 arenas) the call goes ahead as it always did:
+// refusing it would break a valid call, and the callers' contract (gsr.h) is unchanged.  Returns through `out` (may be NULL) the
+// record, and through `known` whether there is one.
+enum { GATE_SAVES = 1, GATE_RECORDS = 2 };
+static int frame_gate(const char* who, const void* geom, const gsr_params* p, int V, int needs, const char* saves_tail,
+                      FrameRecord* out = nullptr, bool* known = nullptr)
+{
+    FrameRecord r;
+    const bool found = find_frame(geom, r);
+    if (out) *out = r;
+    if (known) *known = found;
+    if (!found) return GSR_OK;
+    if ((needs & GATE_SAVES) && !r.need_backward)
+        return fail(GSR_ERR_INVALID, "[gsr] %s: the last %s on this geometry arena had need_backward = 0%s", who,
+                    r.kind == 2 ? "gsr_forward_recolor" : "forward", saves_tail);
+    if ((needs & GATE_RECORDS) && !r.bwd_done)
+        return fail(GSR_ERR_INVALID, "[gsr] %s: no backward has run since the last forward or recolor on this geometry arena (the "
+                    "gradient records are empty; run one of the gsr_backward entries first)", who);
+    if (r.V != V || r.P != p->P || r.W != p->W || r.H != p->H)
+        return fail(GSR_ERR_INVALID, "[gsr] %s: V = %d, P = %d, %d x %d, but the last forward or recolor on this geometry arena "
+                    "had V = %d, P = %d, %d x %d", who, V, p->P, p->W, p->H, r.V, r.P, r.W, r.H);
+    return GSR_OK;
+}
 // per-view bytes of the extra-channel state for a binning arena of capacity cap
 static size_t xstate_view_bytes(int W, int H, int64_t cap, int nx) { return align_up(xstate_view(nullptr, W, H, cap, nx).bytes, 256); }
 
@@ -280,6 +314,13 @@ static int memset_views(hipStream_t s, void* base, size_t stride, size_t bytes, 
     if (bytes == 0) return GSR_OK;
     hipError_t e = V == 1 ? hipMemsetAsync(base, 0, bytes, s) : hipMemset2DAsync(base, stride, 0, bytes, (size_t)V, s);
     return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "[gsr] memset failed: %s", hipGetErrorString(e));
+}
+
+// one block to zero in stream order
+static int zero_async(hipStream_t s, void* dst, size_t bytes)
+{
+    if (hipMemsetAsync(dst, 0, bytes, s) == hipSuccess) return GSR_OK;
+    return fail(GSR_ERR_HIP, "[gsr] memset failed: %s", hipGetErrorString(hipGetLastError()));
 }
 
 // The whole forward for a batch.  mode 0: everything; 1 (resume): from the pair emission on, after a GSR_RETRY or a
@@ -422,14 +463,8 @@ static int forward_impl(const gsr_params* p, int V, void* geom, size_t geom_byte
         t_list_pairs[(size_t)v] = (int64_t)Lp;
         if (mode != 2 && (int64_t)Lp > B.b.cap) retry = true;
     }
-    {
-        // the lists' extent joins the arena's record (host data of the one read-back above: gsr_backward_batch_det sizes by it)
-        FrameRecord r;
-        if (find_frame(geom, r)) {
-            r.list_pairs = *std::max_element(t_list_pairs.begin(), t_list_pairs.end());
-            note_frame(geom, r);
-        }
-    }
+    // the lists' extent joins the arena's record (host data of the one read-back above: gsr_backward_batch_det sizes by it)
+    update_frame(geom, [](FrameRecord& r) { r.list_pairs = *std::max_element(t_list_pairs.begin(), t_list_pairs.end()); });
     if (retry) {
         fail(GSR_RETRY, "[gsr] binning arena holds %lld pairs per view, the frame needs more (num_rendered is enough; gsr_last_list_pairs is exact): repeat with resume = 1",
              (long long)B.b.cap);
@@ -611,46 +646,44 @@ static int check_bwd_pointers(const gsr_params* p, const int* radii, const void*
 }
 
 // The forward or recolor a backward differentiates has to have saved what it reads, for the same views and sizes.
-// Colour backward (x == NULL): without a record (an arena whose forward ran before the record table was last dropped, at more than
-// 4096 arenas) the call goes ahead as it always did: refusing it would break a valid backward, and the caller's contract (gsr.h) is
-// unchanged.  Channels backward: the record has to be that of a channels forward with need_backward = 1 into this extra-state
-// block, with the same channels, layout and sizes.  list_pairs: the record's (-1: none).  math: the arithmetic the saves were written
-// in, from the record; without one, the training switch in force (the caller then has to keep it where the forward had it).
+// Colour backward (x == NULL): frame_gate, and between its first and its last question a rule of this entry's own (a need_backward
+// recolor needs the arenas of a need_backward forward).  Channels backward: the record has to be that of a channels forward with
+// need_backward = 1 into this extra-state block, with the same channels, layout and sizes.  list_pairs: the record's (-1: none).
+// math: the arithmetic the saves were written in, from the record; without one, the training switch in force (the caller then has
+// to keep it where the forward had it).
 static int check_bwd_frame(const void* geom, const gsr_params* p, int V, const BwdExtra* x, int64_t* list_pairs, int* math)
 {
     FrameRecord r;
     *list_pairs = -1;
     *math = x ? 0 : train_math(-1);
+    if (!x) {
+        bool known = false;
+        const int e = frame_gate("backward", geom, p, V, GATE_SAVES, " and saved nothing for it", &r, &known);
+        if (!known) return GSR_OK;
+        *list_pairs = r.list_pairs;
+        *math = r.math;
+        if (r.need_backward && r.fwd_need_backward == 0)   // (comes before the gate's answer about the sizes)
+            return fail(GSR_ERR_INVALID, "[gsr] backward: the recolor's forward on this geometry arena had need_backward = 0 (a "
+                        "need_backward recolor needs the arenas of a need_backward forward)");
+        return e;
+    }
     if (!find_frame(geom, r))
-        return x ? fail(GSR_ERR_INVALID, "[gsr] backward_channels: no forward on this geometry arena (run gsr_forward_batch_channels_train first)")
-                 : GSR_OK;
+        return fail(GSR_ERR_INVALID, "[gsr] backward_channels: no forward on this geometry arena (run gsr_forward_batch_channels_train first)");
     *list_pairs = r.list_pairs;
     *math = r.math;
     const bool same = r.V == V && r.P == p->P && r.W == p->W && r.H == p->H;
-    if (x) {
-        if (r.kind == 2)
-            return fail(GSR_ERR_INVALID, "[gsr] backward_channels after gsr_forward_recolor is not supported: the recolor replaced the saves "
-                        "of the channels forward (run gsr_forward_batch_channels_train again)");
-        if (r.kind != 1 || !r.need_backward || r.xstate == nullptr)
-            return fail(GSR_ERR_INVALID, "[gsr] backward_channels: the forward on this arena saved no extra channels (it needs "
-                        "gsr_forward_batch_channels_train with need_backward = 1)");
-        if (r.nx != x->X.nx || r.layout != x->layout)
-            return fail(GSR_ERR_INVALID, "[gsr] backward_channels: nx = %d, extra_per_view = %d, but the forward had nx = %d, extra_per_view = %d",
-                        x->X.nx, x->layout, r.nx, r.layout);
-        if (!same) return fail(GSR_ERR_INVALID, "[gsr] backward_channels: views / sizes differ from the forward's");
-        if (r.xstate != x->state || x->state_bytes < r.xstate_bytes)
-            return fail(GSR_ERR_INVALID, "[gsr] backward_channels: extra_state is not the block the forward saved into");
-        return GSR_OK;
-    }
-    if (!r.need_backward)
-        return fail(GSR_ERR_INVALID, "[gsr] backward: the last %s on this geometry arena had need_backward = 0 and saved nothing for "
-                    "it", r.kind == 2 ? "gsr_forward_recolor" : "forward");
-    if (r.fwd_need_backward == 0)
-        return fail(GSR_ERR_INVALID, "[gsr] backward: the recolor's forward on this geometry arena had need_backward = 0 (a "
-                    "need_backward recolor needs the arenas of a need_backward forward)");
-    if (!same)
-        return fail(GSR_ERR_INVALID, "[gsr] backward: V = %d, P = %d, %d x %d, but the last forward or recolor on this geometry "
-                    "arena had V = %d, P = %d, %d x %d", V, p->P, p->W, p->H, r.V, r.P, r.W, r.H);
+    if (r.kind == 2)
+        return fail(GSR_ERR_INVALID, "[gsr] backward_channels after gsr_forward_recolor is not supported: the recolor replaced the saves "
+                    "of the channels forward (run gsr_forward_batch_channels_train again)");
+    if (r.kind != 1 || !r.need_backward || r.xstate == nullptr)
+        return fail(GSR_ERR_INVALID, "[gsr] backward_channels: the forward on this arena saved no extra channels (it needs "
+                    "gsr_forward_batch_channels_train with need_backward = 1)");
+    if (r.nx != x->X.nx || r.layout != x->layout)
+        return fail(GSR_ERR_INVALID, "[gsr] backward_channels: nx = %d, extra_per_view = %d, but the forward had nx = %d, extra_per_view = %d",
+                    x->X.nx, x->layout, r.nx, r.layout);
+    if (!same) return fail(GSR_ERR_INVALID, "[gsr] backward_channels: views / sizes differ from the forward's");
+    if (r.xstate != x->state || x->state_bytes < r.xstate_bytes)
+        return fail(GSR_ERR_INVALID, "[gsr] backward_channels: extra_state is not the block the forward saved into");
     return GSR_OK;
 }
 
@@ -706,10 +739,10 @@ static int backward_impl(const gsr_params* p, int V, const int* radii, const voi
         // (deterministic: the ordered reduction writes the rows of the Gaussians it reaches with plain stores; the others stay zero,
         // in the caller's per-view rows and in the staging of the shared ones)
         const size_t n_out = !x ? 0 : (size_t)p->P * (x->layout == 0 ? x->X.nx : x->layout == 1 ? V * x->X.nx : (1 + V) * 4);
-        if (x && hipMemsetAsync(x->XG.grad, 0, n_out * sizeof(float), L.stream) != hipSuccess)
-            return fail(GSR_ERR_HIP, "[gsr] memset failed: %s", hipGetErrorString(hipGetLastError()));
-        if (S.stage && hipMemsetAsync(S.stage, 0, (size_t)V * S.n_stage * sizeof(float), L.stream) != hipSuccess)
-            return fail(GSR_ERR_HIP, "[gsr] memset failed: %s", hipGetErrorString(hipGetLastError()));
+        if (x)
+            if (int e = zero_async(L.stream, x->XG.grad, n_out * sizeof(float))) return e;
+        if (S.stage)
+            if (int e = zero_async(L.stream, S.stage, (size_t)V * S.n_stage * sizeof(float))) return e;
         if (int e = launch_bwd_items(L, B, T, p->P)) return e;
     }
     int dres = 0;
@@ -750,14 +783,8 @@ static int backward_impl(const gsr_params* p, int V, const int* radii, const voi
                                                G.dL_dsh, G.dL_dscale, G.dL_drot))
             return e;
     }
-    {
-        // the records now hold this backward's per-view sums: gsr_backward_cameras may follow
-        FrameRecord r;
-        if (find_frame(geom, r)) {
-            r.bwd_done = 1;
-            note_frame(geom, r);
-        }
-    }
+    // the records now hold this backward's per-view sums: gsr_backward_cameras may follow
+    update_frame(geom, [](FrameRecord& r) { r.bwd_done = 1; });
     return GSR_OK;
 }
 
@@ -847,18 +874,7 @@ int gsr_backward_cameras(const gsr_params* p, int V, const int* radii, const voi
     if (scratch_bytes < gsr_camera_grad_bytes(V, p->P))
         return fail(GSR_ERR_CAPACITY, "[gsr] backward_cameras: scratch block too small (%zu < %zu = gsr_camera_grad_bytes(%d, %d))",
                     scratch_bytes, gsr_camera_grad_bytes(V, p->P), V, p->P);
-    FrameRecord r;
-    if (find_frame(geom, r)) {   // (no record: the call goes ahead, like a colour backward)
-        if (!r.need_backward)
-            return fail(GSR_ERR_INVALID, "[gsr] backward_cameras: the last %s on this geometry arena had need_backward = 0: there are "
-                        "no gradient records", r.kind == 2 ? "gsr_forward_recolor" : "forward");
-        if (!r.bwd_done)
-            return fail(GSR_ERR_INVALID, "[gsr] backward_cameras: no backward has run since the last forward or recolor on this geometry "
-                        "arena (the gradient records are empty; run one of the gsr_backward entries first)");
-        if (r.V != V || r.P != p->P || r.W != p->W || r.H != p->H)
-            return fail(GSR_ERR_INVALID, "[gsr] backward_cameras: V = %d, P = %d, %d x %d, but the last forward or recolor on this "
-                        "geometry arena had V = %d, P = %d, %d x %d", V, p->P, p->W, p->H, r.V, r.P, r.W, r.H);
-    }
+    if (int e = frame_gate("backward_cameras", geom, p, V, GATE_SAVES | GATE_RECORDS, ": there are no gradient records")) return e;
     Batch B;
     if (int e = make_geom_batch(p, V, const_cast<void*>(geom), geom_bytes, true, B)) return e;
     const Launch L{(hipStream_t)stream, p->debug};
@@ -886,18 +902,7 @@ int gsr_backward_view_stats(const gsr_params* p, int V, const int* radii, const 
         return fail(GSR_ERR_INVALID, "[gsr] backward_view_stats: all six outputs are NULL: nothing to write");
     if (((uintptr_t)dL_dmean2D_views & 7u) != 0)
         return fail(GSR_ERR_INVALID, "[gsr] backward_view_stats: dL_dmean2D_views is not 8-byte aligned (its rows leave as 8-B stores)");
-    FrameRecord r;
-    if (find_frame(geom, r)) {   // (no record: the call goes ahead, like gsr_backward_cameras)
-        if (!r.need_backward)
-            return fail(GSR_ERR_INVALID, "[gsr] backward_view_stats: the last %s on this geometry arena had need_backward = 0: there are "
-                        "no gradient records", r.kind == 2 ? "gsr_forward_recolor" : "forward");
-        if (!r.bwd_done)
-            return fail(GSR_ERR_INVALID, "[gsr] backward_view_stats: no backward has run since the last forward or recolor on this "
-                        "geometry arena (the gradient records are empty; run one of the gsr_backward entries first)");
-        if (r.V != V || r.P != p->P || r.W != p->W || r.H != p->H)
-            return fail(GSR_ERR_INVALID, "[gsr] backward_view_stats: V = %d, P = %d, %d x %d, but the last forward or recolor on this "
-                        "geometry arena had V = %d, P = %d, %d x %d", V, p->P, p->W, p->H, r.V, r.P, r.W, r.H);
-    }
+    if (int e = frame_gate("backward_view_stats", geom, p, V, GATE_SAVES | GATE_RECORDS, ": there are no gradient records")) return e;
     Batch B;
     if (int e = make_geom_batch(p, V, const_cast<void*>(geom), geom_bytes, true, B)) return e;
     const Launch L{(hipStream_t)stream, p->debug};
@@ -917,12 +922,7 @@ int gsr_contrib_stats(const gsr_params* p, int V, const int* radii, const void* 
     if (!geom || !binning || !image) return fail(GSR_ERR_INVALID, "[gsr] contrib_stats: a required pointer is NULL");
     if (!weight_sum && !weight_max && !pixel_count && !dominant_count)
         return fail(GSR_ERR_INVALID, "[gsr] contrib_stats: all four outputs are NULL: nothing to write");
-    FrameRecord r;
-    if (find_frame(geom, r)) {   // (no record: the call goes ahead; the record is only read)
-        if (r.V != V || r.P != p->P || r.W != p->W || r.H != p->H)
-            return fail(GSR_ERR_INVALID, "[gsr] contrib_stats: V = %d, P = %d, %d x %d, but the last forward or recolor on this "
-                        "geometry arena had V = %d, P = %d, %d x %d", V, p->P, p->W, p->H, r.V, r.P, r.W, r.H);
-    }
+    if (int e = frame_gate("contrib_stats", geom, p, V, 0, "")) return e;   // (sizes only: the walk reads what every forward leaves)
     Batch B;
     if (int e = make_batch(p, V, const_cast<void*>(geom), geom_bytes, const_cast<void*>(image), image_bytes,
                            const_cast<void*>(binning), binning_bytes, false, B))
@@ -932,8 +932,8 @@ int gsr_contrib_stats(const gsr_params* p, int V, const int* radii, const void* 
     if (!accumulate) {
         void* const outs[4] = {weight_sum, weight_max, pixel_count, dominant_count};
         for (void* o : outs)
-            if (o && hipMemsetAsync(o, 0, (size_t)p->P * 4, L.stream) != hipSuccess)
-                return fail(GSR_ERR_HIP, "[gsr] memset failed: %s", hipGetErrorString(hipGetLastError()));
+            if (o)
+                if (int e = zero_async(L.stream, o, (size_t)p->P * 4)) return e;
     }
     return launch_contrib_stats(L, *p, B, B.b.val[sorted_buffer(tile_count(p))], pixel_weights, weight_sum, weight_max, pixel_count,
                                 dominant_count);

@@ -294,17 +294,35 @@ def _stack_views(settings_list, device):
     return hit[0], hit[1], hit[2]
 
 
-class _RasterizeGaussiansViews(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings_list):
-        rs = settings_list[0]
-        view, proj, cam = _stack_views(settings_list, means3D.device)
-        need_backward = any(ctx.needs_input_grad)
-        counts, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians_batch(
-            rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj,
+def _forward_args(settings_list, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, view, proj, cam):
+    """the 19 positional arguments of _native.rasterize_gaussians_batch for the views of settings_list"""
+    rs = settings_list[0]
+    return (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj,
             rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree, cam, rs.prefiltered,
-            any(s.debug for s in settings_list), need_backward=need_backward)
-        ctx.raster_settings = rs
+            any(s.debug for s in settings_list))
+
+
+def _arena_args(rs, saved, *middle):
+    """The leading arguments of the native calls that run on the arenas of a view-batch forward, from the thirteen tensors every such
+    forward saves (the order of _RasterizeGaussiansViews.forward's save_for_backward): through geomBuffer, with `middle` where the
+    backwards take dL/d image and the followers (backward_cameras, backward_view_stats, contrib_stats) the image's height and width."""
+    colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, _binning, _img, view, proj, cam = saved[:13]
+    return (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj, rs.tanfovx,
+            rs.tanfovy) + middle + (sh, rs.sh_degree, cam, geomBuffer)
+
+
+class _RasterizeGaussiansViews(torch.autograd.Function):
+    """The view batch: forward and colour backward of every view-batch Function but the channels one, which saves more and calls
+    other entries.  cameras: (view, proj, cam) blocks that take the place of the settings' own matrix fields (not part of apply's
+    arguments: _RasterizeGaussiansViewsCameras hands them over)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings_list, cameras=None):
+        view, proj, cam = cameras if cameras is not None else _stack_views(settings_list, means3D.device)
+        counts, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians_batch(
+            *_forward_args(settings_list, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, view, proj, cam),
+            need_backward=any(ctx.needs_input_grad))
+        ctx.raster_settings = settings_list[0]
         ctx.num_rendered = counts
         ctx.opacity_shape = tuple(opacities.shape)
         ctx.det_pairs = _C.last_list_pairs(len(counts)) if means3D.shape[0] != 0 and _C.deterministic_active() else None
@@ -315,13 +333,10 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out_color, _):
-        rs = ctx.raster_settings
-        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer, view, proj,
-         cam) = ctx.saved_tensors
-        grads = _C.rasterize_gaussians_backward_batch(
-            rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj, rs.tanfovx,
-            rs.tanfovy, grad_out_color, sh, rs.sh_degree, cam, geomBuffer, binningBuffer, imgBuffer, rs.debug,
-            deterministic=_C.deterministic_active(), pairs=ctx.det_pairs)
+        rs, saved = ctx.raster_settings, ctx.saved_tensors
+        colors_precomp, _m, scales, rotations, cov3Ds_precomp, _r, sh, _g, binningBuffer, imgBuffer = saved[:10]
+        grads = _C.rasterize_gaussians_backward_batch(*_arena_args(rs, saved, grad_out_color), binningBuffer, imgBuffer, rs.debug,
+                                                      deterministic=_C.deterministic_active(), pairs=ctx.det_pairs)
         return _input_grads(grads, ctx, sh, colors_precomp, scales, rotations, cov3Ds_precomp, None)
 
 
@@ -379,12 +394,10 @@ class _RasterizeGaussiansViewsStats(torch.autograd.Function):
     def backward(ctx, grad_out_color, _):
         grads = _RasterizeGaussiansViews.backward(ctx, grad_out_color, _)
         rs, st = ctx.raster_settings, ctx.stats
-        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, _b, _i, view, proj, cam) = ctx.saved_tensors
         # the gradient records of the backward above are still in the arenas: one pass over them per Gaussian
-        g = _C.backward_view_stats(rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view,
-                                   proj, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree, cam, geomBuffer,
-                                   rs.debug, accumulate=True, grad_norm_sum=st.grad_norm_sum, visible_views=st.visible_views,
-                                   max_radius=st.max_radius, view_grads=st.keep_view_grads)
+        g = _C.backward_view_stats(*_arena_args(rs, ctx.saved_tensors, rs.image_height, rs.image_width), rs.debug, accumulate=True,
+                                   grad_norm_sum=st.grad_norm_sum, visible_views=st.visible_views, max_radius=st.max_radius,
+                                   view_grads=st.keep_view_grads)
         if st.keep_view_grads:
             st.view_grads = dict(mean2D=g[0], color=g[1], opacity=g[2])
         return grads + (None,)
@@ -464,15 +477,13 @@ def rasterize_views_contrib(means3D, means2D, opacities, settings_list, stats, p
     shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales, rotations, cov3D_precomp)
     with torch.no_grad():
         view, proj, cam = _stack_views(settings_list, means3D.device)
-        debug = any(s.debug for s in settings_list)
-        _counts, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians_batch(
-            rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3D_precomp, view, proj,
-            rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, shs, rs.sh_degree, cam, rs.prefiltered, debug,
-            need_backward=False)
-        _C.contrib_stats(rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3D_precomp, view, proj,
-                         rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, shs, rs.sh_degree, cam, geomBuffer, binningBuffer,
-                         imgBuffer, debug, accumulate=True, pixel_weights=pixel_weights, weight_sum=stats.weight_sum,
-                         weight_max=stats.weight_max, pixel_count=stats.pixel_count, dominant_count=stats.dominant_count)
+        fwd = _forward_args(settings_list, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, view, proj, cam)
+        _counts, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians_batch(*fwd, need_backward=False)
+        # (what a Function would have saved, in its order)
+        saved = (colors_precomp, means3D, scales, rotations, cov3D_precomp, radii, shs, geomBuffer, binningBuffer, imgBuffer, view, proj, cam)
+        _C.contrib_stats(*_arena_args(rs, saved, rs.image_height, rs.image_width), binningBuffer, imgBuffer, debug=fwd[-1],
+                         accumulate=True, pixel_weights=pixel_weights, weight_sum=stats.weight_sum, weight_max=stats.weight_max,
+                         pixel_count=stats.pixel_count, dominant_count=stats.dominant_count)
         stats.pixels_seen += V * int(rs.image_height) * int(rs.image_width)
     return color, radii
 
@@ -485,44 +496,25 @@ class _RasterizeGaussiansViewsCameras(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, view, proj, cam,
                 settings_list):
-        rs = settings_list[0]
         _check_views_agree(settings_list)
         device = means3D.device
         _C._require_hip(device)
         ctx.cam_shapes = (tuple(view.shape), tuple(proj.shape), tuple(cam.shape))
-        view, proj, cam = (_C._f32c(view, device, "viewmatrices"), _C._f32c(proj, device, "projmatrices"),
-                           _C._f32c(cam, device, "campos"))
-        need_backward = any(ctx.needs_input_grad)
-        counts, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians_batch(
-            rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj,
-            rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree, cam, rs.prefiltered,
-            any(s.debug for s in settings_list), need_backward=need_backward)
-        ctx.raster_settings = rs
-        ctx.opacity_shape = tuple(opacities.shape)
-        ctx.det_pairs = _C.last_list_pairs(len(counts)) if means3D.shape[0] != 0 and _C.deterministic_active() else None
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
-                              imgBuffer, view, proj, cam)
-        ctx.mark_non_differentiable(radii)
-        return color, radii
+        cameras = (_C._f32c(view, device, "viewmatrices"), _C._f32c(proj, device, "projmatrices"), _C._f32c(cam, device, "campos"))
+        return _RasterizeGaussiansViews.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                                cov3Ds_precomp, settings_list, cameras)
 
     @staticmethod
     def backward(ctx, grad_out_color, _):
-        rs = ctx.raster_settings
-        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer, view, proj,
-         cam) = ctx.saved_tensors
-        grads = _C.rasterize_gaussians_backward_batch(
-            rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj, rs.tanfovx,
-            rs.tanfovy, grad_out_color, sh, rs.sh_degree, cam, geomBuffer, binningBuffer, imgBuffer, rs.debug,
-            deterministic=_C.deterministic_active(), pairs=ctx.det_pairs)
+        grads = _RasterizeGaussiansViews.backward(ctx, grad_out_color, _)
         g_cam = (None, None, None)
         if any(ctx.needs_input_grad[8:11]):
+            rs = ctx.raster_settings
             # the gradient records of the backward above are still in the arenas: one reduction over them per view
-            g = _C.backward_cameras(rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view,
-                                    proj, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree, cam, geomBuffer,
-                                    rs.debug)
+            g = _C.backward_cameras(*_arena_args(rs, ctx.saved_tensors, rs.image_height, rs.image_width), rs.debug)
             g_cam = tuple(t.reshape(shape) if need else None
                           for t, shape, need in zip(g, ctx.cam_shapes, ctx.needs_input_grad[8:11]))
-        return _input_grads(grads, ctx, sh, colors_precomp, scales, rotations, cov3Ds_precomp, *g_cam, None)
+        return grads[:-1] + g_cam + (None,)   # (the cameras' gradients go between the cloud's and the settings' None)
 
 
 def rasterize_views_cameras(means3D, means2D, opacities, settings_list, viewmatrices, projmatrices, campos, shs=None,
@@ -555,9 +547,8 @@ class _RasterizeGaussiansViewsChannels(torch.autograd.Function):
         values = (extra, extra_hi) if extra_hi.numel() != 0 else extra
         xs = None if extra_view_scale.numel() == 0 else extra_view_scale
         counts, color, radii, geomBuffer, binningBuffer, imgBuffer, out_extra = _C.rasterize_gaussians_batch(
-            rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj,
-            rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree, cam, rs.prefiltered,
-            any(s.debug for s in settings_list), need_backward=need_backward, extra=(values, xs, bg_extra))
+            *_forward_args(settings_list, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, view, proj, cam),
+            need_backward=need_backward, extra=(values, xs, bg_extra))
         ctx.raster_settings = rs
         ctx.opacity_shape = tuple(opacities.shape)
         ctx.nx_user = nx_user
@@ -572,9 +563,9 @@ class _RasterizeGaussiansViewsChannels(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out_color, _, grad_out_extra):
-        rs = ctx.raster_settings
-        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer, view, proj,
-         cam, extra, extra_hi, bg_extra, extra_view_scale) = ctx.saved_tensors
+        rs, saved = ctx.raster_settings, ctx.saved_tensors
+        colors_precomp, _m, scales, rotations, cov3Ds_precomp, _r, sh, _g, binningBuffer, imgBuffer = saved[:10]
+        extra, extra_hi, bg_extra, extra_view_scale = saved[13:]
         split = extra_hi.numel() != 0
         nx = 8 if split else extra.shape[-1]
         V = grad_out_color.shape[0]
@@ -584,9 +575,8 @@ class _RasterizeGaussiansViewsChannels(torch.autograd.Function):
         values = (extra, extra_hi) if split else extra
         xs = None if extra_view_scale.numel() == 0 else extra_view_scale
         g = _C.rasterize_gaussians_backward_channels_batch(
-            rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj, rs.tanfovx,
-            rs.tanfovy, grad_out_color, sh, rs.sh_degree, cam, geomBuffer, binningBuffer, imgBuffer, rs.debug,
-            (values, xs, bg_extra), grad_out_extra, state=ctx.xstate, deterministic=ctx.det_channels, pairs=ctx.det_pairs)
+            *_arena_args(rs, saved, grad_out_color), binningBuffer, imgBuffer, rs.debug, (values, xs, bg_extra), grad_out_extra,
+            state=ctx.xstate, deterministic=ctx.det_channels, pairs=ctx.det_pairs)
         g_lo, g_hi = g[8] if split else (g[8], None)
         return _input_grads(g[:8], ctx, sh, colors_precomp, scales, rotations, cov3Ds_precomp, g_lo, g_hi, None, None, None, None)
 

@@ -117,6 +117,9 @@ def _check(rc):
         raise RuntimeError(lib.gsr_last_error().decode("utf-8", "replace"))
 
 
+_F32 = torch.float32
+
+
 def _f32c(t, device, name):
     if t.numel() == 0:
         return t
@@ -169,20 +172,63 @@ def _require_hip(device):
             "There is no CPU path." % device)
 
 
+# the tensors behind GsrParams' eleven pointer fields, in the fields' order, as error messages name them
+_POINTER_FIELDS = ("bg", "means3D", "sh", "colors_precomp", "opacities", "scales", "rotations", "cov3D_precomp", "viewmatrix",
+                   "projmatrix", "campos")
+
+
 def _params(bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
             tan_fovx, tan_fovy, H, W, sh, degree, campos, prefiltered, debug, need_backward):
+    """The only place where the eleven input tensors become a GsrParams (p.M: the SH coefficients per Gaussian, rasterize_points.cu:
+    83-87).  The tensors are taken as they come: only one that is not float32, on the device and contiguous is converted, and those
+    are returned beside the params so that they outlive the enqueued kernels' use of their pointers.  Absent optionals (empty
+    tensors) give NULL, as the reference's do (rasterize_points.cu:94-111 -> rasterizer_impl.cu:321,389,411).  The per-view short
+    path comes through here while the GPU idles: in the usual case no tensor costs a function call of this module."""
     device = means3D.device
-    # (the converted tensors are returned so that they outlive the enqueued kernels' use of their pointers)
-    keep = (_f32c(bg, device, "bg"), _f32c(means3D, device, "means3D"), _f32c(sh, device, "sh"),
-            _f32c(colors, device, "colors_precomp"), _f32c(opacity, device, "opacities"), _f32c(scales, device, "scales"),
-            _f32c(rotations, device, "rotations"), _f32c(cov3D_precomp, device, "cov3D_precomp"),
-            _f32c(viewmatrix, device, "viewmatrix"), _f32c(projmatrix, device, "projmatrix"), _f32c(campos, device, "campos"))
-    M = int(sh.shape[1]) if sh.numel() != 0 and sh.shape[0] != 0 else 0  # rasterize_points.cu:83-87
+    keep, ptrs = [], []
+    for t in (bg, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos):
+        if t.numel() == 0:
+            ptrs.append(None)
+            continue
+        if t.dtype is not _F32 or t.device != device or not t.is_contiguous():
+            t = _f32c(t, device, _POINTER_FIELDS[len(ptrs)])
+            keep.append(t)
+        ptrs.append(t.data_ptr())
     # field order of GsrParams / gsr_params (include/gsr.h)
-    p = GsrParams(means3D.shape[0], int(degree), M, int(W), int(H), float(tan_fovx), float(tan_fovy), float(scale_modifier),
-                  int(bool(prefiltered)), int(bool(debug)), int(bool(need_backward)), int(reference_lists()),
-                  *[_ptr(t) for t in keep])
+    p = GsrParams(means3D.shape[0], int(degree), int(sh.shape[1]) if ptrs[2] is not None else 0, int(W), int(H), float(tan_fovx),
+                  float(tan_fovy), float(scale_modifier), int(bool(prefiltered)), int(bool(debug)), int(bool(need_backward)),
+                  int(reference_lists()), *ptrs)
     return p, keep
+
+
+def _follower_params(background, means3D, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices,
+                     tan_fovx, tan_fovy, H, W, sh, degree, camposs, debug, need_backward=True):
+    """_params of a call that follows a forward on its arenas (the backwards, the readers of the gradient records, the contribution
+    statistics): opacity lives in the geometry arena and the pointer only has to be non-NULL, so means3D stands in; prefiltered
+    plays no part after the forward."""
+    return _params(background, means3D, colors, means3D, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
+                   projmatrices, tan_fovx, tan_fovy, H, W, sh, degree, camposs, False, debug, need_backward)
+
+
+def _size_fault(P, V, bg, sh, colors, opacity, scales, rotations, cov3D_precomp, viewmatrices, projmatrices, camposs):
+    """"<name> must have ..." for the first input of a forward whose size does not fit P Gaussians and V views, else None.  The C ABI
+    sees raw pointers, so this is the one place where a tensor with the wrong number of rows can be caught before a kernel reads
+    past its end.  Shapes only: no device work, no host copy.  Absent optionals (empty tensors) fit."""
+    for name, t, per in (("opacities", opacity, 1), ("scales", scales, 3), ("rotations", rotations, 4),
+                         ("cov3D_precomp", cov3D_precomp, 6), ("colors_precomp", colors, 3)):
+        n = t.numel()
+        if n != per * P and n != 0:
+            return "%s must have %d x num_points = %d elements (got %d)" % (name, per, per * P, n)
+    if sh.numel() != 0:
+        shape = sh.shape
+        if len(shape) != 3 or shape[0] != P or shape[2] != 3:
+            return "sh must have shape (num_points = %d, coefficients, 3) (got %s)" % (P, tuple(shape))
+    if 0 < bg.numel() < 3:   # (the kernels read three values; none at all: the library's NULL check)
+        return "bg must have at least 3 elements (got %d)" % bg.numel()
+    for name, t, per in (("viewmatrices", viewmatrices, 16), ("projmatrices", projmatrices, 16), ("camposs", camposs, 3)):
+        if V < 1 or t.numel() != per * V:
+            return "%s must have %d x num_views = %d elements for num_views >= 1 (got %d)" % (name, per, per * V, t.numel())
+    return None
 
 
 # ---- footprint clipping (include/gsr.h, gsr_params.reference_lists) ---------------------------------------------------
@@ -267,10 +313,6 @@ def det_scratch(V, P, W, H, pairs, binning_bytes, device, nx=0, extra_per_view=0
     n = (lib.gsr_backward_det_channels_bytes(V, P, W, H, int(pairs), nx, extra_per_view) if nx
          else lib.gsr_backward_det_bytes(V, P, W, H, int(pairs)))
     return torch.empty((int(n),), dtype=torch.uint8, device=device)
-
-
-def det_channels_scratch(V, P, W, H, pairs, binning_bytes, nx, extra_per_view, device):
-    return det_scratch(V, P, W, H, pairs, binning_bytes, device, nx, extra_per_view)
 
 
 # ---- binning-arena capacity -----------------------------------------------------------------------------------------
@@ -507,10 +549,9 @@ def _arena_args(geom, binning, image):
 def _bwd_inputs(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices,
                 tan_fovx, tan_fovy, dL_dout_color, sh, degree, camposs, debug):
     """(params, tensors to keep, radii, dL_dout_color) of a general-path backward, converted"""
-    H, W = int(dL_dout_color.shape[2]), int(dL_dout_color.shape[3])
-    # (opacity lives in the geom arena; the pointer only has to be non-NULL: means3D stands in)
-    p, keep = _params(background, means3D, colors, means3D, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
-                      projmatrices, tan_fovx, tan_fovy, H, W, sh, degree, camposs, False, debug, True)
+    p, keep = _follower_params(background, means3D, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
+                               projmatrices, tan_fovx, tan_fovy, int(dL_dout_color.shape[2]), int(dL_dout_color.shape[3]), sh, degree,
+                               camposs, debug)
     return p, keep, radii.contiguous(), _f32c(dL_dout_color, means3D.device, "dL_dout_color")
 
 
@@ -549,12 +590,13 @@ def rasterize_gaussians_batch(background, means3D, colors, opacity, scales, rota
     (gsr_forward_batch_channels_train): a caller-owned extra-state block, kept with the geometry arena (extra_state(geomBuffer))."""
     if means3D.dim() != 2 or means3D.shape[1] != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    P, V = means3D.shape[0], viewmatrices.numel() // 16
+    fault = _size_fault(P, V, background, sh, colors, opacity, scales, rotations, cov3D_precomp, viewmatrices, projmatrices, camposs)
+    if fault is not None:
+        raise RuntimeError(fault)
     device = means3D.device
     _require_hip(device)
-    V = viewmatrices.numel() // 16
-    if viewmatrices.numel() != 16 * V or projmatrices.numel() != 16 * V or camposs.numel() != 3 * V or V < 1:
-        raise RuntimeError("viewmatrices, projmatrices and camposs must describe the same number of views (>= 1)")
-    P, H, W = means3D.shape[0], int(image_height), int(image_width)
+    H, W = int(image_height), int(image_width)
     byte = dict(dtype=torch.uint8, device=device)
     nx, x_per_view, xv, xs, xb = (0, 0, None, None, None) if extra is None else _extra_layout(extra, P, V, device)
     if P == 0:  # rasterize_points.cu:81: the zero image (not the background) is returned
@@ -643,7 +685,6 @@ def rasterize_gaussians_batch(background, means3D, colors, opacity, scales, rota
 # before the launch: inline argument checks, the three scratch arenas as ONE allocation (they live and die together: saved for
 # the backward as one tensor), outputs in their final shape (no views), sizes from dictionaries.  Anything unusual -- first frame
 # of a configuration, debug, P == 0, the overlap mode -- returns None and the caller takes the general path.
-_F32 = torch.float32
 _BIN_BYTES = {}
 _CAP_QUANTUM = 1 << 16
 _TLS_FAST = threading.local()
@@ -660,27 +701,6 @@ def _slab_layout(P, W, H, need_backward, capacity):
     return g, i, b
 
 
-def _view_params(rs, tensors, W, H, prefiltered, need_backward):
-    """GsrParams of one view from the eleven input tensors in the order of its pointer fields (bg ... campos), as they come: only
-    a tensor that is not float32, on the device and contiguous is converted.  Returns (params, M, the converted tensors -- to be kept
-    until the call has been enqueued)."""
-    device = tensors[1].device
-    keep = []
-    ptrs = []
-    for t in tensors:
-        if t.numel() == 0:
-            ptrs.append(None)
-            continue
-        if t.dtype is not _F32 or t.device != device or not t.is_contiguous():
-            t = _f32c(t, device, "an input")
-            keep.append(t)
-        ptrs.append(t.data_ptr())
-    M = int(tensors[2].shape[1]) if ptrs[2] is not None else 0
-    p = GsrParams(tensors[1].shape[0], int(rs.sh_degree), M, W, H, float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier),
-                  prefiltered, 0, need_backward, int(reference_lists()), *ptrs)
-    return p, M, keep
-
-
 def forward_view(rs, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, need_backward):
     """One view through gsr_forward_batch.  Returns (num_rendered, color [3,H,W], radii [P], arenas, layout) -- arenas: ONE uint8
     tensor holding the geometry, image and binning arenas at the byte offsets 0, layout[0], layout[0] + layout[1] -- or None when
@@ -693,8 +713,10 @@ def forward_view(rs, means3D, sh, colors, opacity, scales, rotations, cov3D_prec
     hint = _CAP_HINT.get((device.index, P, W, H))
     if hint is None or device.index is None or device.index != torch.cuda.current_device():
         return None
-    p, _, keep = _view_params(rs, (rs.bg, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, rs.viewmatrix, rs.projmatrix,
-                                   rs.campos), W, H, int(bool(rs.prefiltered)), int(need_backward))
+    if _size_fault(P, 1, rs.bg, sh, colors, opacity, scales, rotations, cov3D_precomp, rs.viewmatrix, rs.projmatrix, rs.campos):
+        return None     # (the general path raises, naming the tensor)
+    p, keep = _params(rs.bg, means3D, colors, opacity, scales, rotations, rs.scale_modifier, cov3D_precomp, rs.viewmatrix,
+                      rs.projmatrix, rs.tanfovx, rs.tanfovy, H, W, sh, rs.sh_degree, rs.campos, rs.prefiltered, False, need_backward)
     capacity = (int(hint * CAP_SLACK) + 4096 + _CAP_QUANTUM - 1) // _CAP_QUANTUM * _CAP_QUANTUM
     g, i, b = _slab_layout(P, W, H, need_backward, capacity)
     arenas = torch.empty((g + i + b,), dtype=torch.uint8, device=device)
@@ -729,12 +751,11 @@ def backward_view(rs, means3D, radii, colors, scales, rotations, cov3D_precomp, 
     scratch block for lists of `pairs` pairs (None: bounded from the binning arena's size)."""
     device = means3D.device
     H, W = int(grad_color.shape[-2]), int(grad_color.shape[-1])
-    # (opacity lives in the geometry arena; the pointer only has to be non-NULL: means3D stands in)
-    p, M, keep = _view_params(rs, (rs.bg, means3D, sh, colors, means3D, scales, rotations, cov3D_precomp, rs.viewmatrix, rs.projmatrix,
-                                   rs.campos), W, H, 0, 1)
+    p, keep = _follower_params(rs.bg, means3D, colors, scales, rotations, rs.scale_modifier, cov3D_precomp, rs.viewmatrix,
+                               rs.projmatrix, rs.tanfovx, rs.tanfovy, H, W, sh, rs.sh_degree, rs.campos, False)
     if grad_color.dtype is not _F32 or grad_color.device != device or not grad_color.is_contiguous():
         grad_color = _f32c(grad_color, device, "dL_dout_color")
-    grads = _grad_tensors(means3D.shape[0], M, device, scales.numel() != 0)
+    grads = _grad_tensors(p.P, p.M, device, scales.numel() != 0)
     g, i, b = layout
     base = arenas.data_ptr()
     with _on_device(device):
@@ -848,7 +869,7 @@ def rasterize_gaussians_backward_channels_batch(background, means3D, radii, colo
                 nx, x_per_view, xv.data_ptr(), _ptr(xs), xb.data_ptr(), st[0].data_ptr(), st[0].numel(), dx.data_ptr(), gx.data_ptr())
             if deterministic:
                 CALLS["backward_channels_det"] += 1
-                scratch = det_channels_scratch(V, P, W, H, pairs, arenas[3], nx, x_per_view, device)
+                scratch = det_scratch(V, P, W, H, pairs, arenas[3], device, nx, x_per_view)
                 _check(lib.gsr_backward_batch_channels_det(*args, scratch.data_ptr(), scratch.numel(), _stream_handle(device)))
             else:
                 _check(lib.gsr_backward_batch_channels(*args, _stream_handle(device)))
@@ -880,10 +901,8 @@ def backward_cameras(background, means3D, radii, colors, scales, rotations, scal
     if P != 0:
         CALLS["backward_cameras"] += 1
         with _on_device(device):
-            # (opacity lives in the geom arena; the pointer only has to be non-NULL: means3D stands in)
-            p, keep = _params(background, means3D, colors, means3D, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
-                              projmatrices, tan_fovx, tan_fovy, int(image_height), int(image_width), sh, degree, camposs, False, debug,
-                              True)
+            p, keep = _follower_params(background, means3D, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
+                                       projmatrices, tan_fovx, tan_fovy, image_height, image_width, sh, degree, camposs, debug)
             scratch = _scratch if _scratch is not None else camera_scratch(V, P, device)
             radii_c = radii.contiguous()
             _check(lib.gsr_backward_cameras(C.byref(p), V, radii_c.data_ptr(), geomBuffer.data_ptr(), geomBuffer.numel(),
@@ -893,13 +912,13 @@ def backward_cameras(background, means3D, radii, colors, scales, rotations, scal
     return out
 
 
-def _stats_out(t, shape, dtype, device, name):
-    """an output of backward_view_stats handed over by the caller: the library writes into it in place"""
+def _stats_out(who, t, shape, dtype, device, name):
+    """an output of backward_view_stats or contrib_stats (`who`) handed over by the caller: the library writes into it in place"""
     if t is None:
         return None
     if tuple(t.shape) != shape or t.dtype != dtype or t.device != device or not t.is_contiguous():
-        raise RuntimeError("backward_view_stats: %s must be a contiguous %s tensor of shape %s on %s (got %s %s on %s)"
-                           % (name, dtype, shape, device, t.dtype, tuple(t.shape), t.device))
+        raise RuntimeError("%s: %s must be a contiguous %s tensor of shape %s on %s (got %s %s on %s)"
+                           % (who, name, dtype, shape, device, t.dtype, tuple(t.shape), t.device))
     return t
 
 
@@ -914,13 +933,13 @@ def backward_view_stats(background, means3D, radii, colors, scales, rotations, s
     device = means3D.device
     _require_hip(device)
     P, V = means3D.shape[0], viewmatrices.numel() // 16
-    i32 = torch.int32
-    stats = (_stats_out(grad_norm_sum, (P,), _F32, device, "grad_norm_sum"), _stats_out(visible_views, (P,), i32, device, "visible_views"),
-             _stats_out(max_radius, (P,), i32, device, "max_radius"))
+    who, i32 = "backward_view_stats", torch.int32
+    stats = (_stats_out(who, grad_norm_sum, (P,), _F32, device, "grad_norm_sum"),
+             _stats_out(who, visible_views, (P,), i32, device, "visible_views"), _stats_out(who, max_radius, (P,), i32, device, "max_radius"))
     shapes = ((V, P, 2), (V, P, 3), (V, P))
     if _out is not None:
-        shares = tuple(_stats_out(t, s, _F32, device, n) for t, s, n in zip(_out, shapes, ("dL_dmean2D_views", "dL_dcolor_views",
-                                                                                           "dL_dopacity_views")))
+        shares = tuple(_stats_out(who, t, s, _F32, device, n)
+                       for t, s, n in zip(_out, shapes, ("dL_dmean2D_views", "dL_dcolor_views", "dL_dopacity_views")))
     elif view_grads:
         new = torch.empty if P != 0 else torch.zeros
         shares = tuple(new(s, dtype=_F32, device=device) for s in shapes)
@@ -929,26 +948,14 @@ def backward_view_stats(background, means3D, radii, colors, scales, rotations, s
     if P != 0:
         CALLS["backward_view_stats"] += 1
         with _on_device(device):
-            # (opacity lives in the geom arena; the pointer only has to be non-NULL: means3D stands in)
-            p, keep = _params(background, means3D, colors, means3D, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
-                              projmatrices, tan_fovx, tan_fovy, int(image_height), int(image_width), sh, degree, camposs, False, debug,
-                              True)
+            p, keep = _follower_params(background, means3D, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
+                                       projmatrices, tan_fovx, tan_fovy, image_height, image_width, sh, degree, camposs, debug)
             radii_c = radii.contiguous()
             _check(lib.gsr_backward_view_stats(C.byref(p), V, radii_c.data_ptr(), geomBuffer.data_ptr(), geomBuffer.numel(),
                                                int(bool(accumulate)), *[None if t is None else t.data_ptr() for t in stats + shares],
                                                _stream_handle(device)))
             del keep
     return shares if (view_grads or _out is not None) else None
-
-
-def _contrib_out(t, dtype, P, device, name):
-    """an output of contrib_stats handed over by the caller: the library accumulates into it in place"""
-    if t is None:
-        return None
-    if tuple(t.shape) != (P,) or t.dtype != dtype or t.device != device or not t.is_contiguous():
-        raise RuntimeError("contrib_stats: %s must be a contiguous %s tensor of shape %s on %s (got %s %s on %s)"
-                           % (name, dtype, (P,), device, t.dtype, tuple(t.shape), t.device))
-    return t
 
 
 def contrib_stats(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices,
@@ -963,9 +970,9 @@ def contrib_stats(background, means3D, radii, colors, scales, rotations, scale_m
     _require_hip(device)
     P, V = means3D.shape[0], viewmatrices.numel() // 16
     H, W = int(image_height), int(image_width)
-    i32 = torch.int32
-    outs = (_contrib_out(weight_sum, _F32, P, device, "weight_sum"), _contrib_out(weight_max, _F32, P, device, "weight_max"),
-            _contrib_out(pixel_count, i32, P, device, "pixel_count"), _contrib_out(dominant_count, i32, P, device, "dominant_count"))
+    outs = tuple(_stats_out("contrib_stats", t, (P,), dtype, device, name)
+                 for t, dtype, name in ((weight_sum, _F32, "weight_sum"), (weight_max, _F32, "weight_max"),
+                                        (pixel_count, torch.int32, "pixel_count"), (dominant_count, torch.int32, "dominant_count")))
     if pixel_weights is not None and (tuple(pixel_weights.shape) != (V, H, W) or pixel_weights.dtype != _F32
                                       or pixel_weights.device != device):
         raise RuntimeError("contrib_stats: pixel_weights must be a %s tensor of shape %s on %s (got %s %s on %s)"
@@ -973,9 +980,8 @@ def contrib_stats(background, means3D, radii, colors, scales, rotations, scale_m
     if P != 0:
         CALLS["contrib_stats"] += 1
         with _on_device(device):
-            # (opacity lives in the geom arena; the pointer only has to be non-NULL: means3D stands in)
-            p, keep = _params(background, means3D, colors, means3D, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
-                              projmatrices, tan_fovx, tan_fovy, H, W, sh, degree, camposs, False, debug, False)
+            p, keep = _follower_params(background, means3D, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
+                                       projmatrices, tan_fovx, tan_fovy, H, W, sh, degree, camposs, debug, need_backward=False)
             radii_c = None if radii is None else radii.contiguous()
             pw = None if pixel_weights is None else pixel_weights.contiguous()
             _check(lib.gsr_contrib_stats(C.byref(p), V, _ptr(radii_c), geomBuffer.data_ptr(), geomBuffer.numel(),

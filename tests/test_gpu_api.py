@@ -347,3 +347,31 @@ def test_short_host_path_refuses_a_means3D_that_is_not_P_by_3(gpu_device):
                               torch.Tensor([]), False) is None
         with pytest.raises(RuntimeError, match=r"means3D must have dimensions \(num_points, 3\)"):
             GaussianRasterizer(_settings(s, dev))(**L)
+
+
+@pytest.mark.parametrize("name,grow", [("opacities", lambda t, P: torch.cat([t, t], 1)),            # [P,2]
+                                       ("scales", lambda t, P: torch.cat([t, t[:, :1]], 1)),        # [P,4]
+                                       ("rotations", lambda t, P: torch.cat([t, t[:, :1]], 1)),     # [P,5]
+                                       ("shs", lambda t, P: torch.cat([t, t[:1]], 0))],             # [P+1,M,3]
+                         ids=["opacities", "scales", "rotations", "shs"])
+def test_short_host_path_refuses_an_input_whose_size_does_not_fit_P(gpu_device, name, grow):
+    """The same for the other per-Gaussian inputs: with a warm capacity hint, a tensor whose size does not fit num_points makes the
+    short path step aside and the general path raise the error that names it.  Every malformed tensor here is LARGER than the
+    well-formed one, so that no launch could read past its end whatever the checks do (too small: tests/test_cpu_input_sizes.py)."""
+    from diff_gaussian_rasterization import GaussianRasterizer, _native as N
+    dev = gpu_device
+    s = build_scene("capsule_circle")
+    L = dict(means3D=_leaf(s.means3D, dev), shs=_leaf(s.shs, dev), opacities=_leaf(s.opacities.reshape(-1, 1), dev),
+             scales=_leaf(s.scales, dev), rotations=_leaf(s.rotations, dev))
+    L["means2D"] = torch.zeros_like(L["means3D"])
+    N.reset_capacity_hints()
+    with torch.no_grad():
+        for _ in range(2):                     # (the first call sets the capacity hint, the second takes the short path)
+            GaussianRasterizer(_settings(s, dev))(**L)
+        assert N._CAP_HINT.get(N._cap_key(dev, s.P, s.W, s.H)) is not None
+        L[name] = grow(L[name].detach(), s.P).contiguous()
+        assert L[name].numel() > {"opacities": 1, "scales": 3, "rotations": 4, "shs": 3 * s.shs.shape[1]}[name] * s.P
+        assert N.forward_view(_settings(s, dev), L["means3D"], L["shs"], torch.Tensor([]), L["opacities"], L["scales"], L["rotations"],
+                              torch.Tensor([]), False) is None
+        with pytest.raises(RuntimeError, match=r"^%s must have " % {"shs": "sh"}.get(name, name)):
+            GaussianRasterizer(_settings(s, dev))(**L)

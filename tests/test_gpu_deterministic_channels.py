@@ -279,8 +279,8 @@ def test_contract_of_the_c_abi(gpu_device, monkeypatch):
     util.check_grads({k: b2[k].reshape(-1, 1) if k == EXTRA else b2[k] for k in both},
                      {k: atomic2[k].reshape(-1, 1) if k == EXTRA else atomic2[k] for k in both}, "second dL_dextra", names=both)
     # a block of exactly the stated size, sized by the lists' exact extent and full of NaN bytes: nothing of it reaches an output
-    real = N.det_channels_scratch
-    monkeypatch.setattr(N, "det_channels_scratch", lambda *a: torch.full((need,), 0xFF, dtype=torch.uint8, device=dev))
+    real = N.det_scratch
+    monkeypatch.setattr(N, "det_scratch", lambda *a: torch.full((need,), 0xFF, dtype=torch.uint8, device=dev))
     assert _same(a1, bw(dx))
     # one byte short: refused with the needed size in the message, outputs untouched
     made = []
@@ -288,7 +288,7 @@ def test_contract_of_the_c_abi(gpu_device, monkeypatch):
     def alloc(shape, dtype=None, device=None):
         made.append(torch.full(shape, -7.5, dtype=dtype, device=device))
         return made[-1]
-    monkeypatch.setattr(N, "det_channels_scratch", lambda *a: torch.empty((need - 1,), dtype=torch.uint8, device=dev))
+    monkeypatch.setattr(N, "det_scratch", lambda *a: torch.empty((need - 1,), dtype=torch.uint8, device=dev))
     with pytest.raises(RuntimeError, match=r"scratch block too small \(%d < %d = gsr_backward_det_channels_bytes\(2, %d, %d, %d, %d, 8, 2\)"
                        % (need - 1, need, P, W, H, pairs)):
         bw(dx, _alloc=alloc)
@@ -297,10 +297,10 @@ def test_contract_of_the_c_abi(gpu_device, monkeypatch):
     # a block sized for the colour entry only is too small as well
     small = int(N.lib.gsr_backward_det_bytes(V, P, W, H, pairs))
     assert small < need
-    monkeypatch.setattr(N, "det_channels_scratch", lambda *a: torch.empty((small,), dtype=torch.uint8, device=dev))
+    monkeypatch.setattr(N, "det_scratch", lambda *a: torch.empty((small,), dtype=torch.uint8, device=dev))
     with pytest.raises(RuntimeError, match=r"scratch block too small \(%d < %d" % (small, need)):
         bw(dx)
-    monkeypatch.setattr(N, "det_channels_scratch", real)
+    monkeypatch.setattr(N, "det_scratch", real)
     # and the arenas still serve a deterministic backward with the first one's bits
     assert _same(a1, bw(dx))
 
