@@ -15,7 +15,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "gaussian-
 import numpy as np  # noqa: E402
 
 import util  # noqa: E402
-import test_gpu_fuzz as F  # noqa: E402
+import sweep_support as F  # noqa: E402
 from oracle.oracle import Oracle, _f32, _fp  # noqa: E402
 
 
@@ -43,7 +43,7 @@ def main():
     err = {m: {n: [] for n in names} for m in (0, 1)}
     worst = {n: (0.0, None) for n in names}
     for c in cases:
-        s, _ = F._case(c)
+        s, _ = F.random_case(c)
         if s.P == 0:
             continue
         dL = util.seeded_dL(s, seed=77 + c)

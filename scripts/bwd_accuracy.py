@@ -11,7 +11,7 @@ import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "gaussian-pcloud-render_amd")]
 import numpy as np, torch
-import util, test_gpu_fuzz as F
+import util, sweep_support as F
 from oracle.oracle import Oracle, Reference
 from diff_gaussian_rasterization import _native as N
 
@@ -50,7 +50,7 @@ def main():
     names = ("mean2D", "conic", "colour", "opacity")
     stats = {n: [] for n in names}
     for c in cases:
-        s, mode = F._case(c)
+        s, mode = F.random_case(c)
         if s.P == 0:
             continue
         dL = util.seeded_dL(s, seed=77 + c)

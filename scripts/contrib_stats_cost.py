@@ -36,13 +36,13 @@ def main():
 
     import torch
     from diff_gaussian_rasterization import _native as N
-    import test_gpu_channels_backward as CB
+    import native_calls as NC
     if not torch.cuda.is_available():
         raise SystemExit("contrib_stats_cost.py measures on the GPU: no HIP device is visible")
     dev = torch.device("cuda:0")
     W, H, V, P = 1920, 1080, a.views, a.points
-    g, views, _, _ = CB._scene(V, P=P, W=W, H=H)
-    args = CB._args(g, views, W, H, dev, (1.0, 1.0, 1.0))
+    g, views, _, _ = NC.circle_scene(V, P=P, W=W, H=H)
+    args = NC.cloud_args(g, views, W, H, dev, (1.0, 1.0, 1.0))
     outs = dict(weight_sum=torch.zeros(P, device=dev), weight_max=torch.zeros(P, device=dev),
                 pixel_count=torch.zeros(P, dtype=torch.int32, device=dev), dominant_count=torch.zeros(P, dtype=torch.int32, device=dev))
     ones = torch.ones((V, H, W), device=dev)

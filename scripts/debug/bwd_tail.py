@@ -7,14 +7,14 @@ for p in (ROOT, os.path.join(ROOT, "gaussian-pcloud-render_amd"), os.path.join(R
 import numpy as np, torch
 from pcrender import camera, synth
 from diff_gaussian_rasterization import _native as N
-import test_gpu_batch as TB
+import native_calls as NC
 dev = torch.device("cuda:0")
 cloud = synth.make_cloud("synth-THuman-800K", seed=0)
 g = synth.make_gaussians(cloud, profile="training", seed=1)
 views = camera.circle_views(12, fov_deg=45.0, width_px=1920, height_px=1080)
 out = (C.c_ulonglong * 8)()
 for V in (1, 12):
-    args = TB._batch_args(g, views[:V], 1920, 1080, dev)
+    args = NC.batch_args(g, views[:V], 1920, 1080, dev)
     G = torch.rand((V, 3, 1080, 1920), device=dev)
     def once():
         r = N.rasterize_gaussians_batch(*args, need_backward=True)

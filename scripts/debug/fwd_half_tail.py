@@ -8,14 +8,14 @@ for p in (ROOT, os.path.join(ROOT, "gaussian-pcloud-render_amd"), os.path.join(R
 import numpy as np, torch
 from pcrender import camera, synth
 from diff_gaussian_rasterization import _native as N
-import test_gpu_batch as TB
+import native_calls as NC
 dev = torch.device("cuda:0")
 cloud = synth.make_cloud("synth-THuman-800K", seed=0)
 g = synth.make_gaussians(cloud, profile="training", seed=1)
 views = camera.circle_views(12, fov_deg=45.0, width_px=1920, height_px=1080)
 vi = int(sys.argv[1]) if len(sys.argv) > 1 else 0
 nv = int(sys.argv[2]) if len(sys.argv) > 2 else 1        # views in the submission (1: half-quadrant kernel; more: the 8 x 8 kernel, steps = pairs)
-args = TB._batch_args(g, (views + views)[vi:vi + nv], 1920, 1080, dev)
+args = NC.batch_args(g, (views + views)[vi:vi + nv], 1920, 1080, dev)
 for _ in range(2):
     N.rasterize_gaussians_batch(*args, need_backward=True)
 torch.cuda.synchronize()

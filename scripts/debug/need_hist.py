@@ -5,7 +5,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "gaussian-
 import numpy as np, torch
 from pcrender import camera, synth
 from diff_gaussian_rasterization import _native as N
-import test_gpu_batch as TB
+import native_calls as NC
 dev = torch.device("cuda:0")
 cloud = synth.make_cloud("synth-THuman-800K", seed=0)
 g = synth.make_gaussians(cloud, profile="training", seed=1)
@@ -13,7 +13,7 @@ W, H = 1920, 1080
 views = camera.circle_views(12, fov_deg=45.0, width_px=W, height_px=H)
 P = g["means3D"].shape[0]
 for v in (0, 1, 5):
-    args = TB._batch_args(g, views[v:v + 1], W, H, dev)
+    args = NC.batch_args(g, views[v:v + 1], W, H, dev)
     counts, color, radii, geom, binning, img = N.rasterize_gaussians_batch(*args, need_backward=True)
     need = N.query("TILE_NEED", P, W, H, counts[0], geom, binning, img).cpu().numpy().astype(np.int64)
     rng = N.query("RANGES", P, W, H, counts[0], geom, binning, img).cpu().numpy().astype(np.int64)

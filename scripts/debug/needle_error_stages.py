@@ -1,12 +1,12 @@
 import sys
 sys.path[:0]=['/root/repo','/root/repo/tests','/root/repo/gaussian-pcloud-render_amd']
 import numpy as np, util
-import test_gpu_fuzz as F
+import sweep_support as F
 from oracle.oracle import Oracle
 f=np.float32; d=np.float64
 def fma(a,b,c): return (a.astype(d)*b.astype(d)+c.astype(d)).astype(f)
 case=int(sys.argv[1]); gid=int(sys.argv[2])
-s,mode=F._case(case)
+s,mode=F.random_case(case)
 dL=util.seeded_dL(s,seed=77+case)
 o,g=Oracle().forward_backward(s,dL,exact=True)
 ex=g["exact"]

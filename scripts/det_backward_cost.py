@@ -23,7 +23,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from diff_gaussian_rasterization import _native as N
-    import test_gpu_channels_backward as CB
+    import native_calls as NC
     dev = torch.device("cuda:0")
     W, H = 1920, 1080
     lines = []
@@ -33,8 +33,8 @@ def main():
         lines.append(s)
 
     for V in (12, 1):
-        g, views, _, _ = CB._scene(V, P=a.points, W=W, H=H)
-        args = CB._args(g, views, W, H, dev, (0.0, 0.0, 0.0))
+        g, views, _, _ = NC.circle_scene(V, P=a.points, W=W, H=H)
+        args = NC.cloud_args(g, views, W, H, dev, (0.0, 0.0, 0.0))
         run = N.rasterize_gaussians_batch(*args, need_backward=True)
         run = N.rasterize_gaussians_batch(*args, need_backward=True)      # (the second call's arena is sized from the first's counts)
         counts, color, radii, geom, binning, img = run

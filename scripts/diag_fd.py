@@ -5,7 +5,7 @@ for p in (ROOT, os.path.join(ROOT, "gaussian-pcloud-render_amd"), os.path.join(R
     sys.path.insert(0, p)
 import numpy as np, torch
 import util
-import test_gpu_configs as T
+import sweep_support as T
 from pcrender import camera, synth
 dev = torch.device("cuda:0")
 cloud = synth.make_cloud("synth-THuman-800K", seed=0)
@@ -17,4 +17,4 @@ _, g = util.run_product(s, dev, dL_dpix=dL, light=True)
 for field, key in (("means3D", "dL_dmean3D"), ("scales", "dL_dscale")):
     for eps in (0.2, 0.05, 0.0125, 0.003):
         rng = np.random.default_rng(77)
-        T._fd_single_gaussians(s, dev, g, dL, field, key, eps, 32, rng, "eps=%g" % eps, in_plane=True)
+        T.fd_single_gaussians(s, dev, g, dL, field, key, eps, 32, rng, "eps=%g" % eps, in_plane=True)

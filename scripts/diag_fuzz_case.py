@@ -4,11 +4,11 @@ import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "gaussian-pcloud-render_amd")]
 import numpy as np, torch
-import util, test_gpu_fuzz as F
+import util, sweep_support as F
 from oracle.oracle import Oracle, Reference
 
 i = int(sys.argv[1])
-s, mode = F._case(i)
+s, mode = F.random_case(i)
 print("case", i, "P", s.P, "W,H", s.W, s.H, "mode", mode, "M", s.M, "D", s.sh_degree, "mod", s.scale_modifier)
 dL = util.seeded_dL(s, seed=77 + i)
 r, gr = Reference("strict").forward_backward(s, dL)

@@ -4,15 +4,15 @@ import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "gaussian-pcloud-render_amd")]
 import numpy as np, torch
-import util, test_gpu_fuzz as F
+import util, sweep_support as F
 dev = torch.device("cuda:0")
 i = int(sys.argv[1]); nb = int(sys.argv[2]) if len(sys.argv) > 2 else 40
-s, mode = F._case(i)
+s, mode = F.random_case(i)
 dL = util.seeded_dL(s, seed=77 + i)
 print("case", i, "P", s.P, "W,H", s.W, s.H, "mode", mode, "M", None if s.shs is None else s.shs.shape[1], "D", s.sh_degree, "cov3d", s.cov3D_precomp is not None)
 p0, g0 = util.run_product(s, dev, dL_dpix=dL)
 for j in range(i - nb, i):
-    sj, mj = F._case(j)
+    sj, mj = F.random_case(j)
     util.run_product(sj, dev, dL_dpix=util.seeded_dL(sj, seed=77 + j))
 for rep in range(3):
     p1, g1 = util.run_product(s, dev, dL_dpix=dL)

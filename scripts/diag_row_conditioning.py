@@ -5,11 +5,11 @@ import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "gaussian-pcloud-render_amd")]
 import numpy as np, torch
-import util, test_gpu_fuzz as F
+import util, sweep_support as F
 from oracle.oracle import Oracle, Reference
 from fp64_backward import gaussian_backward_fp64
 i = int(sys.argv[1])
-s, mode = F._case(i)
+s, mode = F.random_case(i)
 dL = util.seeded_dL(s, seed=77 + i)
 r, gr = Reference("strict").forward_backward(s, dL)
 of, og = Oracle().forward_backward(s, dL)

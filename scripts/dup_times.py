@@ -7,14 +7,14 @@ import numpy as np, torch
 from pcrender import camera, synth
 from diff_gaussian_rasterization import _native as N
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import test_gpu_batch as TB
+import native_calls as NC
 dev = torch.device("cuda:0")
 cloud = synth.make_cloud("synth-THuman-800K", seed=0)
 g = synth.make_gaussians(cloud, profile="training", seed=1)
 views = camera.circle_views(12, fov_deg=45.0, width_px=1920, height_px=1080)
 out = (C.c_ulonglong * 8)()
 for V in (1, 12):
-    args = TB._batch_args(g, views[:V], 1920, 1080, dev)
+    args = NC.batch_args(g, views[:V], 1920, 1080, dev)
     for _ in range(2):
         N.rasterize_gaussians_batch(*args, need_backward=False)
     torch.cuda.synchronize()
@@ -28,7 +28,7 @@ for V in (1, 12):
           % (V, n, us[0], us[1], us[2], us[3], sum(us)))
 # cross-check against the stage's own duration
 N.set_profiling(True)
-args = TB._batch_args(g, views[:12], 1920, 1080, dev)
+args = NC.batch_args(g, views[:12], 1920, 1080, dev)
 N.lib.gsr_debug_dup_times(out, 1)
 N.rasterize_gaussians_batch(*args, need_backward=False)
 torch.cuda.synchronize()

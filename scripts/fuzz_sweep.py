@@ -12,16 +12,18 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "gaussian-
 
 def worker(k, n_workers, first, n_cases, q):
     import torch
-    import test_gpu_fuzz as F
+    import grad_ladder
+    import sweep_support as F
     dev = torch.device("cuda:0")
+    tally = grad_ladder.new_tally()
     failed = []
     for i in range(first + k, first + n_cases, n_workers):
         try:
-            F.test_random_case_matches_reference_build(i, dev)
+            F.check_random_case(i, dev, tally)
         except AssertionError as e:
             failed.append((i, str(e).splitlines()[0][:300]))
             print("FAILED case %d: %s" % (i, failed[-1][1]), flush=True)
-    q.put((dict(F.TALLY), failed))
+    q.put((dict(tally), failed))
 
 
 def main():
@@ -49,7 +51,7 @@ def main():
             failed += f
         cases = tally["cases_exit_4x_reference"] + tally["cases_exit_conditioning"]
         rows = tally["rows_exit_4x_reference"] + tally["rows_exit_conditioning"]
-        import test_gpu_fuzz as F
+        import grad_ladder as F
         over = cases > max(1, int(F.MAX_CASE_FRACTION * n_cases)) or rows > max(2, int(F.MAX_ROW_FRACTION * tally["rows"]))
         print(json.dumps(dict(run=run, n_cases=n_cases, first=opt["first"], seconds=round(time.time() - t0, 1), tally=tally,
                               failed=sorted(failed), exits_over_cap=over)), flush=True)

@@ -110,7 +110,7 @@ def main():
     import numpy as np
     import torch
     from diff_gaussian_rasterization import _native as N
-    import test_gpu_channels_backward as CB
+    import native_calls as NC
     dev = torch.device("cuda:0")
 
     def spread(xs):
@@ -128,8 +128,8 @@ def main():
             % (a.calls, a.blocks, N.lib.gsr_version().decode()))
         W, H = 1920, 1080
         for V in (12, 1):
-            g, views, _, _ = CB._scene(V, P=a.points, W=W, H=H)
-            args = CB._args(g, views, W, H, dev, (1.0, 1.0, 1.0))
+            g, views, _, _ = NC.circle_scene(V, P=a.points, W=W, H=H)
+            args = NC.cloud_args(g, views, W, H, dev, (1.0, 1.0, 1.0))
             dpix = torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, (V, 3, H, W)).astype(np.float32)).to(dev)
             N.rasterize_gaussians_batch(*args, need_backward=True)      # (the next call's arena is sized from this one's counts)
             pairs = None
@@ -179,7 +179,7 @@ def main():
 
         # ---- accuracy of the render-level sums against float64, in units of the reference build's error
         import util
-        import test_gpu_fuzz as FZ
+        import sweep_support as FZ
         from oracle.oracle import Oracle, Reference
         import scripts.bwd_accuracy as BA
         ref, orc = Reference("strict"), Oracle()
@@ -188,7 +188,7 @@ def main():
         ratio = {m: {n: [] for n in names} for m in (0, 1)}
         used = 0
         for c in range(a.cases):
-            s, _ = FZ._case(c)
+            s, _ = FZ.random_case(c)
             if s.P == 0:
                 continue
             dL = util.seeded_dL(s, seed=77 + c)

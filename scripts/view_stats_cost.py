@@ -36,13 +36,13 @@ def main():
     import numpy as np
     import torch
     from diff_gaussian_rasterization import _native as N
-    import test_gpu_channels_backward as CB
+    import native_calls as NC
     if not torch.cuda.is_available():
         raise SystemExit("view_stats_cost.py measures on the GPU: no HIP device is visible")
     dev = torch.device("cuda:0")
     W, H, V, P = 1920, 1080, a.views, a.points
-    g, views, _, _ = CB._scene(V, P=P, W=W, H=H)
-    args = CB._args(g, views, W, H, dev, (1.0, 1.0, 1.0))
+    g, views, _, _ = NC.circle_scene(V, P=P, W=W, H=H)
+    args = NC.cloud_args(g, views, W, H, dev, (1.0, 1.0, 1.0))
     dpix = torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, (V, 3, H, W)).astype(np.float32)).to(dev)
     stats = (torch.zeros(P, device=dev), torch.zeros(P, dtype=torch.int32, device=dev), torch.zeros(P, dtype=torch.int32, device=dev))
     shares = (torch.empty((V, P, 2), device=dev), torch.empty((V, P, 3), device=dev), torch.empty((V, P), device=dev))

@@ -9,7 +9,7 @@ rounding (priced by the colour and channels sweeps) and needs no float64 render 
 Gaussians.
 
   ids / writer / recolors / CHANNEL_CASES   which of batch_cases' (channel_cases') cases the sweep takes and what it does with each
-  _args / _prefilled / _cameras             the call: arguments, NaN-filled outputs, a 0xFF-filled scratch block
+  _prefilled / _cameras                     the call (arguments: native_calls): NaN-filled outputs, a 0xFF-filled scratch block
   records / arbiter / hold_views            records and mask read back, fed to the arbiter, held; exits / live / worst tallied
   views_held / clamp_flips                  the two rules, from the inputs alone, by which a view is not compared"""
 import numpy as np
@@ -18,6 +18,7 @@ import batch_cases as BC
 import camera_cases as CC
 import util
 from fp64_camera import camera_backward_fp64
+from native_calls import follower_args
 
 F = np.float32
 N_SMALL = BC.N_SMALL
@@ -116,25 +117,6 @@ def clamp_flips(s, radii):
 
 
 # ---- the call ---------------------------------------------------------------------------------------------------------------
-def _t(a, dev):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _args(scenes, dev):
-    """rasterize_gaussians_batch arguments for views of one cloud, given as oracle Scenes"""
-    import torch
-    s = scenes[0]
-    e = torch.empty(0)
-    a = lambda x: e if x is None else _t(x, dev)  # noqa: E731
-    vm = _t(np.stack([x.viewmatrix.reshape(4, 4) for x in scenes]), dev)
-    pm = _t(np.stack([x.projmatrix.reshape(4, 4) for x in scenes]), dev)
-    cp = _t(np.stack([x.campos.reshape(3) for x in scenes]), dev)
-    return [a(s.bg), a(s.means3D), a(s.colors_precomp), a(s.opacities.reshape(-1, 1)), a(s.scales), a(s.rotations),
-            float(s.scale_modifier), a(s.cov3D_precomp), vm, pm, s.tanfovx, s.tanfovy, s.H, s.W, a(s.shs),
-            int(s.sh_degree) if s.shs is not None else 0, cp, False, False]
-
-
 def _prefilled(N, V, P, dev):
     import torch
     out = (torch.full((V, 4, 4), float("nan"), device=dev), torch.full((V, 4, 4), float("nan"), device=dev),
@@ -148,8 +130,7 @@ def _cameras(N, args, radii, geom, V=None):
     dev = args[1].device
     V = args[8].shape[0] if V is None else V
     out, scratch = _prefilled(N, V, args[1].shape[0], dev)
-    N.backward_cameras(args[0], args[1], radii[:V], args[2], args[4], args[5], args[6], args[7], args[8][:V], args[9][:V], args[10],
-                       args[11], args[12], args[13], args[14], args[15], args[16][:V], geom, _out=out, _scratch=scratch)
+    N.backward_cameras(*follower_args(args, radii, geom, V), _out=out, _scratch=scratch)
     dv, dp, dc = (o.cpu().numpy() for o in out)
     assert np.isfinite(dv).all() and np.isfinite(dp).all() and np.isfinite(dc).all(), "an output was left unwritten"
     return [dict(dL_dviewmatrix=dv[v].reshape(16), dL_dprojmatrix=dp[v].reshape(16), dL_dcampos=dc[v]) for v in range(V)]

@@ -71,14 +71,14 @@ def draws(i):
 
 
 def case(i):
-    from test_gpu_channels_fp64 import _inputs
+    from fp64_pins import channel_inputs
     c = BC.case(batch_index(i))
     d = draws(i)
     if i >= MEDIUM_BASE and i - MEDIUM_BASE in MEDIUM_POINTS:
         P0, P1 = c["g"]["means3D"].shape[0], MEDIUM_POINTS[i - MEDIUM_BASE]
         c["g"] = {k: a[:P1] if isinstance(a, np.ndarray) and a.shape[0] == P0 else a for k, a in c["g"].items()}
     V, P = len(c["views"]), c["g"]["means3D"].shape[0]
-    x, dense, sc, bgx, dpix, dx = _inputs(P, V, d["nx"], d["layout"], seed=13000 + i, H=c["H"], W=c["W"],
+    x, dense, sc, bgx, dpix, dx = channel_inputs(P, V, d["nx"], d["layout"], seed=13000 + i, H=c["H"], W=c["W"],
                                           scales=ROUNDED_SCALES if d["scale_class"] == "rounded" else EXACT_SCALES)
     return dict(d, i=i, batch=c, x=x, dense=dense, scale=None if d["no_scale"] else sc, bg_extra=bgx, dpix=dpix, dx=dx)
 

@@ -184,6 +184,18 @@ def hold_to_reference(tag, seed, gp, gr, f64, tally, label="fuzz"):
     tally["cases_reference_outside_too"] += int(used_ref_too and not (used_4x or used_cond))
 
 
+# How often a case / a gradient row may leave through a fallback of hold_to_reference.  The bars are principled (float32 conditioning
+# of the per-Gaussian chain), but nothing stops them from being widened until everything passes, so the exits are counted and capped:
+# the closing test of every sweep fails when more than 1 % of the cases or 1e-4 of the rows compared need one.
+# `*_reference_outside_too`: rows outside the plain bar against the float64 value in which the library is at least as close to it as
+# the reference build is -- the reference itself misses the bar there; not an escape of the library, but a drift towards such rows
+# should still show: a looser cap of its own
+MAX_CASE_FRACTION = 0.01
+MAX_ROW_FRACTION = 1e-4
+MAX_CASE_FRACTION_REF_TOO = 0.02
+MAX_ROW_FRACTION_REF_TOO = 4e-4
+
+
 def assert_exits_stay_rare(tally, max_case_fraction, max_row_fraction, max_case_fraction_ref_too, max_row_fraction_ref_too):
     cases = tally["cases_exit_4x_reference"] + tally["cases_exit_conditioning"]
     rows = tally["rows_exit_4x_reference"] + tally["rows_exit_conditioning"]

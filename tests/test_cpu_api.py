@@ -8,6 +8,8 @@ import re
 import pytest
 import torch
 
+from native_calls import unit_settings as _settings
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -60,14 +62,6 @@ def test_python_surface_matches_reference():
     assert issubclass(d._RasterizeGaussians, torch.autograd.Function)
     t = d.cpu_deep_copy_tuple((torch.ones(2), 3, "x"))
     assert t[1] == 3 and t[2] == "x" and torch.equal(t[0], torch.ones(2))
-
-
-def _settings():
-    import diff_gaussian_rasterization as d
-    return d.GaussianRasterizationSettings(
-        image_height=8, image_width=8, tanfovx=1.0, tanfovy=1.0, bg=torch.zeros(3), scale_modifier=1.0,
-        viewmatrix=torch.eye(4), projmatrix=torch.eye(4), sh_degree=0, campos=torch.zeros(3), prefiltered=False,
-        debug=False)
 
 
 def test_argument_validation_is_the_reference_s():

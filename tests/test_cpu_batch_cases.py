@@ -6,8 +6,7 @@ import numpy as np
 
 import batch_cases as BC
 import util
-from grad_ladder import Float64
-from test_gpu_fuzz import MAX_CASE_FRACTION_REF_TOO, MAX_ROW_FRACTION_REF_TOO
+from grad_ladder import MAX_CASE_FRACTION_REF_TOO, MAX_ROW_FRACTION_REF_TOO, Float64
 
 SMALL = list(range(BC.N_SMALL))
 REF_ONLY = SMALL           # the reference-only check runs the whole small class (under a minute on 16 CPUs)

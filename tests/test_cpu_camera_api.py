@@ -9,6 +9,9 @@ import numpy as np
 import pytest
 import torch
 
+from native_calls import unit_settings as _settings
+from refusal_tables import follower_params as _params
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 A, B, Cc, D, E, Fp = 0x1000, 0x2000, 0x3000, 0x4000, 0x5000, 0x6000   # stand-ins for device arrays (never followed)
 
@@ -48,14 +51,6 @@ def test_camera_grad_bytes():
     assert 12 * 782 * 256 <= f(12, 800_000) <= 12 * 782 * 256 + 512
 
 
-def _params(N, P=10, W=8, H=8):
-    p = N.GsrParams()
-    p.P, p.W, p.H = P, W, H
-    for name in ("bg", "means3D", "opacities", "viewmatrix", "projmatrix", "campos", "colors_precomp", "cov3D_precomp"):
-        setattr(p, name, A)
-    return p
-
-
 def test_refusals_before_any_hip_call():
     from diff_gaussian_rasterization import _native as N
     call = N.lib.gsr_backward_cameras
@@ -89,14 +84,6 @@ def test_refusals_before_any_hip_call():
     # a NULL pointer is reported before the scratch size
     rc, err = run(_params(N), dv=None, scratch_bytes=0)
     assert rc == -1 and b"NULL" in err
-
-
-def _settings():
-    import diff_gaussian_rasterization as d
-    return d.GaussianRasterizationSettings(
-        image_height=8, image_width=8, tanfovx=1.0, tanfovy=1.0, bg=torch.zeros(3), scale_modifier=1.0,
-        viewmatrix=torch.eye(4), projmatrix=torch.eye(4), sh_degree=0, campos=torch.zeros(3), prefiltered=False,
-        debug=False)
 
 
 def test_rasterize_views_cameras_validates_and_refuses_cpu_tensors():

@@ -12,12 +12,8 @@ import sys
 import pytest
 import torch
 
-import test_cpu_backward_refusals as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "gaussian-pcloud-render_amd")
-P, W, H, PAIRS, PTR, ROT = R.P, R.W, R.H, R.PAIRS, R.PTR, R.ROT
-NX, LAYOUT = 8, 1
+import refusal_tables as RT
+from refusal_tables import BACKWARD_EXPECTED as EXPECTED, LAYOUT, NX, PAIRS, PKG, PTR, ROT, H, P, W
 
 
 def test_library_exports_the_deterministic_channels_entries():
@@ -66,60 +62,9 @@ def test_scratch_size_query():
 def _run_table():
     """(child process, no device) -> {"rows": {case: [[rc, text] of gsr_backward_batch_channels, [rc, text] of the new entry]},
     "scratch": {case: [rc, text]}, "sizes": {...}}"""
-    from diff_gaussian_rasterization import _native as N
+    N = RT.native_without_device()
     lib = N.lib
-    if lib.gsr_wall_clock_khz() != 0:
-        raise SystemExit("a HIP device is visible: the forwards below would launch kernels on host memory")
-    keep = []
-
-    def params(P=P, W=W, H=H, M=0, need_backward=1, **ptr):
-        p = N.GsrParams()
-        p.P, p.W, p.H, p.M, p.need_backward = P, W, H, M, need_backward
-        for k in ("means3D", "opacities", "bg", "viewmatrix", "projmatrix", "campos", "colors_precomp", "scales", "rotations"):
-            setattr(p, k, PTR)
-        for k, v in ptr.items():
-            setattr(p, k, v)
-        return p
-
-    def buf(n):
-        b = C.create_string_buffer(int(n))
-        keep.append(b)
-        return C.addressof(b)
-
-    def arenas(V):
-        return dict(geom=buf(16), geom_bytes=V * lib.gsr_geom_bytes(P), image=PTR, image_bytes=V * lib.gsr_image_bytes(W, H),
-                    binning=PTR, binning_bytes=V * lib.gsr_binning_bytes(PAIRS), state=buf(16),
-                    state_bytes=V * lib.gsr_extra_state_bytes(W, H, PAIRS, NX) + 256)
-
-    def forward(a, V, kind, nb):
-        p, n = params(need_backward=nb), (C.c_int64 * V)()
-        head = (C.byref(p), V, a["geom"], a["geom_bytes"], a["image"], a["image_bytes"], a["binning"], a["binning_bytes"], PTR, PTR, n, 0)
-        x = (NX, LAYOUT, PTR, None, PTR, PTR)
-        if kind == "colour":
-            rc = lib.gsr_forward_batch(*head, None)
-        elif kind == "infer":
-            rc = lib.gsr_forward_batch_channels(*head, *x, None)
-        else:
-            rc = lib.gsr_forward_batch_channels_train(*head, *x, a["state"], a["state_bytes"], None)
-        assert rc == -2, (rc, lib.gsr_last_error())
-
-    def recolor(a, V, nb):
-        p = params(need_backward=nb)
-        rc = lib.gsr_forward_recolor(C.byref(p), V, 0, a["geom"], a["geom_bytes"], a["binning"], a["binning_bytes"], a["image"],
-                                     a["image_bytes"], PTR, None)
-        assert rc != 0
-
-    def frame(name):
-        V = 2 if name.endswith("_v2") else 1
-        a = arenas(V)
-        name = name[:-3] if V == 2 else name
-        steps = {"none": [], "fwd_nb1": [("colour", 1)], "fwd_nb0": [("colour", 0)], "chan_train": [("train", 1)],
-                 "chan_train_nb0": [("train", 0)], "chan_infer": [("infer", 1)], "recolor_nb0": [("colour", 1), ("recolor", 0)],
-                 "recolor_on_fwd_nb0": [("colour", 0), ("recolor", 1)], "recolor_nb1_no_record": [("recolor", 1)],
-                 "recolor_on_chan_train": [("train", 1), ("recolor", 1)]}[name]
-        for kind, nb in steps:
-            recolor(a, V, nb) if kind == "recolor" else forward(a, V, kind, nb)
-        return a
+    frame = lambda name: RT.frame(N, name)  # noqa: E731
 
     def call(fr, kw, which):
         """which: 'channels', or 'det' (the new entry; scratch / scratch_bytes from kw, default a dummy pointer of 0 bytes)"""
@@ -132,7 +77,7 @@ def _run_table():
         if "binning_pairs" in kw:
             c["binning_bytes"] = lib.gsr_binning_bytes(kw.pop("binning_pairs"))
         c.update(kw)
-        p = params(**pk)
+        p = RT.params(N, **pk)
         args = [C.byref(p) if c["params"] else None, c["V"], c["radii"], c["geom"], c["geom_bytes"], c["binning"], c["binning_bytes"],
                 c["image"], c["image_bytes"], c["dpix"], c["dmean2D"], c["dopacity"], c["dcolor"], c["dmean3D"], c["dcov3D"], c["dsh"],
                 c["dscale"], c["drot"], c["nx"], c["layout"], c["extra"], None, c["bg_extra"], c["state"], c["state_bytes"],
@@ -144,12 +89,12 @@ def _run_table():
         return [rc, lib.gsr_last_error().decode() if rc != 0 else ""]
 
     rows = {}
-    for entry, case, fr, kw in R._table():
+    for entry, case, fr, kw in RT.backward_table():
         if entry != "channels":
             continue
         a = frame(fr)
         if kw.get("state") == "other":
-            kw = dict(kw, state=buf(16))
+            kw = dict(kw, state=RT.buf(16))
         rows[case] = [call(a, kw, "channels"), call(a, kw, "det")]
 
     # the scratch block's own faults, on arenas every other check passes
@@ -177,17 +122,12 @@ def _run_table():
 
 @pytest.fixture(scope="module")
 def refusals():
-    e = dict(os.environ)
-    e["PYTHONPATH"] = os.pathsep.join([PKG, os.path.join(ROOT, "tests"), e.get("PYTHONPATH", "")])
-    e["HIP_VISIBLE_DEVICES"] = e["ROCR_VISIBLE_DEVICES"] = "-1"      # the child sees no device, wherever the suite runs
-    out = subprocess.run([sys.executable, os.path.abspath(__file__)], env=e, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout + out.stderr
-    return json.loads(out.stdout.strip().splitlines()[-1])
+    return RT.child_json(__file__)
 
 
 def test_every_channels_refusal_is_the_new_entrys_too(refusals):
     rows = refusals["rows"]
-    want = sorted(k[len("channels/"):] for k in R.EXPECTED if k.startswith("channels/"))
+    want = sorted(k[len("channels/"):] for k in EXPECTED if k.startswith("channels/"))
     assert len(want) >= 40 and sorted(rows) == want                    # every case of the existing channels rows
     wrong = {k: v for k, v in rows.items() if v[0] != v[1] or v[0][0] == 0}
     assert not wrong, "\n".join("%s: gsr_backward_batch_channels %r, gsr_backward_batch_channels_det %r" % (k, a, b)
@@ -197,7 +137,7 @@ def test_every_channels_refusal_is_the_new_entrys_too(refusals):
 def test_channels_entry_still_refuses_as_pinned(refusals):
     """(the live comparison above compares against THIS build's channels entry: it still answers with the committed literals)"""
     for k, (a, _) in refusals["rows"].items():
-        assert tuple(a) == R.EXPECTED["channels/" + k], k
+        assert tuple(a) == EXPECTED["channels/" + k], k
 
 
 @pytest.mark.parametrize("case", ["null", "one_byte_short", "colour_sized", "zero_bytes", "two_views"])

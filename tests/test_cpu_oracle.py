@@ -60,7 +60,7 @@ def test_oracle_matches_reference_build_golden(name, oracle):
     assert err[~flips].max(initial=0.0) <= 1e-4          # north_star tolerance, fp32 max abs
     # gradients (reference = float atomics in arbitrary order, oracle = double accumulation)
     if not flips.any():
-        for k in ("dL_dmean2D", "dL_dcolor", "dL_dopacity", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot"):
+        for k in util.GRAD_NAMES:
             a, b = go[k].astype(np.float64).ravel(), g[k].astype(np.float64).ravel()
             if b.size:
                 assert np.abs(a - b).max() <= 2e-4 * np.abs(b).max() + 1e-30, k

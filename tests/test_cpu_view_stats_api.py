@@ -11,6 +11,9 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from native_calls import unit_settings as _settings
+from refusal_tables import follower_params as _params
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 A, B, Cc, D, E, Fp, G, Hh = 0x1000, 0x2000, 0x3000, 0x4000, 0x5000, 0x6000, 0x7000, 0x8000   # stand-ins for device arrays (never followed)
 
@@ -35,14 +38,6 @@ def test_symbol_is_exported_declared_and_bound():
     # the recolor paragraph no longer says that the per-view colour gradients cannot be had
     text = open(os.path.join(ROOT, "include", "gsr.h")).read()
     assert "the per-view shares are not separated" not in text and "dL_dcolor_views" in text
-
-
-def _params(N, P=10, W=8, H=8):
-    p = N.GsrParams()
-    p.P, p.W, p.H = P, W, H
-    for name in ("bg", "means3D", "opacities", "viewmatrix", "projmatrix", "campos", "colors_precomp", "cov3D_precomp"):
-        setattr(p, name, A)
-    return p
 
 
 def test_refusals_before_any_hip_call():
@@ -104,14 +99,6 @@ def test_density_stats():
         assert t is k and not t.any()             # in place: the tensors a trainer holds on to stay the accumulators
     st0 = d.DensityStats(0, "cpu", keep_view_grads=True)
     assert st0.keep_view_grads is True and st0.grad_norm_sum.shape == (0,) and st0.mean_grad().shape == (0,)
-
-
-def _settings():
-    import diff_gaussian_rasterization as d
-    return d.GaussianRasterizationSettings(
-        image_height=8, image_width=8, tanfovx=1.0, tanfovy=1.0, bg=torch.zeros(3), scale_modifier=1.0,
-        viewmatrix=torch.eye(4), projmatrix=torch.eye(4), sh_degree=0, campos=torch.zeros(3), prefiltered=False,
-        debug=False)
 
 
 def test_rasterize_views_stats_validates_and_refuses_cpu_tensors():

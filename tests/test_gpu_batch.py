@@ -11,33 +11,10 @@ import pytest
 import torch
 
 import util
+from native_calls import batch_args as _batch_args, colour_backward_args, cloud_views as _views_scene, to_device as _t
 from util import check_grads
 
 pytestmark = pytest.mark.gpu
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _views_scene(n_views=3, P=12000, W=208, H=176, profile="training"):
-    """One cloud, n_views circle cameras (view 0 is axis aligned: depth ties on the voxelised cloud)."""
-    from pcrender import camera, synth
-    cloud = synth.make_cloud("synth-THuman-256", seed=0, P=P)
-    g = synth.make_gaussians(cloud, profile=profile, seed=1)
-    views = camera.circle_views(12, fov_deg=45.0, width_px=W, height_px=H)
-    pick = [0, 1, 5, 7, 10][:n_views]
-    return g, [views[i] for i in pick], W, H
-
-
-def _batch_args(g, views, W, H, dev, bg=(1, 1, 1)):
-    e = torch.empty(0)
-    vm = torch.stack([v["viewmatrix"] for v in views]).to(dev)
-    pm = torch.stack([v["projmatrix"] for v in views]).to(dev)
-    cp = torch.stack([v["campos"] for v in views]).to(dev)
-    return (_t(np.asarray(bg, np.float32), dev), _t(g["means3D"], dev), e, _t(g["opacities"], dev), _t(g["scales"], dev),
-            _t(g["rotations"], dev), 1.0, e, vm, pm, views[0]["tanfovx"], views[0]["tanfovy"], H, W, _t(g["shs"], dev),
-            g["sh_degree"], cp, False, False)
 
 
 def test_batch_forward_backward_vs_oracle(oracle, gpu_device):
@@ -50,9 +27,8 @@ def test_batch_forward_backward_vs_oracle(oracle, gpu_device):
     assert color.shape == (V, 3, H, W) and radii.shape == (V, g["means3D"].shape[0])
     rng = np.random.default_rng(9)
     dL = rng.uniform(-1, 1, (V, 3, H, W)).astype(np.float32)
-    grads = N.rasterize_gaussians_backward_batch(args[0], args[1], radii, args[2], args[4], args[5], 1.0, args[7], args[8], args[9],
-                                                 args[10], args[11], _t(dL, dev), args[14], args[15], args[16], geom, binning, img, False)
-    names = ("dL_dmean2D", "dL_dcolor", "dL_dopacity", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot")
+    grads = N.rasterize_gaussians_backward_batch(*colour_backward_args(args, (counts, color, radii, geom, binning, img), _t(dL, dev), 1.0))
+    names = util.GRAD_NAMES
     gp = {n: x.cpu().numpy() for n, x in zip(names, grads)}
     total = None
     flips = 0
@@ -220,7 +196,7 @@ def test_batch_edge_cases_vs_oracle(oracle, gpu_device):
     assert all(torch.isfinite(x).all() for x in grads)
     # the gradients of the 17 views (one of them empty) against the summed oracle gradients -- or, after an expf threshold flip
     # between glibc and ocml, the summed reference-build gradients -- like test_batch_forward_backward_vs_oracle
-    names = ("dL_dmean2D", "dL_dcolor", "dL_dopacity", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot")
+    names = util.GRAD_NAMES
     gp = {n: x.cpu().numpy() for n, x in zip(names, grads)}
     ones = np.ones((3, H, W), np.float32)
     scenes = [util.scene_from(g, v, W, H, bg=(0.2, 0.5, 0.7)) for v in vs]

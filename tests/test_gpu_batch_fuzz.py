@@ -27,9 +27,11 @@ import torch
 
 import batch_cases as BC
 import util
-from grad_ladder import Float64, assert_exits_stay_rare, hold_to_reference, new_tally
-from test_gpu_channels_fp64 import _args, _t
-from test_gpu_fuzz import MAX_CASE_FRACTION, MAX_CASE_FRACTION_REF_TOO, MAX_ROW_FRACTION, MAX_ROW_FRACTION_REF_TOO
+from grad_ladder import (MAX_CASE_FRACTION, MAX_CASE_FRACTION_REF_TOO, MAX_ROW_FRACTION, MAX_ROW_FRACTION_REF_TOO, Float64,
+                         assert_exits_stay_rare, hold_to_reference, new_tally)
+from native_calls import reference_lists, scene_args as _args, to_device as _t
+from sweep_support import (check_view_against_reference as _check_view_against_reference, records_backward as _backward,
+                           same_bits as _same_bits, view_query as _q)
 
 pytestmark = pytest.mark.gpu
 
@@ -40,49 +42,6 @@ NAMES = util.GRAD_NAMES
 TALLY = new_tally()
 STATS = dict(views=0, float64_cases=0, retry_eligible=0, partial_retries=0, deterministic_runs=0, depth_passes_of_mixed_cases={},
              depth_passes_seen=set())
-
-
-def _q(N, name, P, W, H, R, run, v, V):
-    return N.query(name, P, W, H, R, run[3], run[4], run[5], view=v, n_views=V)
-
-
-def _backward(N, args, run, dL_t, det, pairs=None):
-    """one colour backward on the arenas of `run`: the eight gradients and the per-view records [V, P, 16], numpy"""
-    counts, color, radii, geom, binning, img = run[:6]
-    g = N.rasterize_gaussians_backward_batch(args[0], args[1], radii, args[2], args[4], args[5], args[6], args[7], args[8], args[9],
-                                             args[10], args[11], dL_t, args[14], args[15], args[16], geom, binning, img, False,
-                                             deterministic=det, pairs=pairs)
-    out = {n: t.detach().cpu().numpy() for n, t in zip(NAMES, g)}
-    P, V = args[1].shape[0], dL_t.shape[0]
-    rec = np.stack([N.grad_records(geom, P, view=v, n_views=V).cpu().numpy() for v in range(V)])
-    return out, rec
-
-
-def _same_bits(a, b):
-    return all(np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)) for k in a)
-
-
-def _check_view_against_reference(N, tag, r, run, v, V, P, W, H, mode):
-    counts, color, radii = run[:3]
-    assert counts[v] == r["R"], tag
-    np.testing.assert_array_equal(radii[v].cpu().numpy(), r["radii"], err_msg=tag + " radii")
-    R = r["R"]
-    for name, key, dt in (("TILES_TOUCHED", "tiles_touched", np.uint32), ("POINT_LIST", "vals", np.uint32),
-                          ("POINT_LIST_KEYS", "keys", np.uint64), ("RANGES", "ranges", np.uint32), ("N_CONTRIB", "n_contrib", np.uint32)):
-        a = _q(N, name, P, W, H, R, run, v, V).cpu().numpy().view(dt)
-        np.testing.assert_array_equal(a.reshape(-1), np.asarray(r[key]).astype(dt).reshape(-1), err_msg="%s %s" % (tag, key))
-    vis = r["radii"] > 0
-    for name, key in (("DEPTHS", "depths"), ("MEANS2D", "means2D"), ("CONIC_OPACITY", "conic_opacity")) + \
-            (() if mode == "colors" else (("RGB", "rgb"),)):
-        a = _q(N, name, P, W, H, R, run, v, V).cpu().numpy()
-        assert a[vis].tobytes() == r[key][vis].tobytes(), "%s %s" % (tag, key)
-    assert _q(N, "FINAL_T", P, W, H, R, run, v, V).cpu().numpy().tobytes() == r["final_T"].tobytes(), tag + " final_T"
-    assert color[v].cpu().numpy().tobytes() == r["out_color"].tobytes(), tag + " out_color"
-    # the view's depth-sort control words: what sort.hip derives from the keys (depth bits) of the Gaussians that emit pairs
-    words = _q(N, "DEPTH_SORT", P, W, H, R, run, v, V).cpu().numpy().view(np.uint32)
-    want = BC.depth_sort_words(r["depths"][vis].view(np.uint32))
-    assert tuple(int(x) for x in words[:3]) == want, "%s depth-sort control words %s, the view's keys imply %s" % (tag, words[:3], want)
-    return int(words[2])
 
 
 @pytest.mark.parametrize("i", BC.ids(N_SMALL))
@@ -108,12 +67,9 @@ def test_random_batch_matches_reference_build(i, gpu_device):
         gr = {k: g[k].astype(np.float64) for k in NAMES} if gr is None else {k: gr[k] + g[k] for k in NAMES}
 
     # ---- forward with the reference's full lists
-    old = N.set_reference_lists(True)
-    try:
+    with reference_lists(True):
         full = N.rasterize_gaussians_batch(*args, need_backward=True)
         passes = [_check_view_against_reference(N, "%s view %d" % (tag, v), rf[v], full, v, V, P, W, H, c["mode"]) for v in range(V)]
-    finally:
-        N.set_reference_lists(old)
     STATS["depth_passes_seen"].update(passes)
     if exp["depth_passes"] is not None:
         for v, want in enumerate(exp["depth_passes"]):
@@ -122,8 +78,7 @@ def test_random_batch_matches_reference_build(i, gpu_device):
             STATS["depth_passes_of_mixed_cases"][i] = passes
 
     # ---- forward in the default mode: the batch equals V single-view calls
-    old = N.set_reference_lists(False)
-    try:
+    with reference_lists(False):
         run = N.rasterize_gaussians_batch(*args, need_backward=True)
         pairs = (C.c_int64 * V)()
         assert N.lib.gsr_last_list_pairs(pairs, V) == 0
@@ -190,8 +145,6 @@ def test_random_batch_matches_reference_build(i, gpu_device):
                 STATS["deterministic_runs"] += 1
                 assert _same_bits(d1, d3) and np.array_equal(dr1.view(np.uint32), dr3.view(np.uint32)), tag + ": deterministic, retried arenas"
             util.check_grads(d1, gp, tag + ": deterministic vs atomic", names=NAMES)
-    finally:
-        N.set_reference_lists(old)
 
 
 def test_batch_fuzz_escape_hatches_stay_rare():

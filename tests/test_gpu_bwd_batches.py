@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import util
-from util import run_product, check_grads
+from util import check_grads, run_product, strict_reference as _ref
 
 pytestmark = pytest.mark.gpu
 
@@ -60,10 +60,6 @@ def _check(s, tag, oracle, gpu_device, ref):
         assert (fp["n_contrib"] == fr["n_contrib"]).all(), tag
         check_grads(gp, gr, tag + " vs reference build")
     return fo
-
-
-def _ref():
-    return util.reference_build("strict")
 
 
 @pytest.mark.parametrize("K", COUNTS)

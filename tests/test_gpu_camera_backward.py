@@ -9,7 +9,8 @@ import torch
 
 import camera_cases as CC
 import util
-from camera_sweep import _args, _bits, _cameras, _prefilled, _t
+from camera_sweep import _bits, _cameras, _prefilled
+from native_calls import channels_backward_args, colour_backward_args, follower_args, scene_args as _args, to_device as _t
 
 pytestmark = pytest.mark.gpu
 
@@ -23,11 +24,7 @@ def _forward(N, args, need_backward=True):
 
 
 def _backward(N, args, run, dpix, deterministic=False):
-    radii, geom, binning, img = run
-    g = N.rasterize_gaussians_backward_batch(args[0], args[1], radii, args[2], args[4], args[5], args[6], args[7], args[8], args[9],
-                                             args[10], args[11], dpix, args[14], args[15], args[16], geom, binning, img, False,
-                                             deterministic=deterministic)
-    return g
+    return N.rasterize_gaussians_backward_batch(*colour_backward_args(args, (None, None) + tuple(run), dpix), deterministic=deterministic)
 
 
 def _hold(cams, ref, tag):
@@ -114,9 +111,8 @@ def test_after_a_channels_backward(gpu_device):
     extra = (_t(x, dev), _t(sc, dev), _t(bgx, dev))
     dpix = _t(np.stack(ref["dLs"]), dev)
     counts, color, radii, geom, binning, img, out_x = N.rasterize_gaussians_batch(*args, need_backward=True, extra=extra)
-    N.rasterize_gaussians_backward_channels_batch(args[0], args[1], radii, args[2], args[4], args[5], 1.0, args[7], args[8], args[9],
-                                                  args[10], args[11], dpix, args[14], args[15], args[16], geom, binning, img, False,
-                                                  extra, _t(dx, dev))
+    run = (counts, color, radii, geom, binning, img)
+    N.rasterize_gaussians_backward_channels_batch(*channels_backward_args(args, run, dpix, extra, _t(dx, dev), 1.0))
     cams = _cameras(N, args, radii, geom)
     _hold(cams, ref, "channels")
     run = _forward(N, args)
@@ -169,9 +165,7 @@ def test_refusals_that_need_a_record(gpu_device):
     def refused(radii, geom, message, views=V):
         out, scratch = _prefilled(N, views, P, dev)
         with pytest.raises(RuntimeError, match=message):
-            N.backward_cameras(args[0], args[1], radii[:views], args[2], args[4], args[5], args[6], args[7], args[8][:views],
-                               args[9][:views], args[10], args[11], args[12], args[13], args[14], args[15], args[16][:views], geom,
-                               _out=out, _scratch=scratch)
+            N.backward_cameras(*follower_args(args, radii, geom, views), _out=out, _scratch=scratch)
         torch.cuda.synchronize()
         for o in out:
             assert torch.isnan(o).all(), "a refused call wrote an output"

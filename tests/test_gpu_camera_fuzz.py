@@ -52,7 +52,8 @@ import batch_cases as BC
 import camera_cases as CC
 import camera_sweep as CS
 import channel_cases as CH
-from camera_sweep import _args, _bits, _cameras, _t
+from camera_sweep import _bits, _cameras
+from native_calls import channels_backward_args, colour_backward_args, scene_args as _args, to_device as _t
 
 pytestmark = pytest.mark.gpu
 
@@ -80,10 +81,7 @@ def _pairs(N, V):
 
 
 def _colour_backward(N, args, run, dpix_t, det, n_pairs):
-    counts, color, radii, geom, binning, img = run[:6]
-    N.rasterize_gaussians_backward_batch(args[0], args[1], radii, args[2], args[4], args[5], args[6], args[7], args[8], args[9], args[10],
-                                         args[11], dpix_t, args[14], args[15], args[16], geom, binning, img, False, deterministic=det,
-                                         pairs=n_pairs if det else None)
+    N.rasterize_gaussians_backward_batch(*colour_backward_args(args, run, dpix_t), deterministic=det, pairs=n_pairs if det else None)
 
 
 def _held(N, tag, args, run, scenes, empty, backward, det=False):
@@ -205,9 +203,7 @@ def test_camera_gradients_after_a_channels_backward(k, gpu_device):
     run = N.rasterize_gaussians_batch(*args, need_backward=True, extra=extra)
 
     def backward():
-        N.rasterize_gaussians_backward_channels_batch(args[0], args[1], run[2], args[2], args[4], args[5], args[6], args[7], args[8], args[9],
-                                                      args[10], args[11], dpix_t, args[14], args[15], args[16], run[3], run[4], run[5],
-                                                      False, extra, dx_t)
+        N.rasterize_gaussians_backward_channels_batch(*channels_backward_args(args, run, dpix_t, extra, dx_t))
 
     _held(N, tag, args, run, scenes, b["empty"], backward)
     STATS["channels"] += 1

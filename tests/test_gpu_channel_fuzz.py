@@ -44,10 +44,11 @@ import batch_cases as BC
 import channel_cases as CC
 import util
 from fp64_channels import _groups, fold_extra
-from grad_ladder import ChannelsFloat64, assert_exits_stay_rare, hold_to_reference, new_tally
-from test_gpu_batch_fuzz import _backward, _same_bits
-from test_gpu_channels_fp64 import _args, _err, _ref_decomposition, _t
-from test_gpu_fuzz import MAX_CASE_FRACTION, MAX_CASE_FRACTION_REF_TOO, MAX_ROW_FRACTION, MAX_ROW_FRACTION_REF_TOO
+from fp64_pins import ref_decomposition as _ref_decomposition, rel_err as _err
+from grad_ladder import (MAX_CASE_FRACTION, MAX_CASE_FRACTION_REF_TOO, MAX_ROW_FRACTION, MAX_ROW_FRACTION_REF_TOO, ChannelsFloat64,
+                         assert_exits_stay_rare, hold_to_reference, new_tally)
+from native_calls import channels_backward_args, moments, scene_args as _args, to_device as _t
+from sweep_support import records_backward as _backward, same_bits as _same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -66,14 +67,11 @@ STATS = dict(cases=0, views=0, view_counts=set(), retry_eligible=0, partial_retr
 def _channels_backward(N, args, run, extra, dpix_t, dx_t):
     """one channels backward on the arenas of `run`: the eight gradients, dL_dextra_values (numpy; the split layout: a pair) and the
     per-view records [V, P, 16]"""
-    counts, color, radii, geom, binning, img = run[:6]
-    g = N.rasterize_gaussians_backward_channels_batch(args[0], args[1], radii, args[2], args[4], args[5], args[6], args[7], args[8],
-                                                      args[9], args[10], args[11], dpix_t, args[14], args[15], args[16], geom, binning,
-                                                      img, False, extra, dx_t)
+    g = N.rasterize_gaussians_backward_channels_batch(*channels_backward_args(args, run, dpix_t, extra, dx_t))
     gp = {n: t.detach().cpu().numpy() for n, t in zip(NAMES, g[:8])}
     gx = tuple(a.cpu().numpy() for a in g[8]) if isinstance(g[8], tuple) else g[8].cpu().numpy()
     P, V = args[1].shape[0], dpix_t.shape[0]
-    rec = np.stack([N.grad_records(geom, P, view=v, n_views=V).cpu().numpy() for v in range(V)])
+    rec = np.stack([N.grad_records(run[3], P, view=v, n_views=V).cpu().numpy() for v in range(V)])
     return gp, gx, rec
 
 
@@ -185,8 +183,7 @@ def test_random_channels_batch_matches_reference_build(i, gpu_device):
 
     # ---- the moments modes 0 and 1
     if i % 4 == 0:
-        was = N.lib.gsr_set_backward_moments(-1)
-        try:
+        with moments(None):
             for mode in (0, 1):
                 assert N.lib.gsr_set_backward_moments(mode) == mode
                 gpm, gxm, recm = _channels_backward(N, args, run, extra, dpix_t, dx_t)
@@ -194,8 +191,6 @@ def test_random_channels_batch_matches_reference_build(i, gpu_device):
                 hold_to_reference("%s moments mode %d" % (tag, mode), 4242 + i, gpm, gr, f64, TALLY, label="channel fuzz")
                 _check_extra_grads("%s moments mode %d" % (tag, mode), gxm, want, layout, exp["empty"])
                 _check_records("%s moments mode %d" % (tag, mode), recm, want, None, exp["empty"])
-        finally:
-            N.lib.gsr_set_backward_moments(was)
 
     # ---- partial retry: some views overflow the arena (and the extra-state block carved from its capacity), others do not
     live = sorted(p for p in pairs if p > 0)

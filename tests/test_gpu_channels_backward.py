@@ -11,34 +11,13 @@ import pytest
 import torch
 
 import util
+from fp64_pins import CHECKED, check_channels_grads as _check
+from native_calls import (channels_backward as _channels_bwd, channels_backward_args, circle_scene as _scene, cloud_args as _args,
+                          colour_backward as _colour_bwd, longest_list as _long_lists, recolor_args, to_device as _t)
 
 pytestmark = pytest.mark.gpu
 
-NAMES = ("dL_dmean2D", "dL_dcolor", "dL_dopacity", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot")
-CHECKED = ("dL_dmean2D", "dL_dopacity", "dL_dmean3D", "dL_dscale", "dL_drot", "dL_dsh", "dL_dcolor")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _scene(n_views, P=12000, W=208, H=176, bg=(0.0, 0.0, 0.0)):
-    from pcrender import camera, synth
-    cloud = synth.make_cloud("synth-THuman-256", seed=0, P=P)
-    g = synth.make_gaussians(cloud, profile="training", seed=1)
-    views = camera.circle_views(12, fov_deg=45.0, width_px=W, height_px=H)
-    pick = list(range(12)) if n_views == 12 else [0, 1, 5, 7, 10][:n_views]
-    return g, [views[i] for i in pick], W, H
-
-
-def _args(g, views, W, H, dev, bg):
-    e = torch.empty(0)
-    vm = torch.stack([v["viewmatrix"] for v in views]).to(dev)
-    pm = torch.stack([v["projmatrix"] for v in views]).to(dev)
-    cp = torch.stack([v["campos"] for v in views]).to(dev)
-    return [_t(np.asarray(bg, np.float32), dev), _t(g["means3D"], dev), e, _t(g["opacities"], dev), _t(g["scales"], dev),
-            _t(g["rotations"], dev), 1.0, e, vm, pm, views[0]["tanfovx"], views[0]["tanfovy"], H, W, _t(g["shs"], dev),
-            g["sh_degree"], cp, False, False]
+NAMES = util.GRAD_NAMES
 
 
 def _extra_inputs(P, V, nx, layout, dev, seed):
@@ -58,14 +37,6 @@ def _extra_inputs(P, V, nx, layout, dev, seed):
         x = (lo, hi)
         dense = torch.cat([lo.unsqueeze(0).expand(V, P, 4), hi], 2)
     return x, scale, bgx, dense
-
-
-def _colour_bwd(N, args, dL, need_grads=True):
-    """forward + backward of plain colour calls; returns the numpy gradient dict"""
-    counts, color, radii, geom, binning, img = N.rasterize_gaussians_batch(*args, need_backward=True)
-    g = N.rasterize_gaussians_backward_batch(args[0], args[1], radii, args[2], args[4], args[5], 1.0, args[7], args[8], args[9],
-                                             args[10], args[11], dL, args[14], args[15], args[16], geom, binning, img, False)
-    return {n: x.detach().cpu().numpy().astype(np.float64) for n, x in zip(NAMES, g)}
 
 
 def _decomposition(N, args, V, P, nx, dense, scale, bgx, dpix, dx):
@@ -101,31 +72,6 @@ def _fold(gx, layout, V, P):
         return gx
     return np.concatenate([gx[:, :, :4].sum(0).reshape(-1), gx[:, :, 4:].reshape(-1)])
 
-
-def _channels_bwd(N, args, x, scale, bgx, dpix, dx, capacity=None):
-    counts, color, radii, geom, binning, img, out_x = N.rasterize_gaussians_batch(*args, need_backward=True, extra=(x, scale, bgx),
-                                                                                 capacity=capacity)
-    g = N.rasterize_gaussians_backward_channels_batch(args[0], args[1], radii, args[2], args[4], args[5], 1.0, args[7], args[8],
-                                                      args[9], args[10], args[11], dpix, args[14], args[15], args[16], geom, binning,
-                                                      img, False, (x, scale, bgx), dx)
-    gp = {n: t.detach().cpu().numpy() for n, t in zip(NAMES, g[:8])}
-    gx = g[8]
-    gx = torch.cat([gx[0].reshape(-1), gx[1].reshape(-1)]) if isinstance(gx, tuple) else gx
-    return gp, gx.cpu().numpy(), (counts, color, radii, out_x, geom, binning, img)
-
-
-def _check(gp, go, gx, gxo, tag):
-    util.check_grads({n: gp[n] for n in CHECKED}, {n: go[n] for n in CHECKED}, tag, names=CHECKED)
-    util.check_grads({"dL_dextra": gx.reshape(-1, 1)}, {"dL_dextra": gxo.reshape(-1, 1)}, tag, names=("dL_dextra",))
-
-
-def _long_lists(N, geom, binning, img, counts, P, W, H, V):
-    """the longest tile list of the batch (entries): > 1024 means the slices start at recorded chunk boundaries"""
-    best = 0
-    for v in range(V):
-        r = N.query("RANGES", P, W, H, counts[v], geom, binning, img, view=v, n_views=V).reshape(-1, 2).long()
-        best = max(best, int((r[:, 1] - r[:, 0]).max()))
-    return best
 
 
 @pytest.mark.parametrize("nx,layout,V", [(4, 0, 1), (4, 1, 2), (8, 0, 2), (8, 1, 1), (8, 2, 2), (8, 2, 12), (4, 0, 12)])
@@ -248,10 +194,8 @@ def test_misuse_is_refused_with_a_message(gpu_device):
     dx = torch.zeros((V, nx, H, W), device=dev)
 
     def bwd(r, extra, state=None):
-        return N.rasterize_gaussians_backward_channels_batch(args[0], args[1], r[2], args[2], args[4], args[5], 1.0, args[7], args[8],
-                                                             args[9], args[10], args[11], dpix, args[14], args[15], args[16], r[3],
-                                                             r[4], r[5], False, extra, dx[:, :extra[0].shape[-1]] if not
-                                                             isinstance(extra[0], tuple) else dx, state=state)
+        dxe = dx[:, :extra[0].shape[-1]] if not isinstance(extra[0], tuple) else dx
+        return N.rasterize_gaussians_backward_channels_batch(*channels_backward_args(args, r, dpix, extra, dxe, 1.0), state=state)
 
     r = N.rasterize_gaussians_batch(*args, need_backward=True, extra=(x, scale, bgx))
     st = N.extra_state(r[3])
@@ -272,7 +216,7 @@ def test_misuse_is_refused_with_a_message(gpu_device):
         bwd(r0, (x, scale, bgx), state=st)
     # after a recolor
     r = N.rasterize_gaussians_batch(*args, need_backward=True, extra=(x, scale, bgx))
-    N.recolor(args[0], args[1], torch.ones_like(args[1]), torch.empty(0), 0, args[16], H, W, r[0], r[3], r[4], r[5])
+    N.recolor(*recolor_args(args, r, torch.ones_like(args[1])))
     with pytest.raises(RuntimeError, match="recolor is not supported"):
         bwd(r, (x, scale, bgx))
 

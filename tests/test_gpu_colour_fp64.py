@@ -13,104 +13,17 @@ import pytest
 import torch
 
 import util
-from fp64_channels import channels_backward_fp64_scenes, with_colours
-import test_gpu_channels_backward as CB
-from test_gpu_channels_fp64 import _args, _deep_stack, _err, _flip, _synth, _t
+from fp64_channels import with_colours
+from fp64_pins import (MATRIX_SCENES, colour_fp64 as _fp64, colour_pin as _pin, colour_records_backward as _backward,
+                       deep_stack_cloud as _deep_stack, flipped_view as _flip, ill_conditioned as _ill_conditioned, raw_forward as _raw_forward,
+                       recolor as _recolor, recolor_setup as _recolor_setup, reference_sums as _ref, rel_err as _err, scenes_dpix as _dpix,
+                       synth_scenes as _synth, well_conditioned as _well_conditioned)
+from native_calls import circle_scene as _scene, longest_list as _long_lists, moments, scene_args as _args, to_device as _t
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 MODES = (0, 1, 2)
-MATRIX_SCENES = ["random_aniso", "culled_mix", "opaque_early_stop", "deep_stack", "big_splats", "one_gaussian", "all_culled"]
-CHAIN = ("dL_dmean3D", "dL_dscale", "dL_drot")
-NAMES = ("dL_dmean2D", "dL_dcolor", "dL_dopacity", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot")
-
-
-def _fp64(oracle, scenes, dpix):
-    """the float64 colour backward of views `scenes` (one oracle Scene per view): per-view records and the summed chain"""
-    V, P = len(scenes), scenes[0].P
-    H, W = scenes[0].H, scenes[0].W
-    return channels_backward_fp64_scenes(oracle, scenes, np.zeros((V, P, 0), F), None, np.zeros(0, F), dpix,
-                                         np.zeros((V, 0, H, W), F))
-
-
-def _ref(ref, scenes, dpix):
-    """the same sums made of the reference build's float32 per-view backwards: per view (mean2D, conic), summed chain"""
-    views, tot = [], {}
-    for v, s in enumerate(scenes):
-        _, g = ref.forward_backward(s, dpix[v])
-        views.append(dict(mean2D=g["dL_dmean2D"][:, :2].astype(np.float64), conic=g["dL_dconic"][:, [0, 1, 3]].astype(np.float64)))
-        for k in ("dL_dmean3D", "dL_dscale", "dL_drot", "dL_dcov3D"):
-            tot[k] = tot.get(k, 0.0) + g[k].astype(np.float64)
-    return views, tot
-
-
-def _backward(N, args, dpix, dev, run=None):
-    """colour forward (need_backward) + gsr_backward_batch: (per-Gaussian grads, records [V][P,16] float64, run tuple)"""
-    if run is None:
-        run = N.rasterize_gaussians_batch(*args, need_backward=True)
-    counts, color, radii, geom, binning, img = run[:6]
-    g = N.rasterize_gaussians_backward_batch(args[0], args[1], radii, args[2], args[4], args[5], args[6], args[7], args[8], args[9],
-                                             args[10], args[11], _t(dpix, dev), args[14], args[15], args[16], geom, binning, img, False)
-    P, V = args[1].shape[0], dpix.shape[0]
-    gp = {n: t.detach().cpu().numpy() for n, t in zip(NAMES, g)}
-    rec = [N.grad_records(geom, P, view=v, n_views=V).cpu().numpy().astype(np.float64) if P else np.zeros((0, 16)) for v in range(V)]
-    return gp, rec, run
-
-
-def _well_conditioned(gp, rec, want, scenes, tag):
-    """per-view colour / opacity records, dL_dcolor, dL_dopacity, dL_dsh, dL_dcov3D (precomputed covariance) against float64"""
-    for v, (w, r) in enumerate(zip(want["views"], rec)):
-        assert np.isfinite(r).all(), (tag, v)
-        util.check_grads({"opacity": r[:, 8:9], "colour": r[:, 5:8]}, {"opacity": w["opacity"][:, None], "colour": w["colour"]},
-                         "%s view %d" % (tag, v), names=("opacity", "colour"))
-    gw = want["grads"]
-    names = ["dL_dopacity", "dL_dcolor"] + (["dL_dsh"] if scenes[0].shs is not None else []) + \
-        (["dL_dcov3D"] if scenes[0].cov3D_precomp is not None else [])
-    exp = {"dL_dopacity": gw["dL_dopacity"], "dL_dcolor": gw["dL_dcolor"]}
-    if "dL_dsh" in names:
-        exp["dL_dsh"] = gw["dL_dsh"]
-    if "dL_dcov3D" in names:
-        exp["dL_dcov3D"] = gw["dL_dcov3D"]
-    util.check_grads(gp, exp, tag, names=tuple(names))
-
-
-def _ill_conditioned(gp, rec, want, rv, rt, scenes):
-    """(library error, reference build error) against float64 of mean2D, conic (per view, worst) and the chain (worst leaf)"""
-    chain = CHAIN if scenes[0].scales is not None and scenes[0].cov3D_precomp is None else ("dL_dmean3D", "dL_dcov3D")
-    lib = dict(mean2D=max(_err(r[:, 0:2], w["mean2D"]) for r, w in zip(rec, want["views"])),
-               conic=max(_err(r[:, 2:5], w["conic"]) for r, w in zip(rec, want["views"])),
-               chain=max(_err(gp[k], want["grads"][k]) for k in chain))
-    ref = dict(mean2D=max(_err(r["mean2D"], w["mean2D"]) for r, w in zip(rv, want["views"])),
-               conic=max(_err(r["conic"], w["conic"]) for r, w in zip(rv, want["views"])),
-               chain=max(_err(rt[k], want["grads"][k]) for k in chain))
-    return lib, ref
-
-
-def _pin(N, oracle, ref, scenes, dpix, dev, tag, run=None, args=None, cache=None):
-    """one colour backward against float64: well-conditioned outputs by check_grads; returns the ill-conditioned errors
-    (None when nothing was drawn: then every record must be exactly zero).  cache: a dict that keeps the references of these
-    scenes for further calls"""
-    gp, rec, run = _backward(N, _args(scenes, dev) if args is None else args, dpix, dev, run=run)
-    cache = {} if cache is None else cache
-    if "want" not in cache:
-        cache["want"] = _fp64(oracle, scenes, dpix)
-    want = cache["want"]
-    _well_conditioned(gp, rec, want, scenes, tag)
-    if all(np.abs(w["conic"]).max(initial=0.0) == 0 for w in want["views"]):
-        assert not any(r.any() for r in rec), tag
-        return None, run
-    if "ref" not in cache:
-        cache["ref"] = _ref(ref, scenes, dpix)
-    rv, rt = cache["ref"]
-    return _ill_conditioned(gp, rec, want, rv, rt, scenes), run
-
-
-def _dpix(scenes, seed):
-    s = scenes[0]
-    return np.random.default_rng(seed).uniform(-1, 1, (len(scenes), 3, s.H, s.W)).astype(F)
-
-
 # caps on the median error against float64 in units of the reference build's, per (moments mode, V), with a margin of 1.4x or more
 # over the ratios observed on an MI355X in two runs (mean2D / conic / chain; float atomics make them vary from run to run).
 # V = 1: mode 0 2.10-2.25x / 2.11-2.30x / 4.22-5.46x, mode 1 1.42-1.52x / 1.18-1.29x / 1.40x, mode 2 1.46-1.56x / 1.17-1.18x / 1.39-1.40x.
@@ -129,8 +42,7 @@ def test_moments_modes_against_float64(oracle, gpu_device):
     g, views, W, H, batch = _synth(3, P=12000, W=96, H=80)
     cases = [(name, [util.build_scene(name)]) for name in MATRIX_SCENES] + [("synth view 0", batch[:1]), ("synth V=3", batch)]
     err = {(m, v): {k: [] for k in ("mean2D", "conic", "chain")} for m in MODES + ("ref",) for v in (1, 3)}
-    was = N.lib.gsr_set_backward_moments(-1)
-    try:
+    with moments(None):
         for name, scenes in cases:
             dpix = _dpix(scenes, 7 + len(name))
             V = len(scenes)
@@ -150,8 +62,6 @@ def test_moments_modes_against_float64(oracle, gpu_device):
                     err[(mode, V)][k].append(lib[k])
                     if mode == MODES[0]:
                         err[("ref", V)][k].append(r[k])
-    finally:
-        N.lib.gsr_set_backward_moments(was)
     med = {key: {k: float(np.median(a)) for k, a in e.items()} for key, e in err.items()}
     for V in (1, 3):
         for m in MODES:
@@ -228,14 +138,14 @@ def test_capped_last_slice(oracle, gpu_device, V, P):
         assert e2 <= 1e-5 and ec <= 1e-5, (V, v, e2, ec)
     shift = 9 if V == 1 else 10
     counts, _, _, geom, binning, img = run
-    assert CB._long_lists(N, geom, binning, img, counts, P, W, H, V) > 32 << shift, "the list no longer reaches the capped last slice"
+    assert _long_lists(N, geom, binning, img, counts, P, W, H, V) > 32 << shift, "the list no longer reaches the capped last slice"
 
 
 def test_empty_middle_view(oracle, gpu_device):
     """V = 3 whose middle camera faces away: its records are exactly zero, the gradients come from the other two views"""
     from diff_gaussian_rasterization import _native as N
     dev = gpu_device
-    g, views, W, H = CB._scene(3, P=12000, W=96, H=80)
+    g, views, W, H = _scene(3, P=12000, W=96, H=80)
     views = [views[0], _flip(views[1]), views[2]]
     scenes = [util.scene_from(g, v, W, H, bg=(0.1, 0.2, 0.3)) for v in views]
     dpix = _dpix(scenes, 12)
@@ -256,7 +166,7 @@ def test_empty_middle_view(oracle, gpu_device):
 def test_twelve_views(oracle, gpu_device):
     """the benchmark's view count on a small image: per-view strides of every arena at V = 12"""
     from diff_gaussian_rasterization import _native as N
-    g, views, W, H = CB._scene(12, P=6000, W=64, H=48)
+    g, views, W, H = _scene(12, P=6000, W=64, H=48)
     scenes = [util.scene_from(g, v, W, H, bg=(0.3, 0.3, 0.3)) for v in views]
     e, _ = _pin(N, oracle, util.reference_build(), scenes, _dpix(scenes, 13), gpu_device, "V=12")
     lib, r = e
@@ -266,7 +176,7 @@ def test_twelve_views(oracle, gpu_device):
 def test_precomputed_covariance_and_colours(oracle, gpu_device):
     """V = 2 with cov3D_precomp and colors_precomp: dL_dcov3D and dL_dcolor are outputs of their own"""
     from diff_gaussian_rasterization import _native as N
-    g, views, W, H = CB._scene(2, P=8000, W=96, H=80)
+    g, views, W, H = _scene(2, P=8000, W=96, H=80)
     g = dict(g)
     g["colors_precomp"] = np.random.default_rng(4).uniform(0, 1, (g["means3D"].shape[0], 3)).astype(F)
     scenes = [util.scene_from(g, v, W, H, bg=(0.5, 0.2, 0.1), mode="colors", use_cov3d=True) for v in views]
@@ -276,15 +186,6 @@ def test_precomputed_covariance_and_colours(oracle, gpu_device):
 
 
 # ------------------------------------------------------------------------------------------------ backward after a recolor
-def _recolor(N, args, run, colours=None, campos=None):
-    counts, color, radii, geom, binning, img = run[:6]
-    e = torch.empty(0)
-    H, W = args[12], args[13]
-    if colours is not None:
-        return N.recolor(args[0], args[1], colours, e, 0, args[16], H, W, counts, geom, binning, img, need_backward=True)
-    return N.recolor(args[0], args[1], e, args[14], args[15], campos, H, W, counts, geom, binning, img, need_backward=True)
-
-
 def _moved(s, campos):
     """the Scene s seen from the same camera, its SH evaluated from another camera position"""
     return util.Scene(W=s.W, H=s.H, tanfovx=s.tanfovx, tanfovy=s.tanfovy, bg=s.bg, means3D=s.means3D, opacities=s.opacities,
@@ -299,15 +200,6 @@ def _pin_recolor(N, oracle, scenes, args, run, dpix, dev, tag):
     rv, rt = _ref(util.reference_build(), scenes, dpix)
     lib, r = _ill_conditioned(gp, rec, want, rv, rt, scenes)
     assert lib["chain"] <= 6.0 * r["chain"] and lib["mean2D"] <= 4.0 * max(r["mean2D"], 1e-6), (tag, lib, r)
-
-
-def _recolor_setup(dev, V=2):
-    g, views, W, H = CB._scene(V, P=8000, W=96, H=80)
-    g = dict(g)
-    rng = np.random.default_rng(21)
-    g["shs"] = (0.6 * rng.standard_normal(g["shs"].shape)).astype(F)      # view-dependent enough to change the clamp mask
-    scenes = [util.scene_from(g, v, W, H, bg=(0.2, 0.2, 0.6)) for v in views]
-    return g, scenes, _args(scenes, dev)
 
 
 @pytest.mark.parametrize("kind", ["sh_other_campos", "colours_shared", "colours_per_view", "twice"])
@@ -365,21 +257,6 @@ def test_colour_backward_after_channels_forward(oracle, gpu_device):
 
 
 # ------------------------------------------------------------------------------------------------ refused backwards
-def _raw_forward(N, args, run, need_backward):
-    """gsr_forward_batch with the given need_backward on the (full-size) arenas of `run`"""
-    import ctypes as C
-    counts, color, radii, geom, binning, img = run[:6]
-    V = len(counts)
-    p, keep = N._params(*args, need_backward=need_backward)
-    cnt = (C.c_int64 * V)()
-    with torch.cuda.device(args[1].device):
-        rc = N.lib.gsr_forward_batch(C.byref(p), V, geom.data_ptr(), geom.numel(), img.data_ptr(), img.numel(), binning.data_ptr(),
-                                     binning.numel(), radii.data_ptr(), color.data_ptr(), cnt, 0,
-                                     torch.cuda.current_stream(args[1].device).cuda_stream)
-    torch.cuda.synchronize()
-    assert rc == 0, N.lib.gsr_last_error()
-
-
 def test_unsupported_colour_backwards_are_refused(gpu_device):
     from diff_gaussian_rasterization import _native as N
     dev = gpu_device

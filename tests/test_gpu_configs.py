@@ -18,21 +18,15 @@ import pytest
 import torch
 
 import util
-from util import build_scene, check_grads, run_product
+from native_calls import to_device as _t
+from sweep_support import fd_single_gaussians
+from util import build_scene, check_grads, run_product, strict_reference as _ref
 
 pytestmark = pytest.mark.gpu
 
 RGB_TOL = 1e-4
 MAX_FLIP_FRACTION = 2e-3
 NTHREADS = os.cpu_count() or 1
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _ref():
-    return util.reference_build("strict")
 
 
 def _image_close(got, want, tag):
@@ -306,46 +300,6 @@ def test_textured_mesh_sampled_cloud_vs_oracle(oracle, gpu_device, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ finite differences
-def _fd_single_gaussians(s, dev, g, dL, field, grad_key, rel_eps, K, rng, tag, in_plane=False):
-    """Central differences of loss = sum(image * dL) of the HIP forward, perturbing ONE Gaussian at a time along a random
-    direction in ONE input tensor, against the analytic directional derivative of that Gaussian.  Returns (slope of the
-    least-squares line FD = slope * analytic, Pearson correlation) over K Gaussians.  in_plane: position steps keep the
-    view-space depth (steps in depth reorder overlapping splats, a jump no gradient describes)."""
-    from oracle.oracle import Scene
-    base = getattr(s, field)
-    gk = g[grad_key].astype(np.float64).reshape(base.shape)
-    strength = np.linalg.norm(gk, axis=1)
-    cand = np.nonzero(strength > np.quantile(strength[strength > 0], 0.5))[0]   # Gaussians that matter to this loss
-    pick = rng.choice(cand, size=min(K, cand.size), replace=False)
-    fd, an = [], []
-    r2 = np.array([s.viewmatrix[2], s.viewmatrix[6], s.viewmatrix[10]], np.float64)   # view direction (row 2 of the rotation)
-    for k in pick:
-        d = rng.standard_normal(base.shape[1])
-        if field == "means3D" and in_plane:
-            d -= r2 * (d @ r2) / (r2 @ r2)
-        d /= np.linalg.norm(d)
-        step = rel_eps * (np.abs(s.scales[k]).mean() if field != "rotations" else 1.0)
-        vals = []
-        thetas = []
-        for sign in (+1, -1):
-            arr = base.copy()
-            arr[k] = (base[k].astype(np.float64) + sign * step * d).astype(np.float32)
-            kw = dict(means3D=s.means3D, opacities=s.opacities, scales=s.scales, rotations=s.rotations)
-            kw[field] = arr
-            s2 = Scene(W=s.W, H=s.H, tanfovx=s.tanfovx, tanfovy=s.tanfovy, bg=s.bg, viewmatrix=s.viewmatrix,
-                       projmatrix=s.projmatrix, campos=s.campos, shs=s.shs, sh_degree=s.sh_degree, **kw)
-            img = run_product(s2, dev, light=True)[0]["out_color"].astype(np.float64)
-            vals.append(float((img * dL).sum()))
-            thetas.append(arr[k].astype(np.float64))
-        fd.append(vals[0] - vals[1])
-        an.append(float(gk[k] @ (thetas[0] - thetas[1])))       # the float32 values actually rendered define the step
-    fd, an = np.asarray(fd), np.asarray(an)
-    slope = float((fd * an).sum() / (an * an).sum())
-    corr = float(np.corrcoef(fd, an)[0, 1])
-    print("%s %s: %d Gaussians, FD = %.4f x analytic, correlation %.5f" % (tag, field, fd.size, slope, corr))
-    return slope, corr
-
-
 def test_gradient_matches_finite_difference_on_isolated_gaussians(gpu_device):
     """48 well separated splats (no overlap, so no depth-order effects): position in all three directions, scale, rotation."""
     W, H = 512, 384
@@ -370,7 +324,7 @@ def test_gradient_matches_finite_difference_on_isolated_gaussians(gpu_device):
     assert p["visible"] == P and int(p["tiles_touched"].max()) <= 16      # compact, on screen
     frng = np.random.default_rng(78)
     for field, key, rel_eps in (("means3D", "dL_dmean3D", 0.02), ("scales", "dL_dscale", 0.02), ("rotations", "dL_drot", 0.01)):
-        slope, corr = _fd_single_gaussians(s, gpu_device, gr, dL, field, key, rel_eps, P, frng, "isolated")
+        slope, corr = fd_single_gaussians(s, gpu_device, gr, dL, field, key, rel_eps, P, frng, "isolated")
         assert abs(slope - 1.0) <= 0.03 and corr >= 0.99, (field, slope, corr)
 
 
@@ -397,7 +351,7 @@ def test_gradient_matches_finite_difference_in_dense_scenes(which, gpu_device):
     # steps of 0.2 sigma: the jump terms scale with sqrt(step), the smooth part with the step (scripts/diag_fd.py: the
     # correlation falls from 0.99 to 0.9 between steps of 0.2 and 0.003 sigma while the slope stays at 1 within noise)
     for field, key, rel_eps in (("means3D", "dL_dmean3D", 0.2), ("scales", "dL_dscale", 0.2), ("rotations", "dL_drot", 0.05)):
-        slope, corr = _fd_single_gaussians(s, gpu_device, g, dL, field, key, rel_eps, K, rng, which, in_plane=True)
+        slope, corr = fd_single_gaussians(s, gpu_device, g, dL, field, key, rel_eps, K, rng, which, in_plane=True)
         # (the full-size scene regresses over 96 splats of very unequal weight: a looser slope bar, still far from the
         # factor-of-two errors a wrong term would cause)
         small = which == "capsule_circle"

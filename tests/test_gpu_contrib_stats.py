@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import contrib_ref as R
-from camera_sweep import _args, _t
+from native_calls import colour_backward_args, contrib_stats_args, scene_args as _args, scene_settings as _settings, to_device as _t
 
 pytestmark = pytest.mark.gpu
 
@@ -36,9 +36,8 @@ def _contrib(N, args, run, weights=None, old=None, want=NAMES, V=None, out=None,
     V = args[8].shape[0] if V is None else V
     out = _prefilled(args[1].shape[0], dev, old) if out is None else out
     o = {n: (t if n in want else None) for n, t in zip(NAMES, out)}
-    N.contrib_stats(args[0], args[1], run[2][:V] if radii else None, args[2], args[4], args[5], args[6], args[7], args[8][:V],
-                    args[9][:V], args[10], args[11], args[12], args[13], args[14], args[15], args[16][:V], run[3], run[4], run[5],
-                    accumulate=old is not None, pixel_weights=None if weights is None else _t(weights, dev), **o)
+    N.contrib_stats(*contrib_stats_args(args, run, V, radii), accumulate=old is not None,
+                    pixel_weights=None if weights is None else _t(weights, dev), **o)
     return {n: t.cpu().numpy() for n, t in o.items() if t is not None}
 
 
@@ -165,9 +164,7 @@ def test_random_scene_with_every_input_form(gpu_device, mode):
 
 
 def _det_backward(N, args, run, dpix):
-    return N.rasterize_gaussians_backward_batch(args[0], args[1], run[2], args[2], args[4], args[5], args[6], args[7], args[8], args[9],
-                                                args[10], args[11], dpix, args[14], args[15], args[16], run[3], run[4], run[5], False,
-                                                deterministic=True)
+    return N.rasterize_gaussians_backward_batch(*colour_backward_args(args, run, dpix), deterministic=True)
 
 
 def test_the_arenas_are_untouched(gpu_device):
@@ -235,14 +232,6 @@ def test_a_mismatching_call_is_refused_with_the_outputs_untouched(gpu_device):
     with pytest.raises(RuntimeError, match="all four outputs are NULL"):
         _contrib(N, args, run, want=())
     R.check(_contrib(N, args, run), c["ref"], "the matching call")
-
-
-def _settings(scs, dev):
-    from diff_gaussian_rasterization import GaussianRasterizationSettings
-    return [GaussianRasterizationSettings(
-        image_height=s.H, image_width=s.W, tanfovx=s.tanfovx, tanfovy=s.tanfovy, bg=_t(s.bg, dev), scale_modifier=1.0,
-        viewmatrix=_t(s.viewmatrix.reshape(4, 4), dev), projmatrix=_t(s.projmatrix.reshape(4, 4), dev), sh_degree=s.sh_degree,
-        campos=_t(s.campos, dev), prefiltered=False, debug=False) for s in scs]
 
 
 def test_rasterize_views_contrib(gpu_device):

@@ -9,17 +9,13 @@ import numpy as np
 import pytest
 
 import util
-from util import run_product
+from util import run_product, strict_reference as _ref
 
 pytestmark = pytest.mark.gpu
 
 TILES_X, TILES_Y = 42, 38          # one splat per interior tile
 W, H = TILES_X * 16, TILES_Y * 16
 Z0 = 2.0
-
-
-def _ref():
-    return util.reference_build("strict")
 
 
 def _targets():

@@ -18,35 +18,18 @@ if __name__ == "__main__":
         sys.path.insert(0, _p)
 
 import util  # noqa: E402
-import test_gpu_channels_backward as CB  # noqa: E402
-from test_gpu_channels_fp64 import _args, _deep_stack, _err, _flip, _settings, _synth, _t  # noqa: E402
+from fp64_pins import (colour_fp64 as _fp64, deep_stack_cloud as _deep_stack, flipped_view as _flip,  # noqa: E402
+                       raw_forward as _raw_forward, rel_err as _err, synth_scenes as _synth, view_settings as _settings)
+from native_calls import (circle_scene as _scene, cloud_args as _cloud_args, longest_list as _long_lists, moments,  # noqa: E402
+                          scene_args as _args, to_device as _t)
+from sweep_support import (leaves as _leaves, nine_tensors_backward as _backward, power_scene, same_bits as _same,  # noqa: E402
+                           uniform_dpix as _dpix)
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-NAMES = ("dL_dmean2D", "dL_dcolor", "dL_dopacity", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot")
+NAMES = util.GRAD_NAMES
 GOLDEN = sorted(f[4:-4] for f in os.listdir(os.path.join(ROOT, "tests", "golden")) if f.startswith("ref_") and f.endswith(".npz"))
-
-
-def _dpix(V, H, W, seed):
-    return np.random.default_rng(seed).uniform(-1, 1, (V, 3, H, W)).astype(F)
-
-
-def _backward(N, args, run, dpix, det, dev):
-    """one colour backward on the arenas of `run`: the eight per-Gaussian gradients and the per-view records (which hold dL_dconic),
-    as numpy arrays: nine tensors"""
-    counts, color, radii, geom, binning, img = run[:6]
-    g = N.rasterize_gaussians_backward_batch(args[0], args[1], radii, args[2], args[4], args[5], args[6], args[7], args[8], args[9],
-                                             args[10], args[11], _t(dpix, dev), args[14], args[15], args[16], geom, binning, img, False,
-                                             deterministic=det)
-    out = {n: t.detach().cpu().numpy() for n, t in zip(NAMES, g)}
-    P, V = args[1].shape[0], dpix.shape[0]
-    out["records"] = np.stack([N.grad_records(geom, P, view=v, n_views=V).cpu().numpy() for v in range(V)])
-    return out
-
-
-def _same(a, b):
-    return all(np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)) for k in a)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the cases
@@ -61,8 +44,8 @@ def _case_golden(name):
 
 def _case_views(V, P, W, H, mode=None, seed=4):
     def build(N, dev):
-        g, views, W_, H_ = CB._scene(V, P=P, W=W, H=H)
-        args = CB._args(g, views, W, H, dev, (0.1, 0.2, 0.3))
+        g, views, W_, H_ = _scene(V, P=P, W=W, H=H)
+        args = _cloud_args(g, views, W, H, dev, (0.1, 0.2, 0.3))
         return args, N.rasterize_gaussians_batch(*args, need_backward=True), _dpix(V, H, W, seed), mode
     return build
 
@@ -76,13 +59,13 @@ def _case_deep(V, P):
         run = N.rasterize_gaussians_batch(*args, need_backward=True)
         counts, _, _, geom, binning, img = run
         # the list reaches the capped last slice (512-entry slices at V = 1, 1024 from V = 2 on)
-        assert CB._long_lists(N, geom, binning, img, counts, P, W, H, V) > 32 << (9 if V == 1 else 10)
+        assert _long_lists(N, geom, binning, img, counts, P, W, H, V) > 32 << (9 if V == 1 else 10)
         return args, run, _dpix(V, H, W, 60 + V), None
     return build
 
 
 def _case_empty_middle(N, dev):
-    g, views, W, H = CB._scene(3, P=12000, W=96, H=80)
+    g, views, W, H = _scene(3, P=12000, W=96, H=80)
     views = [views[0], _flip(views[1]), views[2]]
     scenes = [util.scene_from(g, v, W, H, bg=(0.1, 0.2, 0.3)) for v in views]
     args = _args(scenes, dev)
@@ -92,7 +75,7 @@ def _case_empty_middle(N, dev):
 
 
 def _case_precomp(N, dev):
-    g, views, W, H = CB._scene(2, P=8000, W=96, H=80)
+    g, views, W, H = _scene(2, P=8000, W=96, H=80)
     g = dict(g)
     g["colors_precomp"] = np.random.default_rng(4).uniform(0, 1, (g["means3D"].shape[0], 3)).astype(F)
     scenes = [util.scene_from(g, v, W, H, bg=(0.5, 0.2, 0.1), mode="colors", use_cov3d=True) for v in views]
@@ -101,7 +84,7 @@ def _case_precomp(N, dev):
 
 
 def _case_recolor(N, dev):
-    g, views, W, H = CB._scene(2, P=8000, W=96, H=80)
+    g, views, W, H = _scene(2, P=8000, W=96, H=80)
     scenes = [util.scene_from(g, v, W, H, bg=(0.2, 0.2, 0.6)) for v in views]
     args = list(_args(scenes, dev))
     run = N.rasterize_gaussians_batch(*args, need_backward=True)
@@ -137,14 +120,11 @@ CASES.update({
 
 def _run_case(N, dev, name, repeats):
     """one forward, `repeats` deterministic backwards over it"""
-    was = N.lib.gsr_set_backward_moments(-1)
-    try:
+    with moments(None):
         args, run, dpix, mode = CASES[name](N, dev)
         if mode is not None:
             assert N.lib.gsr_set_backward_moments(mode) == mode
         return [_backward(N, args, run, dpix, True, dev) for _ in range(repeats)]
-    finally:
-        N.lib.gsr_set_backward_moments(was)
 
 
 @pytest.fixture(scope="module")
@@ -179,17 +159,6 @@ def test_repeatable_from_call_to_call_and_from_process_to_process(gpu_device, ch
 
 
 # ------------------------------------------------------------------------------------------------------- the scene can tell
-def power_scene(P=48, W=640, H=480, seed=5):
-    """large, semi-transparent splats that cover some hundred tiles each: hundreds of work units add into one record.
-    Chosen on an MI355X: over five atomic backwards all ten pairs of runs differed, in 961 to 1026 of the 1248 gradient elements
-    (two sessions)."""
-    rng = np.random.default_rng(seed)
-    g = dict(means3D=np.stack([rng.uniform(-0.6, 0.6, P), rng.uniform(-0.4, 0.4, P), rng.uniform(2.0, 4.0, P)], 1).astype(F),
-             scales=rng.uniform(0.25, 0.6, (P, 3)).astype(F), rotations=np.tile(np.array([1, 0, 0, 0], F), (P, 1)),
-             opacities=rng.uniform(0.05, 0.3, (P, 1)).astype(F), shs=(0.5 * rng.standard_normal((P, 1, 3))).astype(F), sh_degree=0)
-    return util.scene_from(g, util.identity_camera(W, H), W, H, bg=(0.1, 0.1, 0.1))
-
-
 def test_the_atomic_path_is_visibly_not_repeatable_on_the_power_scene(gpu_device):
     from diff_gaussian_rasterization import _native as N
     dev = gpu_device
@@ -232,7 +201,7 @@ def test_edge_scenes_pass_the_existing_bars(oracle, gpu_device, name):
 def test_one_full_size_view_passes_the_existing_bars(gpu_device):
     """one 1920 x 1080 view of the 200 K cloud: deterministic against the reference build's backward"""
     import diff_gaussian_rasterization as d
-    g, views, W, H = CB._scene(1, P=200_000, W=1920, H=1080)
+    g, views, W, H = _scene(1, P=200_000, W=1920, H=1080)
     s = util.scene_from(g, views[0], W, H, bg=(0.0, 0.0, 0.0))
     dL = util.seeded_dL(s)
     was = d.get_deterministic()
@@ -270,14 +239,12 @@ def test_error_against_float64_is_the_atomic_path_s(oracle, gpu_device):
     session.  The partial sums are shared and the final rounding is the best float32 allows: there is nothing left in the
     reduction to make more exact."""
     from diff_gaussian_rasterization import _native as N
-    from test_gpu_colour_fp64 import _fp64
     dev = gpu_device
     g, views, W, H, batch = _synth(3, P=12000, W=96, H=80)
     cases = [(n, [util.build_scene(n)]) for n in FP64_SCENES] + [("synth V=3", batch)]
     sl = dict(mean2D=slice(0, 2), conic=slice(2, 5), colour=slice(5, 8), opacity=slice(8, 9))
     errs = {m: {k: {"det": [], "atomic": [[] for _ in range(5)]} for k in METRICS} for m in (0, 1, 2)}
-    was = N.lib.gsr_set_backward_moments(-1)
-    try:
+    with moments(None):
         for name, scenes in cases:
             dpix = _dpix(len(scenes), scenes[0].H, scenes[0].W, 7 + len(name))
             want = _fp64(oracle, scenes, dpix)["views"]
@@ -296,8 +263,6 @@ def test_error_against_float64_is_the_atomic_path_s(oracle, gpu_device):
                     rec = _backward(N, args, run, dpix, False, dev)["records"]
                     for k in METRICS:
                         errs[m][k]["atomic"][r].append(err(rec, k))
-    finally:
-        N.lib.gsr_set_backward_moments(was)
     bad = []
     for m in (0, 1, 2):
         for k in METRICS:
@@ -313,9 +278,8 @@ def test_error_against_float64_is_the_atomic_path_s(oracle, gpu_device):
 # ------------------------------------------------------------------------------------------------------------------ contract
 def test_contract_of_the_c_abi(gpu_device, monkeypatch):
     from diff_gaussian_rasterization import _native as N
-    from test_gpu_colour_fp64 import _raw_forward
     dev = gpu_device
-    g, views, W, H = CB._scene(2, P=8000, W=96, H=80)
+    g, views, W, H = _scene(2, P=8000, W=96, H=80)
     scenes = [util.scene_from(g, v, W, H, bg=(0.2, 0.2, 0.6)) for v in views]
     args = _args(scenes, dev)
     P, V = scenes[0].P, 2
@@ -357,12 +321,6 @@ def test_contract_of_the_c_abi(gpu_device, monkeypatch):
 LEAVES = ("means3D", "means2D", "shs", "opacities", "scales", "rotations")
 
 
-def _leaves(g, dev):
-    L = {k: _t(g[k], dev).requires_grad_(True) for k in ("means3D", "shs", "opacities", "scales", "rotations")}
-    L["means2D"] = torch.zeros((g["means3D"].shape[0], 3), device=dev, requires_grad=True)
-    return L
-
-
 def _grads(L):
     return {k: L[k].grad.detach().clone() for k in LEAVES}
 
@@ -379,7 +337,7 @@ def forced_on():
 def test_python_rasterize_views_twelve_views(gpu_device, forced_on):
     d, dev = forced_on, gpu_device
     from diff_gaussian_rasterization import _native as N
-    g, views, W, H = CB._scene(12, P=12000, W=208, H=176)
+    g, views, W, H = _scene(12, P=12000, W=208, H=176)
     sts = _settings(views, W, H, (0.1, 0.1, 0.1), dev, g["sh_degree"])
     dpix = _t(_dpix(12, H, W, 70), dev)
     out = []
@@ -415,7 +373,7 @@ def test_python_per_view_rasterizer(gpu_device, forced_on):
     """GaussianRasterizer per view (the general path on the first frame of a configuration, then the short path)"""
     d, dev = forced_on, gpu_device
     from diff_gaussian_rasterization import _native as N
-    g, views, W, H = CB._scene(1, P=12000, W=208, H=176)
+    g, views, W, H = _scene(1, P=12000, W=208, H=176)
     st = _settings(views, W, H, (0.1, 0.1, 0.1), dev, g["sh_degree"])[0]
     dpix = _t(_dpix(1, H, W, 71)[0], dev)
     out = []
@@ -439,7 +397,7 @@ def test_python_per_view_rasterizer(gpu_device, forced_on):
 
 def test_python_channels_call_raises_when_forced_on(gpu_device, forced_on):
     d, dev = forced_on, gpu_device
-    g, views, W, H = CB._scene(2, P=2000, W=96, H=80)
+    g, views, W, H = _scene(2, P=2000, W=96, H=80)
     sts = _settings(views, W, H, (0.0, 0.0, 0.0), dev, g["sh_degree"])
     L = _leaves(g, dev)
     x = torch.zeros((2000, 4), device=dev, requires_grad=True)

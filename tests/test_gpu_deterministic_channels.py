@@ -19,14 +19,17 @@ if __name__ == "__main__":
         sys.path.insert(0, _p)
 
 import util  # noqa: E402
-import test_gpu_channels_backward as CB  # noqa: E402
 from fp64_channels import channels_backward_fp64_scenes, fold_extra  # noqa: E402
-from test_gpu_channels_fp64 import _args, _deep_stack, _err, _flat, _flip, _inputs, _settings, _synth, _t  # noqa: E402
+from fp64_pins import (channel_inputs as _inputs, deep_stack_cloud as _deep_stack, flat64 as _flat, flipped_view as _flip,  # noqa: E402
+                       rel_err as _err, synth_scenes as _synth, view_settings as _settings)
+from native_calls import (channels_backward_args, circle_scene as _scene, longest_list as _long_lists, moments,  # noqa: E402
+                          scene_args as _args, to_device as _t)
+from sweep_support import power_scene, same_bits as _same  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-NAMES = ("dL_dmean2D", "dL_dcolor", "dL_dopacity", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot")
+NAMES = util.GRAD_NAMES
 EXTRA = "dL_dextra_values"
 
 
@@ -44,19 +47,14 @@ def _backward(N, args, run, xt, sct, bgxt, dpix, dx, det, dev, **kw):
     """one channels backward on the arenas of `run`: the eight per-Gaussian gradients, the per-view records and dL_dextra_values
     (flat, in the layout of the values) as numpy arrays: ten tensors"""
     counts, color, radii, geom, binning, img = run[:6]
-    g = N.rasterize_gaussians_backward_channels_batch(args[0], args[1], radii, args[2], args[4], args[5], 1.0, args[7], args[8], args[9],
-                                                      args[10], args[11], _t(dpix, dev), args[14], args[15], args[16], geom, binning, img,
-                                                      False, (xt, sct, bgxt), _t(dx, dev), deterministic=det, **kw)
+    g = N.rasterize_gaussians_backward_channels_batch(*channels_backward_args(args, run, _t(dpix, dev), (xt, sct, bgxt), _t(dx, dev), 1.0),
+                                                      deterministic=det, **kw)
     out = {n: t.detach().cpu().numpy() for n, t in zip(NAMES, g[:8])}
     gx = g[8]
     out[EXTRA] = (torch.cat([gx[0].reshape(-1), gx[1].reshape(-1)]) if isinstance(gx, tuple) else gx.reshape(-1)).cpu().numpy()
     P, V = args[1].shape[0], dpix.shape[0]
     out["records"] = np.stack([N.grad_records(geom, P, view=v, n_views=V).cpu().numpy() for v in range(V)])
     return out
-
-
-def _same(a, b):
-    return all(np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)) for k in a)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the cases
@@ -80,7 +78,7 @@ def _case_layout(layout, nx):
 
 def _case_modes(mode):
     def build():
-        g, views, W, H = CB._scene(3, P=12000, W=208, H=176)
+        g, views, W, H = _scene(3, P=12000, W=208, H=176)
         return _pack([util.scene_from(g, v, W, H, bg=(0.1, 0.2, 0.3)) for v in views], 8, 2, seed=5, mode=mode)
     return build
 
@@ -93,13 +91,13 @@ def _case_deep(V, P):
 
         def check(N, run):   # the list reaches the capped last slice (512-entry slices at V = 1, 1024 from V = 2 on)
             counts, _, _, geom, binning, img = run[:6]
-            assert CB._long_lists(N, geom, binning, img, counts, P, W, H, V) > 32 << (9 if V == 1 else 10)
+            assert _long_lists(N, geom, binning, img, counts, P, W, H, V) > 32 << (9 if V == 1 else 10)
         return _pack(scenes, 4, 1, seed=40 + V, check=check)
     return build
 
 
 def _case_empty_middle():
-    g, views, W, H = CB._scene(3, P=12000, W=96, H=80)
+    g, views, W, H = _scene(3, P=12000, W=96, H=80)
     views = [views[0], _flip(views[1]), views[2]]
 
     def check(N, run):
@@ -112,7 +110,7 @@ def _case_no_scale():
 
 
 def _case_precomp():
-    g, views, W, H = CB._scene(2, P=8000, W=96, H=80)
+    g, views, W, H = _scene(2, P=8000, W=96, H=80)
     g = dict(g)
     g["colors_precomp"] = np.random.default_rng(4).uniform(0, 1, (g["means3D"].shape[0], 3)).astype(F)
     return _pack([util.scene_from(g, v, W, H, bg=(0.5, 0.2, 0.1), mode="colors", use_cov3d=True) for v in views], 8, 2, seed=14)
@@ -123,7 +121,7 @@ PULLED = (12, 20000, 1024, 704)
 
 def _case_pulled():
     V, P, W, H = PULLED
-    g, views, W, H = CB._scene(V, P=P, W=W, H=H)
+    g, views, W, H = _scene(V, P=P, W=W, H=H)
     return _pack([util.scene_from(g, v, W, H, bg=(0.0, 0.0, 0.0)) for v in views], 8, 2, seed=77)
 
 
@@ -139,8 +137,7 @@ CASES.update({
 
 def _run_case(N, dev, name, repeats, atomic=0):
     """one forward, `repeats` deterministic backwards over it (then `atomic` atomic ones): (case, deterministic results, atomic)"""
-    was = N.lib.gsr_set_backward_moments(-1)
-    try:
+    with moments(None):
         c = CASES[name]()
         if c["mode"] is not None:
             assert N.lib.gsr_set_backward_moments(c["mode"]) == c["mode"]
@@ -151,8 +148,6 @@ def _run_case(N, dev, name, repeats, atomic=0):
             c["check"](N, run)
         bw = lambda det: _backward(N, args, run, xt, sct, bgxt, c["dpix"], c["dx"], det, dev)  # noqa: E731
         return c, [bw(True) for _ in range(repeats)], [bw(False) for _ in range(atomic)]
-    finally:
-        N.lib.gsr_set_backward_moments(was)
 
 
 @pytest.fixture(scope="module")
@@ -228,7 +223,6 @@ def test_power_scene_with_eight_extra_channels(gpu_device):
     """Five atomic channels backwards on the colour test's power scene: how many elements of dL_dextra_values differ between pairs
     is printed, not asserted (profiles/r13_det_channels_backward.txt records it); five deterministic ones are identical."""
     from diff_gaussian_rasterization import _native as N
-    from test_gpu_deterministic_backward import power_scene
     dev = gpu_device
     s = power_scene()
     x, dense, sc, bgx, dpix, dx = _inputs(s.P, 1, 8, 0, seed=8, H=s.H, W=s.W)
@@ -320,7 +314,7 @@ def test_python_rasterize_views_channels(gpu_device, channels_on):
     d, dev = channels_on, gpu_device
     from diff_gaussian_rasterization import _native as N
     V = 2
-    g, views, W, H = CB._scene(V, P=8000, W=96, H=80)
+    g, views, W, H = _scene(V, P=8000, W=96, H=80)
     P = g["means3D"].shape[0]
     sts = _settings(views, W, H, (0.0, 0.0, 0.0), dev, g["sh_degree"])
     rng = np.random.default_rng(80)

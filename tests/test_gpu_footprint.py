@@ -14,13 +14,9 @@ import numpy as np
 import pytest
 
 import util
-from util import SCENES, build_scene, run_product, seeded_dL, check_clipped_equivalent
+from util import build_scene, check_clipped_equivalent, run_product, SCENES, seeded_dL, strict_reference as _ref
 
 pytestmark = pytest.mark.gpu
-
-
-def _ref():
-    return util.reference_build("strict")
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -71,7 +67,7 @@ N_FUZZ = int(os.environ.get("GSR_FOOTPRINT_FUZZ_CASES", "96"))   # (a 6 000-case
 
 @pytest.mark.parametrize("i", range(N_FUZZ))
 def test_random_case_clipped_vs_reference_build(i, gpu_device):
-    from test_gpu_fuzz import _case
+    from sweep_support import random_case as _case
     ref = _ref()
     s, _ = _case(i)
     r = ref.forward(s)
@@ -84,7 +80,7 @@ def test_random_case_clipped_vs_reference_build(i, gpu_device):
 
 @pytest.mark.parametrize("name", ["thuman256_1080p", "thuman800k_1080p", "mesh2m_4k"])
 def test_fullsize_clipped_bit_exact_vs_reference_build(name, gpu_device):
-    from test_gpu_fullsize import _scene, CONFIGS
+    from sweep_support import FULLSIZE_CONFIGS as CONFIGS, fullsize_scene as _scene
     ref = _ref()
     s = _scene(CONFIGS[name], voxel_exact=(name == "thuman256_1080p"))
     r = ref.forward(s)
@@ -96,7 +92,7 @@ def test_fullsize_clipped_bit_exact_vs_reference_build(name, gpu_device):
 
 
 def test_fullsize_clipped_lists_are_sublists_and_gradients_hold(gpu_device):
-    from test_gpu_fullsize import _scene, CONFIGS
+    from sweep_support import FULLSIZE_CONFIGS as CONFIGS, fullsize_scene as _scene
     ref = _ref()
     s = _scene(CONFIGS["thuman800k_1080p"])
     dL = seeded_dL(s)

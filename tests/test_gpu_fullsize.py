@@ -8,32 +8,10 @@ import pytest
 import torch
 
 import util
-from util import run_product
+from sweep_support import FULLSIZE_CONFIGS as CONFIGS, fullsize_scene as _scene
+from util import run_product, strict_reference as _ref
 
 pytestmark = pytest.mark.gpu
-
-CONFIGS = {
-    # BASELINE.json configs[1]: THuman-256 (200K voxelised), 1080p, inference profile
-    "thuman256_1080p": dict(workload="synth-THuman-256", W=1920, H=1080, profile="inference", view=0),
-    # configs[2]: THuman-800K, 1080p, training profile (the headline workload)
-    "thuman800k_1080p": dict(workload="synth-THuman-800K", W=1920, H=1080, profile="training", view=3),
-    # configs[4]: 2M-point sampled mesh, 4K
-    "mesh2m_4k": dict(workload="synth-mesh-2M", W=3840, H=2160, profile="training", view=5),
-}
-
-
-def _scene(cfg, voxel_exact=False):
-    from pcrender import camera, synth
-    cloud = synth.make_cloud(cfg["workload"], seed=0)
-    g = synth.make_gaussians(cloud, profile=cfg["profile"], seed=1)
-    if voxel_exact:
-        g["means3D"] = cloud["means3D"].copy()
-    v = camera.circle_views(12, fov_deg=45.0, width_px=cfg["W"], height_px=cfg["H"])[cfg["view"]]
-    return util.scene_from(g, v, cfg["W"], cfg["H"], bg=(1, 1, 1))
-
-
-def _ref():
-    return util.reference_build("strict")
 
 
 @pytest.mark.parametrize("name", ["thuman256_1080p", "thuman800k_1080p", "mesh2m_4k"])

@@ -4,86 +4,24 @@ the reference's circle path) rendered by the HIP library and by the reference bu
 kernels compiled for gfx950): integer outputs and forward floats must be bit-identical, gradients within tolerance.
 Each case is tiny, so the sweep also hits the degenerate ends (P = 1, 1x1 tile grids, lists shorter than a round,
 lists of several rounds, everything culled)."""
-import numpy as np
+import os
+
 import pytest
 
-import util
-from grad_ladder import Float64, assert_exits_stay_rare, hold_to_reference, new_tally
-from util import run_product
+from grad_ladder import (MAX_CASE_FRACTION, MAX_CASE_FRACTION_REF_TOO, MAX_ROW_FRACTION, MAX_ROW_FRACTION_REF_TOO, assert_exits_stay_rare,
+                         new_tally)
+from sweep_support import check_random_case
 
 pytestmark = pytest.mark.gpu
 
-import os
 N_CASES = int(os.environ.get("GSR_FUZZ_CASES", "512"))
-
-
-# How often a case / a gradient row leaves through each fallback of the gradient comparison below.  The bars are principled
-# (float32 conditioning of the per-Gaussian chain), but nothing stops them from being widened until everything passes, so
-# the exits are counted and capped: test_fuzz_escape_hatches_stay_rare fails when more than 1 % of the cases or 1e-4 of the
-# rows compared need one.
-# `*_reference_outside_too`: rows outside the plain bar against the float64 value in which the library is at least as close to that
-# value as the reference build is -- the reference itself misses the bar there; recorded, but not an escape of the library.
+# the exits of the gradient comparison (tests/grad_ladder.py) over the sweep, capped by test_fuzz_escape_hatches_stay_rare
 TALLY = new_tally()
-MAX_CASE_FRACTION = 0.01
-MAX_ROW_FRACTION = 1e-4
-# `reference_outside_too` has a cap of its own (looser: those are rows on which the REFERENCE misses the bar against the float64
-# value and the library is at least as close; but a drift of the library towards such rows should still show)
-MAX_CASE_FRACTION_REF_TOO = 0.02
-MAX_ROW_FRACTION_REF_TOO = 4e-4
-
-
-def _ref():
-    return util.reference_build("strict")
-
-
-def _case(i):
-    from pcrender import camera, synth
-    rng = np.random.default_rng(1000 + i)
-    W = int(rng.choice([1, 7, 16, 17, 31, 33, 64, 97, 130, 200]))
-    H = int(rng.choice([1, 5, 16, 23, 32, 48, 65, 111]))
-    P = int(rng.choice([1, 2, 63, 64, 65, 300, 1500, 4000]))
-    D = int(rng.integers(0, 4))
-    rows = int(rng.choice([(D + 1) ** 2, 16, 13 if D <= 2 else 16]))
-    rows = max(rows, (D + 1) ** 2)
-    scale = float(rng.choice([0.004, 0.02, 0.05, 0.15, 0.4]))
-    spread = float(rng.choice([0.3, 1.0, 3.0]))
-    g = synth.random_scene(P, W, H, seed=2000 + i, sh_degree=D, sh_rows=rows, spread=spread, scale=scale,
-                           anisotropy=float(rng.choice([0.5, 1.0, 2.0])))
-    if rng.random() < 0.3:
-        g["rotations"] = (g["rotations"] * rng.uniform(0.5, 1.6, (P, 1))).astype(np.float32)   # kernels never normalise (Q3)
-    if rng.random() < 0.2:
-        g["opacities"][:] = 1.0
-    if rng.random() < 0.15:
-        g["means3D"][:, 2] -= 5.0                                                              # mostly behind the camera
-    mode = "colors" if rng.random() < 0.25 else "sh"
-    use_cov = bool(rng.random() < 0.25)
-    mod = float(rng.choice([1.0, 1.0, 0.6, 2.5]))
-    bg = tuple(float(x) for x in rng.uniform(0, 1, 3))
-    if rng.random() < 0.5:
-        view = util.identity_camera(W, H, float(rng.choice([30.0, 45.0, 60.0, 80.0])))
-    else:                                   # the reference caller's circle camera, looking at the origin from r = 3
-        view = camera.circle_views(n_imgs=12, fov_deg=45.0, width_px=W, height_px=H)[int(rng.integers(0, 12))]
-        g["means3D"][:, 2] -= 3.0
-    return util.scene_from(g, view, W, H, bg=bg, mode=mode, scale_modifier=mod, use_cov3d=use_cov), mode
 
 
 @pytest.mark.parametrize("i", range(N_CASES))
 def test_random_case_matches_reference_build(i, gpu_device):
-    ref = _ref()
-    s, mode = _case(i)
-    dL = util.seeded_dL(s, seed=77 + i)
-    r, gr = ref.forward_backward(s, dL)
-    p, gp = run_product(s, gpu_device, dL_dpix=dL)
-    assert p["R"] == r["R"]
-    for k in ("radii", "tiles_touched", "vals", "keys", "ranges", "n_contrib"):
-        np.testing.assert_array_equal(p[k], r[k], err_msg="case %d %s" % (i, k))
-    vis = r["radii"] > 0
-    for k in ("depths", "means2D", "conic_opacity") + (() if mode == "colors" else ("rgb",)):
-        assert p[k][vis].tobytes() == r[k][vis].tobytes(), "case %d %s" % (i, k)
-    assert p["final_T"].tobytes() == r["final_T"].tobytes()
-    assert p["out_color"].tobytes() == r["out_color"].tobytes()
-    # the gradient comparison and its counted fallbacks: tests/grad_ladder.py (shared with the batched sweep)
-    hold_to_reference("case %d" % i, 4242 + i, gp, gr, Float64([s], [dL]), TALLY)
+    check_random_case(i, gpu_device, TALLY)
 
 
 def test_fuzz_escape_hatches_stay_rare():

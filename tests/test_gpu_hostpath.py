@@ -12,11 +12,9 @@ import numpy as np
 import pytest
 import torch
 
+from native_calls import to_device as _t
+
 pytestmark = pytest.mark.gpu
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 def _setup(dev, n_views=3, P=12000, W=208, H=176):

@@ -49,7 +49,7 @@ def test_documented_ctypes_stub_matches_oracle(name, oracle, gpu_device):
     g = stub.rasterize_gaussians_backward(args[0], args[1], radii, args[2], args[4], args[5], s.scale_modifier, args[7], args[8],
                                           args[9], s.tanfovx, s.tanfovy, t(dL), args[14], s.sh_degree, args[16], geom, R, binning,
                                           img, False)
-    names = ("dL_dmean2D", "dL_dcolor", "dL_dopacity", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot")
+    names = util.GRAD_NAMES
     gp = {n: x.cpu().numpy() for n, x in zip(names, g)}
     if not (err > 1e-4).any():
         util.check_grads(gp, go, "INTEGRATION.md stub / " + name)

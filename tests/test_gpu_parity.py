@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import util
+from native_calls import half_views
 from util import SCENES, build_scene, run_product, seeded_dL
 
 pytestmark = pytest.mark.gpu
@@ -203,14 +204,11 @@ def test_half_quadrant_forward_equals_the_8x8_kernel(name, gpu_device):
     from diff_gaussian_rasterization import _native as N
     s = build_scene(name)
     dL = seeded_dL(s)
-    was = N.lib.gsr_set_forward_half_views(-1)
-    try:
+    with half_views(None):
         assert N.lib.gsr_set_forward_half_views(0) == 0
         a, ga = run_product(s, gpu_device, dL_dpix=dL)
         assert N.lib.gsr_set_forward_half_views(1) == 1
         b, gb = run_product(s, gpu_device, dL_dpix=dL)
-    finally:
-        N.lib.gsr_set_forward_half_views(was)
     for k in ("out_color", "final_T", "n_contrib", "radii", "vals", "ranges", "tile_need"):
         assert a[k].tobytes() == b[k].tobytes(), k
     r = _ref("strict").forward(s)
@@ -227,7 +225,7 @@ def test_subquadrant_moments_mode_is_correct_and_more_accurate(oracle, gpu_devic
     scenes, and against the float64 render backward (the oracle's arbiter) the mean2D / conic sums are closer than in the default
     mode (moments about the quadrant centre) over a set of fuzz cases with sub-pixel to tile-sized splats."""
     import torch
-    import test_gpu_fuzz as F
+    import sweep_support as F
     from diff_gaussian_rasterization import _native as N
     ref = _ref("strict")
     was = N.lib.gsr_set_backward_moments(-1)
@@ -243,7 +241,7 @@ def test_subquadrant_moments_mode_is_correct_and_more_accurate(oracle, gpu_devic
             _check_grads(gp, gr, name + " (sub-quadrant moments vs ref)")
         err = {m: {"mean2D": [], "conic": []} for m in (0, 1, 2)}
         for c in range(0, 48):
-            s, _ = F._case(c)
+            s, _ = F.random_case(c)
             if s.P == 0:
                 continue
             dL = seeded_dL(s, seed=77 + c)

@@ -5,13 +5,10 @@ import pytest
 import torch
 
 import util
+from native_calls import to_device as _t
 from util import build_scene, run_product
 
 pytestmark = pytest.mark.gpu
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 @pytest.mark.parametrize("name", ["capsule_circle", "big_splats", "culled_mix"])

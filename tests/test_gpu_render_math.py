@@ -10,64 +10,19 @@
   4. the Python surface: render_passes follows set_render_math.
 
 Every test that flips the switch restores it."""
-import contextlib
-
 import numpy as np
 import pytest
 import torch
 
 import util
+from native_calls import (RENDER_SCENES as SCENES, RGB_TOL, batch_args as _batch_args, cloud_views as _views_scene, half_views,
+                          one_view as _one_view, render_math, renders as _renders, to_device as _t)
 from util import build_scene, run_product
 
 pytestmark = pytest.mark.gpu
 
-RGB_TOL = 1e-4            # the contract's tolerance (north_star)
 MAX_FLIP_SHARE = 5e-3     # the project's own bar for threshold flips (test_fma_contraction_moves_few_decisions)
-SCENES = ["random_aniso", "sh_deg3", "colors_precomp", "cov3d_precomp", "culled_mix", "all_culled", "voxel_ties", "opaque_early_stop",
-          "capsule_circle", "big_splats", "deep_stack", "one_gaussian"]
 F = np.float32
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-@contextlib.contextmanager
-def render_math(mode):
-    """the arithmetic mode for the block; the value in force before is restored whatever happens inside"""
-    from diff_gaussian_rasterization import _native as N
-    was = N.lib.gsr_set_render_math(-1)
-    try:
-        assert N.lib.gsr_set_render_math(mode) == mode
-        yield
-    finally:
-        N.lib.gsr_set_render_math(was)
-
-
-@contextlib.contextmanager
-def half_views(views):
-    from diff_gaussian_rasterization import _native as N
-    was = N.lib.gsr_set_forward_half_views(-1)
-    try:
-        assert N.lib.gsr_set_forward_half_views(views) == views
-        yield
-    finally:
-        N.lib.gsr_set_forward_half_views(was)
-
-
-_RENDERS = {}
-
-
-def _renders(name, dev):
-    """(scene, exact inference forward, fast inference forward) of a test scene: rendered once, shared, never written to"""
-    if name not in _RENDERS:
-        s = build_scene(name)
-        with render_math(0):
-            exact, _ = run_product(s, dev, need_backward=False)
-        with render_math(1):
-            fast, _ = run_product(s, dev, need_backward=False)
-        _RENDERS[name] = (s, exact, fast)
-    return _RENDERS[name]
 
 
 def _over(a, b):
@@ -116,30 +71,6 @@ def test_fast_half_quadrant_kernel_equals_the_fast_8x8_kernel(name, gpu_device):
         assert a[k].tobytes() == b[k].tobytes(), k
     # (and it is the fast arithmetic both ran: the shared renders are the default single-view path)
     assert b["out_color"].tobytes() == _renders(name, gpu_device)[2]["out_color"].tobytes()
-
-
-def _views_scene(n_views=3, P=12000, W=208, H=176):
-    from pcrender import camera, synth
-    cloud = synth.make_cloud("synth-THuman-256", seed=0, P=P)
-    g = synth.make_gaussians(cloud, profile="training", seed=1)
-    views = camera.circle_views(12, fov_deg=45.0, width_px=W, height_px=H)
-    return g, [views[i] for i in [0, 1, 5, 7, 10][:n_views]], W, H
-
-
-def _batch_args(g, views, W, H, dev, bg=(1, 1, 1)):
-    e = torch.empty(0)
-    vm = torch.stack([v["viewmatrix"] for v in views]).to(dev)
-    pm = torch.stack([v["projmatrix"] for v in views]).to(dev)
-    cp = torch.stack([v["campos"] for v in views]).to(dev)
-    return (_t(np.asarray(bg, F), dev), _t(g["means3D"], dev), e, _t(g["opacities"], dev), _t(g["scales"], dev),
-            _t(g["rotations"], dev), 1.0, e, vm, pm, views[0]["tanfovx"], views[0]["tanfovy"], H, W, _t(g["shs"], dev),
-            g["sh_degree"], cp, False, False)
-
-
-def _one_view(args, v):
-    a = list(args)
-    a[8], a[9], a[16] = args[8][v], args[9][v], args[16][v]
-    return a
 
 
 def test_a_view_alone_and_in_a_batch_agree_and_calls_repeat(gpu_device):

@@ -18,10 +18,12 @@ import torch
 
 import round_cases as RC
 import util
-from grad_ladder import Float64, assert_exits_stay_rare, hold_to_reference, new_tally
-from test_gpu_batch_fuzz import _backward, _check_view_against_reference, _same_bits
-from test_gpu_channels_fp64 import _args, _compare_batch, _inputs, _ref_decomposition, _t
-from test_gpu_fuzz import MAX_CASE_FRACTION, MAX_CASE_FRACTION_REF_TOO, MAX_ROW_FRACTION, MAX_ROW_FRACTION_REF_TOO
+from fp64_pins import channel_inputs as _inputs, compare_batch as _compare_batch, ref_decomposition as _ref_decomposition
+from grad_ladder import (MAX_CASE_FRACTION, MAX_CASE_FRACTION_REF_TOO, MAX_ROW_FRACTION, MAX_ROW_FRACTION_REF_TOO, Float64,
+                         assert_exits_stay_rare, hold_to_reference, new_tally)
+from native_calls import reference_lists, scene_args as _args, to_device as _t
+from sweep_support import (check_view_against_reference as _check_view_against_reference, records_backward as _backward,
+                           same_bits as _same_bits)
 
 pytestmark = pytest.mark.gpu
 
@@ -50,8 +52,7 @@ def test_colour_forward_and_backward(name, V, gpu_device):
     f64 = Float64(scenes, dL, nthreads=16)
     n_pairs = max(1, max(r["R"] for r in rf))
 
-    old = N.set_reference_lists(True)
-    try:
+    with reference_lists(True):
         full = N.rasterize_gaussians_batch(*args, need_backward=True)
         for v in range(V):
             _check_view_against_reference(N, "%s view %d" % (tag, v), rf[v], full, v, V, P, W, H, "sh")
@@ -72,8 +73,6 @@ def test_colour_forward_and_backward(name, V, gpu_device):
         d2, r2 = _backward(N, args, run, dL_t, True, pairs=n_pairs)
         assert _same_bits(d1, d2) and np.array_equal(r1.view(np.uint32), r2.view(np.uint32)), tag + ": deterministic, clipped lists"
         util.check_grads(d1, gp, tag + ": deterministic vs atomic, clipped lists", names=NAMES)
-    finally:
-        N.set_reference_lists(old)
 
 
 @pytest.mark.parametrize("V", [1, 2])
@@ -88,11 +87,8 @@ def test_channels_forward_and_backward(name, nx, V, oracle, gpu_device):
     tag = "round scene %s V=%d nx=%d" % (name, V, nx)
     layout = 2 if nx == 8 else 1
     x, dense, sc, bgx, dpix, dx = _inputs(P, V, nx, layout, seed=60 + nx + V, H=H, W=W)
-    old = N.set_reference_lists(True)
-    try:
+    with reference_lists(True):
         run = _compare_batch(N, oracle, scenes, x, dense, sc, bgx, dpix, dx, layout, gpu_device, tag, 1e-5)
-    finally:
-        N.set_reference_lists(old)
     images = np.zeros((V, nx, H, W), np.float32)
     _ref_decomposition(ref, scenes, dense, sc, bgx, dpix, dx, images=images)
     out_x = run[3].cpu().numpy()

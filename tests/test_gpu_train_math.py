@@ -12,48 +12,24 @@ forward kernels with their checkpoint stores and the RenderBwdFast backward kern
   6. the Python surface.
 
 Every test that flips a switch restores it."""
-import contextlib
-
 import numpy as np
 import pytest
 import torch
 
 import util
+import fp64_pins as FP
+import native_calls as NC
+import sweep_support as SW
+from fp64_pins import deep_stack_cloud as _deep_stack, synth_scenes as _synth, view_settings as _settings
+from native_calls import (RENDER_SCENES as SCENES, RGB_TOL, batch_args as _batch_args, cloud_views as _views_scene, half_views, moments,
+                          render_math, renders as _renders, scene_args as _args, to_device as _t, train_math)
 from util import build_scene, run_product
-import test_gpu_channels_backward as CB
-import test_gpu_colour_fp64 as C64
-import test_gpu_deterministic_backward as DET
-from test_gpu_channels_fp64 import _args, _deep_stack, _settings, _synth, _t
-from test_gpu_render_math import RGB_TOL, SCENES, _batch_args, _renders, _views_scene, half_views, render_math
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 MODES = (0, 1, 2)
-NAMES = C64.NAMES
-
-
-@contextlib.contextmanager
-def train_math(mode):
-    """the training arithmetic for the block; the value in force before is restored whatever happens inside"""
-    from diff_gaussian_rasterization import _native as N
-    was = N.lib.gsr_set_train_math(-1)
-    try:
-        assert N.lib.gsr_set_train_math(mode) == mode
-        yield
-    finally:
-        N.lib.gsr_set_train_math(was)
-
-
-@contextlib.contextmanager
-def moments(mode):
-    from diff_gaussian_rasterization import _native as N
-    was = N.lib.gsr_set_backward_moments(-1)
-    try:
-        assert N.lib.gsr_set_backward_moments(mode) == mode
-        yield
-    finally:
-        N.lib.gsr_set_backward_moments(was)
+NAMES = util.GRAD_NAMES
 
 
 STATE = ("out_color", "final_T", "n_contrib")
@@ -155,14 +131,14 @@ def _flipped(s, dev):
 
 
 def _pin_fast(N, oracle, ref, scenes, dpix, dev, tag, cache, flips, run=None, args=None):
-    """C64._pin under the training switch in force.  A V = 1 scene whose fast forward decides differently from the exact one (flips
+    """FP.colour_pin under the training switch in force.  A V = 1 scene whose fast forward decides differently from the exact one (flips
     counts them) may leave check_grads' bars, but only in rows of Gaussians listed in a tile that holds such a pixel."""
-    gp, rec, run = C64._backward(N, _args(scenes, dev) if args is None else args, dpix, dev, run=run)
+    gp, rec, run = FP.colour_records_backward(N, _args(scenes, dev) if args is None else args, dpix, dev, run=run)
     if "want" not in cache:
-        cache["want"] = C64._fp64(oracle, scenes, dpix)
+        cache["want"] = FP.colour_fp64(oracle, scenes, dpix)
     want = cache["want"]
     try:
-        C64._well_conditioned(gp, rec, want, scenes, tag)
+        FP.well_conditioned(gp, rec, want, scenes, tag)
     except AssertionError:
         if N.lib.gsr_set_train_math(-1) != 1 or len(scenes) != 1:
             raise
@@ -187,9 +163,9 @@ def _pin_fast(N, oracle, ref, scenes, dpix, dev, tag, cache, flips, run=None, ar
         assert not any(r.any() for r in rec), tag
         return None, run
     if "ref" not in cache:
-        cache["ref"] = C64._ref(ref, scenes, dpix)
+        cache["ref"] = FP.reference_sums(ref, scenes, dpix)
     rv, rt = cache["ref"]
-    return C64._ill_conditioned(gp, rec, want, rv, rt, scenes), run
+    return FP.ill_conditioned(gp, rec, want, rv, rt, scenes), run
 
 
 KEYS = ("mean2D", "conic", "chain")
@@ -231,12 +207,12 @@ def test_fast_gradients_against_float64(oracle, gpu_device):
     dev = gpu_device
     ref = util.reference_build()
     g, views, W, H, batch = _synth(3, P=12000, W=96, H=80)
-    cases = [(name, [build_scene(name)]) for name in C64.MATRIX_SCENES] + [("synth V=3", batch)]
+    cases = [(name, [build_scene(name)]) for name in FP.MATRIX_SCENES] + [("synth V=3", batch)]
     err = {(t, m): {k: [] for k in KEYS} for t in ("fast", "exact", "ref") for m in MODES}
     synth = {}
     flips = {}
     for name, scenes in cases:
-        dpix = C64._dpix(scenes, 7 + len(name))
+        dpix = FP.scenes_dpix(scenes, 7 + len(name))
         cache = {}
         for mode in MODES:
             with moments(mode):
@@ -271,14 +247,14 @@ def test_fast_backward_starts_from_the_fast_forward_s_checkpoints(oracle, gpu_de
     g, W, H = _deep_stack(P, 17)
     cam = util.identity_camera(W, H)
     scenes = [util.scene_from(g, cam, W, H, bg=(0.2, 0.3, 0.4)) for _ in range(V)]
-    dpix = C64._dpix(scenes, 60 + V)
+    dpix = FP.scenes_dpix(scenes, 60 + V)
     ref = util.reference_build()
     cache, res = {}, {}
     for t, sw in (("fast", 1), ("exact", 0)):
         with train_math(sw):
             res[t], run = _pin_fast(N, oracle, ref, scenes, dpix, dev, "deep stack V=%d %s" % (V, t), cache, {})
     counts, _, _, geom, binning, img = run
-    assert CB._long_lists(N, geom, binning, img, counts, P, W, H, V) > 32 << (9 if V == 1 else 10)
+    assert NC.longest_list(N, geom, binning, img, counts, P, W, H, V) > 32 << (9 if V == 1 else 10)
     _hold("deep%d" % V, _ratios(*res["fast"]), _ratios(*res["exact"]))
 
 
@@ -287,10 +263,10 @@ def test_fast_backward_after_a_recolor(oracle, gpu_device):
     from diff_gaussian_rasterization import _native as N
     from fp64_channels import with_colours
     dev = gpu_device
-    g, scenes, args = C64._recolor_setup(dev)
+    g, scenes, args = FP.recolor_setup(dev)
     P = scenes[0].P
     cols = np.random.default_rng(30).uniform(-0.2, 1.2, (P, 3)).astype(F)
-    dpix = C64._dpix(scenes, 31)
+    dpix = FP.scenes_dpix(scenes, 31)
     coloured = [with_colours(s, cols, s.bg) for s in scenes]
     ref = util.reference_build()
     cache, res = {}, {}
@@ -298,7 +274,7 @@ def test_fast_backward_after_a_recolor(oracle, gpu_device):
         with train_math(sw):
             a = list(args)
             run = N.rasterize_gaussians_batch(*a, need_backward=True)
-            C64._recolor(N, a, run, colours=_t(cols, dev))
+            FP.recolor(N, a, run, colours=_t(cols, dev))
             a[2], a[14], a[15] = _t(cols, dev), torch.empty(0), 0
             res[t], _ = _pin_fast(N, oracle, ref, coloured, dpix, dev, "recolor %s" % t, cache, {}, run=run, args=a)
     _hold("recolor", _ratios(*res["fast"]), _ratios(*res["exact"]))
@@ -310,18 +286,18 @@ def test_backward_follows_the_forward_not_the_switch(gpu_device):
     dev = gpu_device
     s = build_scene("random_aniso")
     args = _args([s], dev)
-    dpix = DET._dpix(1, s.H, s.W, 3)
+    dpix = SW.uniform_dpix(1, s.H, s.W, 3)
 
     def seq(fwd, bwd):
         with train_math(fwd):
             run = N.rasterize_gaussians_batch(*args, need_backward=True)
         with train_math(bwd):
-            return DET._backward(N, args, run, dpix, True, dev)
+            return SW.nine_tensors_backward(N, args, run, dpix, True, dev)
     fast_off, fast_on = seq(1, 0), seq(1, 1)
-    assert DET._same(fast_off, fast_on)
+    assert SW.same_bits(fast_off, fast_on)
     exact_on, exact_off = seq(0, 1), seq(0, 0)
-    assert DET._same(exact_on, exact_off)
-    assert not DET._same(fast_on, exact_off)        # (the two modes are distinguishable here at all)
+    assert SW.same_bits(exact_on, exact_off)
+    assert not SW.same_bits(fast_on, exact_off)        # (the two modes are distinguishable here at all)
 
 
 # ---- 4. deterministic fast backward -------------------------------------------------------------------------------------------------
@@ -332,16 +308,16 @@ def test_deterministic_fast_backward(gpu_device, name, mode):
     dev = gpu_device
     s = build_scene(name)
     args = _args([s], dev)
-    dpix = DET._dpix(1, s.H, s.W, 3)
+    dpix = SW.uniform_dpix(1, s.H, s.W, 3)
     with train_math(1), moments(mode):
         run = N.rasterize_gaussians_batch(*args, need_backward=True)
-        a = DET._backward(N, args, run, dpix, True, dev)
-        b = DET._backward(N, args, run, dpix, True, dev)
-        atomic = DET._backward(N, args, run, dpix, False, dev)
+        a = SW.nine_tensors_backward(N, args, run, dpix, True, dev)
+        b = SW.nine_tensors_backward(N, args, run, dpix, True, dev)
+        atomic = SW.nine_tensors_backward(N, args, run, dpix, False, dev)
         run2 = N.rasterize_gaussians_batch(*args, need_backward=True)
-        c = DET._backward(N, args, run2, dpix, True, dev)
-    assert DET._same(a, b), "two deterministic fast backwards over one forward differ"
-    assert DET._same(a, c), "a second fast forward + backward gave other bits"
+        c = SW.nine_tensors_backward(N, args, run2, dpix, True, dev)
+    assert SW.same_bits(a, b), "two deterministic fast backwards over one forward differ"
+    assert SW.same_bits(a, c), "a second fast forward + backward gave other bits"
     assert all(np.isfinite(v).all() for v in a.values())
     util.check_grads(a, {k: atomic[k] for k in NAMES}, "%s mode %d, deterministic vs atomic (fast)" % (name, mode), names=NAMES)
 
@@ -363,7 +339,7 @@ def test_channels_training_calls_do_not_look_at_the_switch(gpu_device, nx):
     dx = _t(rng.uniform(-1, 1, (V, nx, H, W)).astype(F), dev)
 
     def run():
-        gp, gx, r = CB._channels_bwd(N, args, x, scale, bgx, dpix, dx)
+        gp, gx, r = NC.channels_backward(N, args, x, scale, bgx, dpix, dx)
         counts, color, radii, out_x, geom, binning, img = r
         st = [N.query(k, P, W, H, counts[v], geom, binning, img, view=v, n_views=V) for k in ("FINAL_T", "N_CONTRIB") for v in range(V)]
         return gp, gx, r, st
@@ -374,7 +350,7 @@ def test_channels_training_calls_do_not_look_at_the_switch(gpu_device, nx):
     assert r0[0] == r1[0] and torch.equal(r0[1], r1[1]) and torch.equal(r0[2], r1[2]) and torch.equal(r0[3], r1[3])
     for p, q in zip(st0, st1):
         assert torch.equal(p, q)
-    CB._check(gp1, gp0, gx1, gx0, "channels backward nx=%d, training switch on vs off" % nx)
+    FP.check_channels_grads(gp1, gp0, gx1, gx0, "channels backward nx=%d, training switch on vs off" % nx)
 
 
 # ---- 6. Python ----------------------------------------------------------------------------------------------------------------------
@@ -390,7 +366,7 @@ def fast_training():
 
 def test_python_images_are_the_fast_inference_images(gpu_device, fast_training):
     d, dev = fast_training, gpu_device
-    g, views, W, H = CB._scene(3, P=12000, W=208, H=176)
+    g, views, W, H = NC.circle_scene(3, P=12000, W=208, H=176)
     sts = _settings(views, W, H, (0.1, 0.1, 0.1), dev, g["sh_degree"])
 
     def views_call(L):
@@ -399,12 +375,12 @@ def test_python_images_are_the_fast_inference_images(gpu_device, fast_training):
     def one_call(L):
         return d.GaussianRasterizer(sts[1])(means3D=L["means3D"], means2D=L["means2D"], shs=L["shs"], opacities=L["opacities"],
                                             scales=L["scales"], rotations=L["rotations"])[0]
-    plain = {k: v.detach() for k, v in DET._leaves(g, dev).items()}
+    plain = {k: v.detach() for k, v in SW.leaves(g, dev).items()}
     with render_math(1):
         want_views, want_one = views_call(plain), one_call(plain)      # nothing requires a gradient: inference forwards
     with render_math(0):
         exact_views = views_call(plain)
-        got_views, got_one = views_call(DET._leaves(g, dev)), one_call(DET._leaves(g, dev))
+        got_views, got_one = views_call(SW.leaves(g, dev)), one_call(SW.leaves(g, dev))
     assert torch.equal(got_views.detach(), want_views) and torch.equal(got_one.detach(), want_one)
     assert not torch.equal(exact_views, want_views)
 

@@ -11,7 +11,8 @@ import torch
 
 import util
 import view_stats_ref as R
-from camera_sweep import _args, _t
+from native_calls import (channels_backward_args, colour_backward_args, follower_args, scene_args as _args, scene_settings as _settings,
+                          to_device as _t)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,10 +28,7 @@ def _forward(N, args, need_backward=True):
 
 def _backward(N, args, run, dpix, deterministic=False):
     """the reference's 8-tuple: dL_dmeans2D [P,3], dL_dcolors [P,3], dL_dopacity [P,1], ..."""
-    counts, color, radii, geom, binning, img = run[:6]
-    return N.rasterize_gaussians_backward_batch(args[0], args[1], radii, args[2], args[4], args[5], args[6], args[7], args[8], args[9],
-                                                args[10], args[11], dpix, args[14], args[15], args[16], geom, binning, img, False,
-                                                deterministic=deterministic)
+    return N.rasterize_gaussians_backward_batch(*colour_backward_args(args, run, dpix), deterministic=deterministic)
 
 
 def _prefilled(V, P, dev, old=None):
@@ -50,9 +48,8 @@ def _stats(N, args, radii, geom, old=None, want=NAMES, V=None, out=None):
     V = args[8].shape[0] if V is None else V
     out = _prefilled(V, args[1].shape[0], dev, old) if out is None else out
     o = [t if n in want else None for n, t in zip(NAMES, out)]
-    N.backward_view_stats(args[0], args[1], radii[:V], args[2], args[4], args[5], args[6], args[7], args[8][:V], args[9][:V], args[10],
-                          args[11], args[12], args[13], args[14], args[15], args[16][:V], geom, accumulate=old is not None,
-                          grad_norm_sum=o[0], visible_views=o[1], max_radius=o[2], _out=tuple(o[3:]))
+    N.backward_view_stats(*follower_args(args, radii, geom, V), accumulate=old is not None, grad_norm_sum=o[0], visible_views=o[1],
+                          max_radius=o[2], _out=tuple(o[3:]))
     return {n: t.cpu().numpy() for n, t in zip(NAMES, o) if t is not None}
 
 
@@ -143,9 +140,7 @@ def _write(N, kind, scs, dev, dL_seed=500):
         x, sc, bgx, dx = CC.channels_inputs(scs)
         extra = (_t(x, dev), _t(sc, dev), _t(bgx, dev))
         run = N.rasterize_gaussians_batch(*args, need_backward=True, extra=extra)
-        g = N.rasterize_gaussians_backward_channels_batch(args[0], args[1], run[2], args[2], args[4], args[5], 1.0, args[7], args[8],
-                                                          args[9], args[10], args[11], dpix, args[14], args[15], args[16], run[3],
-                                                          run[4], run[5], False, extra, _t(dx, dev))
+        g = N.rasterize_gaussians_backward_channels_batch(*channels_backward_args(args, run, dpix, extra, _t(dx, dev), 1.0))
         return args, run, g
     run = _forward(N, args)
     if kind == "recolor_per_view":
@@ -279,14 +274,6 @@ def test_refusals_that_need_a_record(gpu_device):
 
 
 # ---- the Python layer -------------------------------------------------------------------------------------------------------
-def _settings(scs, dev):
-    from diff_gaussian_rasterization import GaussianRasterizationSettings
-    return [GaussianRasterizationSettings(
-        image_height=s.H, image_width=s.W, tanfovx=s.tanfovx, tanfovy=s.tanfovy, bg=_t(s.bg, dev), scale_modifier=1.0,
-        viewmatrix=_t(s.viewmatrix.reshape(4, 4), dev), projmatrix=_t(s.projmatrix.reshape(4, 4), dev), sh_degree=s.sh_degree,
-        campos=_t(s.campos, dev), prefiltered=False, debug=False) for s in scs]
-
-
 def _leaves(s, dev):
     out = [_t(a, dev).requires_grad_(True) for a in (s.means3D, s.opacities.reshape(-1, 1), s.shs, s.scales, s.rotations)]
     return out + [torch.zeros_like(out[0], requires_grad=True)]

@@ -37,6 +37,6 @@ def test_small_scene(gpu_device):
 
 
 def test_headline_frame(gpu_device):
-    import test_gpu_fullsize as F
-    s = F._scene(F.CONFIGS["thuman800k_1080p"])
+    import sweep_support as F
+    s = F.fullsize_scene(F.FULLSIZE_CONFIGS["thuman800k_1080p"])
     _compare("synth-THuman-800K 1080p", s, gpu_device, light=True)

@@ -21,6 +21,10 @@ from pcrender import synth  # noqa: E402
 REF_USES = {"strict": 0, "fast": 0}
 
 
+def strict_reference():
+    return reference_build("strict")
+
+
 def reference_build(variant="strict"):
     """The reference's own kernels built for gfx950 (oracle/_ref/libgsr_ref_<variant>.so, made by oracle/build_ref.sh where
     /root/reference exists; git-ignored, it rides to the GPU box with the push).  The -m gpu tests that compare against it are
@@ -258,7 +262,7 @@ def _run_product(scene, device, dL_dpix, debug, need_backward, light):
         g = N.rasterize_gaussians_backward(
             args[0], args[1], radii, args[2], args[4], args[5], scene.scale_modifier, args[7], args[8], args[9],
             scene.tanfovx, scene.tanfovy, t(dL_dpix), args[14], scene.sh_degree, args[16], geom, R, binning, img, debug)
-        names = ("dL_dmean2D", "dL_dcolor", "dL_dopacity", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot")
+        names = GRAD_NAMES
         grads = {n: x.cpu().numpy() for n, x in zip(names, g)}
     return out, grads
 
