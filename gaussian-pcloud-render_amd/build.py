@@ -17,7 +17,7 @@ OBJ_DIR = os.path.join(HERE, "build")
 LIB = os.path.join(OUT_DIR, "libgsr_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-UNITS = ["api", "preprocess", "sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "det_backward", "camera_bwd",
+UNITS = ["api", "host", "inspect", "preprocess", "sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "det_backward", "camera_bwd",
          "view_stats", "contrib_stats"]
 
 # -ffp-contract=off : one rounding per written operation (integer outputs reproducible, DESIGN.md "Numerics")
@@ -42,7 +42,7 @@ def build(force=False, save_temps=False, verbose=True):
     def cc(u):
         src, obj = os.path.join(CSRC, u + ".hip"), os.path.join(OBJ_DIR, u + ".o")
         cmd = [HIPCC] + FLAGS + ["-c", src, "-o", obj]
-        if u == "api":
+        if u in ("api", "inspect"):   # the units that define the C ABI's entries
             cmd.insert(-4, "-fvisibility=default")
         if save_temps:
             cmd += ["-save-temps=obj"]

@@ -1,4 +1,5 @@
-// api.hip -- the C ABI of include/gsr.h: argument checks, arena carving, kernel sequencing.
+// api.hip -- the render path of the C ABI of include/gsr.h: argument checks, arena carving, kernel sequencing.  The host state behind it
+// is host.hpp / host.hip, the process-wide switches are switches.hpp, and the entries only tests and measurements call are inspect.hip.
 //
 // Host orchestration corresponding to reference CR/rasterizer_impl.cu:198-336 (Rasterizer::forward) and
 // :340-434 (Rasterizer::backward), re-planned for this library's data flow.  One submission covers a BATCH of V camera
@@ -19,146 +20,21 @@
 // but only waited for once the WHOLE frame has been enqueued.  If a view's count exceeds the capacity the call returns
 // GSR_RETRY with the true counts and the caller repeats the binning half with a larger arena (resume = 1).
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
+#include <atomic>
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "common.hpp"
-#include <atomic>
-#include <map>
-#include <mutex>
+#include "host.hpp"
+#include "switches.hpp"
 
 namespace gsr {
-
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int check_launch(const Launch& L, const char* what)
-{
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && L.debug) e = hipStreamSynchronize(L.stream);  // CHECK_CUDA(…, debug) of the reference
-    if (e != hipSuccess) return fail(GSR_ERR_HIP, "[gsr] %s: %s", what, hipGetErrorString(e));
-    return GSR_OK;
-}
-
-// ---- optional per-step timing (hipEvents on the launch stream) -------------------------------------
-// Records are kept PER STREAM (several host threads may render at once, each on its own stream, and one frame's forward
-// and backward usually come from different host threads -- autograd runs the backward on its own thread -- but on the
-// same stream).  The switch is process wide.
-struct ProfEntry {
-    const char* name;
-    int a, b;  // indices into the stream's event pool
-};
-struct ProfTables {
-    std::vector<hipEvent_t> pool;
-    size_t used = 0;
-    std::vector<ProfEntry> rec;
-    int event()
-    {
-        if (used == pool.size()) {
-            // timing events only: no system-scope fence when they are recorded (hipEventRecord's default release writes the L2s back
-            // and invalidates them between two stages, so the kernel behind an event pair started cold: the per-stage pass read
-            // k_render_backward 7-10 % slower than the kernel trace of the same run, profiles/r04_bench_kernel_stats.csv)
-            hipEvent_t e;
-            if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) (void)hipEventCreate(&e);
-            pool.push_back(e);
-        }
-        return (int)used++;
-    }
-};
-static std::atomic<int> g_prof_on{0};    // 0 off, 1 every stage, 2 the two render kernels only (cheap enough for a timed region)
-static std::mutex g_prof_mu;
-static std::map<hipStream_t, ProfTables> g_prof;   // guarded by g_prof_mu
-
-struct ProfScope {
-    hipStream_t s;
-    bool on;
-    ProfEntry e;
-    ProfScope(const char* name, hipStream_t stream) : s(stream), on(false)
-    {
-        const int mode = g_prof_on;
-        on = mode == 1 || (mode == 2 && strncmp(name, "render_", 7) == 0);
-        if (!on) return;
-        e.name = name;
-        hipEvent_t ea;
-        {
-            std::lock_guard<std::mutex> lk(g_prof_mu);
-            ProfTables& t = g_prof[s];
-            e.a = t.event();
-            e.b = t.event();
-            ea = t.pool[e.a];
-        }
-        (void)hipEventRecord(ea, s);
-    }
-    ~ProfScope()
-    {
-        if (!on) return;
-        std::lock_guard<std::mutex> lk(g_prof_mu);
-        ProfTables& t = g_prof[s];
-        (void)hipEventRecord(t.pool[e.b], s);
-        t.rec.push_back(e);
-    }
-};
-
-// ---- per-thread landing zone for the counter read-back ----------------------------------------------------
-// Host memory mapped into the device: the pair-emission kernel stores the per-view counters there itself, and the host
-// reads them after an event recorded behind that kernel.  No copy command (on this runtime a small device->host copy is a
-// blit kernel plus two ~10 us bubbles in the stream).
-constexpr int MAX_VIEWS = 256;
-// One per (host thread, device): an event belongs to the device that was current when it was created, so a thread that
-// renders on several GPUs needs one landing zone for each.
-struct HostLanding {
-    uint64_t* pinned = nullptr;   // [MAX_VIEWS][4]: num_rendered, trap flag, stall flag, -   (host address)
-    uint64_t* mapped = nullptr;   // the same memory as the device sees it
-    hipEvent_t ev = nullptr;
-};
-static thread_local std::map<int, HostLanding> t_lands;
-static int landing(HostLanding** out)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(GSR_ERR_HIP, "[gsr] hipGetDevice: %s", hipGetErrorString(hipGetLastError()));
-    HostLanding& h = t_lands[dev];
-    if (!h.pinned) {
-        if (hipHostMalloc((void**)&h.pinned, MAX_VIEWS * 4 * sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-            hipHostGetDevicePointer((void**)&h.mapped, h.pinned, 0) != hipSuccess ||
-            // (hipEventDisableSystemFence on this event was tried -- the counters live in coherent host memory and the kernel fences
-            // them itself, so the record would not need the system-scope release of the L2s -- and cost the per-view path a fifth of
-            // its rate, 1 363 -> 1 050-1 130 frames/s, gpurun_out/r4m: waiting for such an event does not return when the emission
-            // kernel ends but when the stream drains, and the host stops running ahead of the device)
-            hipEventCreateWithFlags(&h.ev, hipEventDisableTiming) != hipSuccess) {
-            h.pinned = nullptr;
-            return fail(GSR_ERR_HIP, "[gsr] pinned host buffer: %s", hipGetErrorString(hipGetLastError()));
-        }
-    }
-    *out = &h;
-    return GSR_OK;
-}
 
 // pairs in the lists of the calling thread's last forward, per view (<= num_rendered: footprint clipping); gsr_last_list_pairs
 static thread_local std::vector<int64_t> t_list_pairs;
 
 // device->host read-backs the library has issued since it was loaded (one per forward call: the per-view counters)
 static std::atomic<long long> g_d2h_count{0};
-
-// ---- how the pair emission numbers its workgroups (common.hpp block_tickets) ------------------------------------------------------
-static std::atomic<int> g_tickets{[] { const char* e = getenv("GSR_TICKETS"); return e && atoi(e) == 0 ? 0 : 1; }()};
-int block_tickets(int set)
-{
-    if (set >= 0) g_tickets = set != 0;
-    return g_tickets;
-}
-
-static int tile_count(const gsr_params* p) { return ((p->W + TILE_X - 1) / TILE_X) * ((p->H + TILE_Y - 1) / TILE_Y); }
 
 static int check_params(const gsr_params* p, int V = 1)
 {
@@ -184,13 +60,6 @@ static int check_params(const gsr_params* p, int V = 1)
         return fail(GSR_ERR_INVALID, "[gsr] %lld tiles x %d views: too many for one launch", (long long)(gx * gy), V);
     return GSR_OK;
 }
-
-// how many u32 tile-key bits the tile sort covers: the reference's 32+bit minus the 32 depth bits
-static int tile_bits(int T) { return (int)higher_msb((uint32_t)T); }
-// which of the two ping-pong buffers holds the sorted lists (depends on the pass count only)
-static int sorted_buffer(int T) { return ((tile_bits(T) + RADIX_BITS - 1) / RADIX_BITS) & 1; }
-
-static inline void* align256(void* p) { return (void*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
 
 // Carve the caller's three allocations into V per-view arenas.  binning may be NULL (count-only forward).  with_grad: the
 // V gradient-record blocks that follow the V geometry arenas are part of the geometry allocation (need_backward calls).
@@ -234,78 +103,6 @@ static int make_batch(const gsr_params* p, int V, void* geom, size_t geom_bytes,
     return GSR_OK;
 }
 
-// What the last forward on a geometry arena saved for the backward, kept on the host so that gsr_backward_batch and
-// gsr_backward_batch_channels can refuse a backward that does not match it without reading anything back from the device.  Keyed by
-// the arena's address: every forward and recolor on an arena rewrites its record.
-struct FrameRecord {
-    int kind = 0;             // 0 colour forward, 1 channels forward, 2 recolor
-    int need_backward = 0;
-    int nx = 0, layout = 0;   // channels forwards
-    int V = 0, P = 0, W = 0, H = 0;
-    const void* xstate = nullptr;   // the extra-state block the channels forward saved into (NULL: none)
-    size_t xstate_bytes = 0;
-    int fwd_need_backward = -1;  // need_backward of the forward whose geometry and lists the arena holds (a recolor carries it on;
-                                 // -1: unknown, a recolor on an arena without a record)
-    int64_t list_pairs = -1;     // largest per-view pair count of that forward's lists (a recolor carries it on; -1: unknown): what the
-                                 // scratch of a deterministic backward has to hold slots for
-    int math = 0;                // arithmetic of the call that last wrote the colour saves (0 exact, 1 fast): the forward, or a recolor --
-                                 // it rewrites final_T and n_contrib of every pixel and, through the same kernel, every slice-boundary
-                                 // state and accumulated colour a backward reads.  The render backward runs the same mode.
-    int bwd_done = 0;            // a backward has run since this record was written (every forward and recolor writes a fresh one):
-                                 // the gradient records hold its sums, which is what gsr_backward_cameras reads
-    FrameRecord() = default;
-    FrameRecord(int kind_, const gsr_params* p, int V_) : kind(kind_), need_backward(p->need_backward != 0), V(V_), P(p->P), W(p->W), H(p->H) {}
-};
-static std::mutex g_frames_mu;
-static std::map<const void*, FrameRecord> g_frames;
-static void note_frame(const void* geom, const FrameRecord& r)
-{
-    std::lock_guard<std::mutex> lk(g_frames_mu);
-    if (g_frames.size() > 4096 && !g_frames.count(geom)) g_frames.clear();   // (arenas come and go; records of freed ones are dropped)
-    g_frames[geom] = r;
-}
-static bool find_frame(const void* geom, FrameRecord& r)
-{
-    std::lock_guard<std::mutex> lk(g_frames_mu);
-    const auto it = g_frames.find(geom);
-    if (it == g_frames.end()) return false;
-    r = it->second;
-    return true;
-}
-// read-modify-write of an arena's record under one lock (no record: nothing happens)
-template <class F> static void update_frame(const void* geom, F change)
-{
-    std::lock_guard<std::mutex> lk(g_frames_mu);
-    const auto it = g_frames.find(geom);
-    if (it != g_frames.end()) change(it->second);
-}
-
-// The one check of an arena's record for the entries that run on the arenas of a finished forward or recolor: `who` (the entry's
-// name in the messages) needs the last forward / recolor to have saved for a backward (GATE_SAVES; saves_tail ends that message),
-// a backward to have run since (GATE_RECORDS), and always the same V, P, W, H -- asked in this order.  Without a record (an arena
-// whose forward ran before the record table was last dropped, at more than 4096 arenas) the call goes ahead as it always did:
-// refusing it would break a valid call, and the callers' contract (gsr.h) is unchanged.  Returns through `out` (may be NULL) the
-// record, and through `known` whether there is one.
-enum { GATE_SAVES = 1, GATE_RECORDS = 2 };
-static int frame_gate(const char* who, const void* geom, const gsr_params* p, int V, int needs, const char* saves_tail,
-                      FrameRecord* out = nullptr, bool* known = nullptr)
-{
-    FrameRecord r;
-    const bool found = find_frame(geom, r);
-    if (out) *out = r;
-    if (known) *known = found;
-    if (!found) return GSR_OK;
-    if ((needs & GATE_SAVES) && !r.need_backward)
-        return fail(GSR_ERR_INVALID, "[gsr] %s: the last %s on this geometry arena had need_backward = 0%s", who,
-                    r.kind == 2 ? "gsr_forward_recolor" : "forward", saves_tail);
-    if ((needs & GATE_RECORDS) && !r.bwd_done)
-        return fail(GSR_ERR_INVALID, "[gsr] %s: no backward has run since the last forward or recolor on this geometry arena (the "
-                    "gradient records are empty; run one of the gsr_backward entries first)", who);
-    if (r.V != V || r.P != p->P || r.W != p->W || r.H != p->H)
-        return fail(GSR_ERR_INVALID, "[gsr] %s: V = %d, P = %d, %d x %d, but the last forward or recolor on this geometry arena "
-                    "had V = %d, P = %d, %d x %d", who, V, p->P, p->W, p->H, r.V, r.P, r.W, r.H);
-    return GSR_OK;
-}
 // per-view bytes of the extra-channel state for a binning arena of capacity cap
 static size_t xstate_view_bytes(int W, int H, int64_t cap, int nx) { return align_up(xstate_view(nullptr, W, H, cap, nx).bytes, 256); }
 
@@ -950,297 +747,6 @@ int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const
     return launch_mark_visible(L, P, means3D, viewmatrix, present);
 }
 
-// ---- inspection (tests / roofline report only) -------------------------------------------------------
-namespace {
-// One wave reads the shader clock (s_memtime: one tick per shader cycle) and the constant-rate wall clock (s_memrealtime) around a
-// fixed chain of dependent FMAs: delta(shader) / delta(wall) x the wall clock rate is the shader clock the chip is running at
-// while the probe is resident -- next to whatever else is on the device (DVFS follows the power budget, so a kernel time means
-// little without the clock it was measured at).
-__global__ void k_clock_probe(unsigned long long* out, int iters)
-{
-    const unsigned long long s0 = clock64(), w0 = wall_clock64();
-    float x = (float)threadIdx.x * 1e-3f;
-    for (int i = 0; i < iters; i++) {
-#pragma unroll
-        for (int k = 0; k < 64; k++) x = __builtin_fmaf(x, 0.999f, 1e-3f);
-    }
-    const unsigned long long s1 = clock64(), w1 = wall_clock64();
-    if (threadIdx.x == 0) {
-        out[0] = s1 - s0;
-        out[1] = w1 - w0;
-    }
-    if (x == 12345.678f) out[1] = 0;   // keeps the chain
-}
-__global__ void k_query(int what, int64_t n, const Splat* __restrict__ sp, const uint8_t* __restrict__ clamped,
-                        const uint32_t* __restrict__ k, int key16, const uint32_t* __restrict__ v, void* __restrict__ dst)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    float* d = (float*)dst;
-    switch (what) {
-    case GSR_Q_DEPTHS: d[i] = sp[i].q2.y; break;
-    case GSR_Q_MEANS2D: d[2 * i] = sp[i].q0.x; d[2 * i + 1] = sp[i].q0.y; break;
-    case GSR_Q_CONIC_OPACITY:
-        d[4 * i] = sp[i].q0.z; d[4 * i + 1] = sp[i].q0.w; d[4 * i + 2] = sp[i].q1.x; d[4 * i + 3] = sp[i].q1.y;
-        break;
-    case GSR_Q_RGB: d[3 * i] = sp[i].q1.z; d[3 * i + 1] = sp[i].q1.w; d[3 * i + 2] = sp[i].q2.x; break;
-    case GSR_Q_POINT_LIST_KEYS:
-        ((uint64_t*)dst)[i] = ((uint64_t)(key16 ? (uint32_t)((const uint16_t*)k)[i] : k[i]) << 32) | (uint64_t)__float_as_uint(sp[v[i]].q2.y);
-        break;
-    case GSR_Q_LIST_PAIRS: {
-        const uint64_t* c = (const uint64_t*)k;   // k = the view's counters
-        if (i == 0) { ((uint64_t*)dst)[0] = c[CNT_NUM_RENDERED]; ((uint64_t*)dst)[1] = c[CNT_NUM_REFERENCE]; }
-        break;
-    }
-    case GSR_Q_DEPTH_SORT: {
-        uint32_t* o = (uint32_t*)dst;   // k = the view's sortctl words
-        if (i == 0) { o[0] = k[SORTCTL_BASE]; o[1] = k[SORTCTL_BITS]; o[2] = depth_sort_passes(k[SORTCTL_BITS]); o[3] = 0u; }
-        break;
-    }
-    case GSR_Q_CLAMPED: {
-        uint8_t* c = (uint8_t*)dst;
-        c[3 * i] = clamped[i] & 1; c[3 * i + 1] = (clamped[i] >> 1) & 1; c[3 * i + 2] = (clamped[i] >> 2) & 1;
-        break;
-    }
-    default: break;
-    }
-}
-}  // namespace
-
-int gsr_query(const gsr_params* p, int what, const void* geom, const void* binning, size_t binning_bytes, const void* image,
-              int64_t R, void* dst, size_t dst_bytes, gsr_stream_t stream)
-{
-    if (!p || !dst) return fail(GSR_ERR_INVALID, "[gsr] query: NULL");
-    hipStream_t s = (hipStream_t)stream;
-    const int P = p->P, T = tile_count(p);
-    const int64_t N = (int64_t)p->W * p->H;
-    const GeomView g = geom_view(align256(const_cast<void*>(geom)), P);
-    if (binning && binning_bytes < 512) return fail(GSR_ERR_CAPACITY, "[gsr] query: binning arena too small");
-    const int64_t cap = binning ? bin_capacity_from_bytes(((binning_bytes - 256)) / 256 * 256) : 0;
-    if (binning && R > cap && (what == GSR_Q_POINT_LIST || what == GSR_Q_POINT_LIST_KEYS))
-        return fail(GSR_ERR_CAPACITY, "[gsr] query: arena holds %lld pairs, asked for %lld (the lists hold GSR_Q_LIST_PAIRS pairs)", (long long)cap, (long long)R);
-    const BinView b = bin_view(align256(const_cast<void*>(binning)), cap > 0 ? cap : 1);
-    const ImageView iv = image_view(align256(const_cast<void*>(image)), p->W, p->H);
-    const int res = sorted_buffer(T);
-    int64_t n = 0;
-    size_t bytes = 0;
-    const void* src = nullptr;
-    switch (what) {
-    case GSR_Q_DEPTHS: n = P; bytes = (size_t)P * 4; break;
-    case GSR_Q_MEANS2D: n = P; bytes = (size_t)P * 8; break;
-    case GSR_Q_CONIC_OPACITY: n = P; bytes = (size_t)P * 16; break;
-    case GSR_Q_RGB: n = P; bytes = (size_t)P * 12; break;
-    case GSR_Q_CLAMPED: n = P; bytes = (size_t)P * 3; break;
-    case GSR_Q_POINT_LIST_KEYS: n = R; bytes = (size_t)R * 8; break;
-    case GSR_Q_TILES_TOUCHED: src = g.tiles_touched; bytes = (size_t)P * 4; break;
-    case GSR_Q_POINT_LIST: src = b.val[res]; bytes = (size_t)R * 4; break;
-    case GSR_Q_RANGES: src = iv.ranges; bytes = (size_t)T * 8; break;
-    case GSR_Q_FINAL_T: src = iv.final_T; bytes = (size_t)N * 4; break;
-    case GSR_Q_N_CONTRIB: src = iv.n_contrib; bytes = (size_t)N * 4; break;
-    case GSR_Q_TILE_NEED: src = iv.tile_need; bytes = (size_t)T * 4; break;
-    case GSR_Q_DEPTH_SORT: n = 1; bytes = 16; break;
-    case GSR_Q_LIST_PAIRS: n = 1; bytes = 16; break;
-    default: return fail(GSR_ERR_INVALID, "[gsr] query: unknown item %d", what);
-    }
-    if (dst_bytes < bytes) return fail(GSR_ERR_CAPACITY, "[gsr] query %d: destination too small", what);
-    if (bytes == 0) return GSR_OK;
-    if (src) {
-        if (hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(GSR_ERR_HIP, "[gsr] query copy failed");
-    } else {
-        hipLaunchKernelGGL(k_query, dim3((unsigned)div_up(n, 256)), dim3(256), 0, s, what, n, g.splat, g.clamped,
-                           what == GSR_Q_DEPTH_SORT ? (const uint32_t*)g.sortctl
-                           : what == GSR_Q_LIST_PAIRS ? (const uint32_t*)g.counters : (const uint32_t*)b.key[res],
-                           (int)tile_keys16(T), b.val[res], dst);
-        if (hipGetLastError() != hipSuccess) return fail(GSR_ERR_HIP, "[gsr] query kernel failed");
-    }
-    return GSR_OK;
-}
-
-// Device self-test of internal primitives that have no observable output of their own: the matrix-core pixel
-// contraction of the render backward, and the stable radix sort against std::stable_sort on random keys with many ties.
-int gsr_selftest(gsr_stream_t stream)
-{
-    hipStream_t s = (hipStream_t)stream;
-    const DevBuf<float> d(256);
-    if (!d.p) return fail(GSR_ERR_HIP, "[gsr] selftest: hipMalloc failed");
-    const int rm = selftest_mm(s, d.p);
-    if (rm != 0) return fail(GSR_ERR_HIP, "[gsr] selftest: matrix-core pixel contraction wrong at check %d", rm);
-    const int rd = selftest_det_reduce(s);
-    if (rd != 0) return fail(GSR_ERR_HIP, "[gsr] selftest: ordered reduction of the deterministic backward differs from the host sum at check %d", rd);
-    const int rx = selftest_det_reduce_extra(s);
-    if (rx != 0) return fail(GSR_ERR_HIP, "[gsr] selftest: ordered reduction of the extra channels differs from the host sum at check %d", rx);
-
-    const int64_t n = 100003;
-    std::vector<uint32_t> hk(n), hv(n), order(n);
-    uint32_t x = 12345u;
-    for (int64_t i = 0; i < n; i++) {
-        x = x * 1664525u + 1013904223u;
-        hk[i] = (x >> 8) % 3001u;  // many ties
-        hv[i] = (uint32_t)i;
-        order[i] = (uint32_t)i;
-    }
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hk[a] < hk[b]; });
-    const DevBuf<uint32_t> k0(hk, s), k1(n), v0(n), v1(n), hist(RADIX * (size_t)sort_hist_stride(n)), tot(RADIX);
-    if (!k0.p || !k1.p || !v0.p || !v1.p || !hist.p || !tot.p) return fail(GSR_ERR_HIP, "[gsr] selftest: hipMalloc failed");
-    int res = 0;
-    const Launch L{s, 1};
-    const SortJob job{{k0.p, k1.p}, {v0.p, v1.p}, hist.p, tot.p, 0, nullptr, 0, n, 1};
-    if (int rc = launch_radix_sort_pairs(L, job, /*iota_vals=*/true, 12, &res)) return rc;
-    std::vector<uint32_t> gk(n), gv(n);
-    if (!(res ? k1 : k0).download(gk.data(), s) || !(res ? v1 : v0).download(gv.data(), s) || hipStreamSynchronize(s) != hipSuccess)
-        return GSR_ERR_HIP;
-    for (int64_t i = 0; i < n; i++)
-        if (gv[i] != order[i] || gk[i] != hk[order[i]]) return fail(GSR_ERR_HIP, "[gsr] selftest: radix sort differs from std::stable_sort at %lld", (long long)i);
-    return GSR_OK;
-}
-
-// Test probe of sort.hip: launch_radix_sort_pairs on the caller's arrays, in work buffers of its own (freed on every path, like the
-// self-test's).  The caller says which kernels run (key width, block size, depth control); nothing is decided silently here.
-int gsr_sort_probe(const void* keys, const uint32_t* vals, size_t stride, const uint64_t* n_dev, size_t n_stride, int V, int64_t cap,
-                   int end_bit, int flags, void* keys_out, uint32_t* vals_out, uint32_t* ctl_out, gsr_stream_t stream)
-{
-    const bool key16 = (flags & GSR_SORT_KEY16) != 0, small = (flags & GSR_SORT_SMALL_BLOCKS) != 0, depth = (flags & GSR_SORT_DEPTH_CTL) != 0;
-    if (flags & ~(GSR_SORT_KEY16 | GSR_SORT_SMALL_BLOCKS | GSR_SORT_DEPTH_CTL)) return fail(GSR_ERR_INVALID, "[gsr] sort probe: unknown flags 0x%x", flags);
-    if (!keys || !keys_out || !vals_out) return fail(GSR_ERR_INVALID, "[gsr] sort probe: NULL keys or outputs");
-    if (V < 1) return fail(GSR_ERR_INVALID, "[gsr] sort probe: view count %d", V);
-    if (cap < 0 || cap > ((int64_t)1 << 30)) return fail(GSR_ERR_INVALID, "[gsr] sort probe: capacity %lld", (long long)cap);
-    if (end_bit < 1 || end_bit > 32) return fail(GSR_ERR_INVALID, "[gsr] sort probe: end_bit %d is not in 1..32", end_bit);
-    if (key16 && end_bit > 16) return fail(GSR_ERR_INVALID, "[gsr] sort probe: 16-bit keys have no bit %d", end_bit - 1);
-    if (depth && (end_bit != 32 || key16 || vals != nullptr))
-        return fail(GSR_ERR_INVALID, "[gsr] sort probe: depth control sorts 32 bits of uint32_t keys with index values");
-    if (depth && !ctl_out) return fail(GSR_ERR_INVALID, "[gsr] sort probe: depth control needs ctl_out");
-    if (small && (key16 || end_bit % RADIX_BITS != 0))
-        return fail(GSR_ERR_INVALID, "[gsr] sort probe: small blocks take uint32_t keys and whole 8-bit digits");
-    const size_t ksz = key16 ? 2 : 4;
-    if (V > 1 && (stride % 256 != 0 || stride < (size_t)cap * 4))
-        return fail(GSR_ERR_INVALID, "[gsr] sort probe: view stride %zu (a multiple of 256, at least 4 * cap)", stride);
-    if (n_dev && V > 1 && (n_stride == 0 || n_stride % 8 != 0)) return fail(GSR_ERR_INVALID, "[gsr] sort probe: count stride %zu", n_stride);
-    if (cap == 0) return GSR_OK;
-
-    hipStream_t s = (hipStream_t)stream;
-    const int tile = small ? RS_TILE_SMALL : RS_TILE;
-    const size_t nblk_pad = (size_t)sort_hist_stride(cap, tile);
-    // one stride serves every array of a SortJob: the caller's when the count matrix fits it (the views then sit at the caller's
-    // alignment), else the count matrix's size
-    const size_t need = std::max(align_up((size_t)cap * 4, 256), (size_t)RADIX * nblk_pad * 4);
-    const size_t S = (V > 1 && stride >= need) ? stride : need;
-    const size_t words = (size_t)V * S / 4;
-    const DevBuf<uint32_t> k0(words), k1(words), v0(words), v1(words), hist(words), tot(words), mm(words), ctl(words);
-    if (!k0.p || !k1.p || !v0.p || !v1.p || !hist.p || !tot.p || !mm.p || !ctl.p) return fail(GSR_ERR_HIP, "[gsr] sort probe: hipMalloc failed");
-    const auto hip_fail = [&](const char* what) {
-        (void)hipStreamSynchronize(s);
-        (void)hipGetLastError();
-        return fail(GSR_ERR_HIP, "[gsr] sort probe: %s failed", what);
-    };
-    if (hipMemsetAsync(ctl.p, 0, words * 4, s) != hipSuccess) return hip_fail("memset");
-    for (int v = 0; v < V; v++) {
-        if (hipMemcpyAsync((char*)k0.p + v * S, (const char*)keys + v * stride, (size_t)cap * ksz, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-            (vals && hipMemcpyAsync((char*)v0.p + v * S, (const char*)vals + v * stride, (size_t)cap * 4, hipMemcpyDeviceToDevice, s) != hipSuccess))
-            return hip_fail("copy in");
-    }
-    SortJob job{{k0.p, k1.p}, {v0.p, v1.p}, hist.p, tot.p, S, n_dev, n_stride, cap, V};
-    job.small_blocks = small;
-    if (depth) { job.blk_minmax = mm.p; job.sortctl = ctl.p; }
-    int res = 0;
-    const Launch L{s, 1};
-    if (int rc = launch_radix_sort_pairs(L, job, /*iota_vals=*/vals == nullptr, end_bit, &res, key16)) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
-    std::vector<uint32_t> hctl((size_t)V * 4, 0u);
-    if (depth) {
-        for (int v = 0; v < V; v++)
-            if (hipMemcpyAsync(&hctl[4 * (size_t)v], (const char*)ctl.p + v * S, 16, hipMemcpyDeviceToHost, s) != hipSuccess) return hip_fail("control words");
-        if (hipStreamSynchronize(s) != hipSuccess) return hip_fail("sort");
-    }
-    for (int v = 0; v < V; v++) {
-        int buf = res;
-        if (depth) {   // (base, bits, passes, 0) like GSR_Q_DEPTH_SORT; a view's result is where ITS pass count left it
-            hctl[4 * (size_t)v + 2] = depth_sort_passes(hctl[4 * (size_t)v + SORTCTL_BITS]);
-            hctl[4 * (size_t)v + 3] = 0u;
-            buf = (int)(hctl[4 * (size_t)v + 2] & 1u);
-        }
-        if (hipMemcpyAsync((char*)keys_out + v * stride, (const char*)job.key[buf] + v * S, (size_t)cap * ksz, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-            hipMemcpyAsync((char*)vals_out + v * stride, (const char*)job.val[buf] + v * S, (size_t)cap * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
-            return hip_fail("copy out");
-    }
-    if (depth && hipMemcpyAsync(ctl_out, hctl.data(), (size_t)V * 16, hipMemcpyHostToDevice, s) != hipSuccess) return hip_fail("control words");
-    if (hipStreamSynchronize(s) != hipSuccess) return hip_fail("sort");
-    return GSR_OK;
-}
-
-// Test probe of binning.hip: k_tile_ranges on the caller's sorted keys and device counts, straight into the caller's ranges.
-int gsr_tile_ranges_probe(const void* keys, size_t stride, const uint64_t* n_dev, size_t n_stride, int V, int64_t cap, int T, int key16,
-                          uint32_t* ranges, gsr_stream_t stream)
-{
-    if (!keys || !n_dev || !ranges) return fail(GSR_ERR_INVALID, "[gsr] tile ranges probe: NULL");
-    if (V < 1) return fail(GSR_ERR_INVALID, "[gsr] tile ranges probe: view count %d", V);
-    if (cap < 0 || cap > 0xFFFFFFFFll) return fail(GSR_ERR_INVALID, "[gsr] tile ranges probe: capacity %lld", (long long)cap);
-    if (T < 1 || (key16 && T > 65536)) return fail(GSR_ERR_INVALID, "[gsr] tile ranges probe: %d tiles", T);
-    if (V > 1 && (stride % 16 != 0 || stride < (size_t)cap * (key16 ? 2 : 4) || n_stride == 0 || n_stride % 8 != 0))
-        return fail(GSR_ERR_INVALID, "[gsr] tile ranges probe: view strides %zu / %zu", stride, n_stride);
-    hipStream_t s = (hipStream_t)stream;
-    const Launch L{s, 1};
-    if (int rc = launch_tile_ranges_raw(L, V, n_dev, n_stride, cap, keys, stride, reinterpret_cast<uint2*>(ranges), (size_t)T * sizeof(uint2), T, key16 != 0)) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
-    return GSR_OK;
-}
-
-int gsr_clock_probe_launch(void* dst16, int iters, gsr_stream_t stream)
-{
-    if (!dst16 || iters < 1) return fail(GSR_ERR_INVALID, "[gsr] clock probe: bad argument");
-    hipLaunchKernelGGL(k_clock_probe, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned long long*)dst16, iters);
-    if (hipGetLastError() != hipSuccess) return fail(GSR_ERR_HIP, "[gsr] clock probe launch failed");
-    return GSR_OK;
-}
-
-int gsr_wall_clock_khz(void)
-{
-    int dev = 0, khz = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess) return 0;
-    return khz;
-}
-
-void gsr_set_profiling(int on)
-{
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    g_prof_on = on < 0 ? 0 : on > 2 ? 1 : on;
-    for (auto& kv : g_prof) { kv.second.rec.clear(); kv.second.used = 0; }
-}
-
-int gsr_get_profile(const char** names, float* ms, int cap)
-{
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    int n = 0;
-    for (auto& kv : g_prof) {
-        ProfTables& t = kv.second;
-        for (auto& e : t.rec) {
-            if (n >= cap) break;
-            (void)hipEventSynchronize(t.pool[e.b]);
-            float d = 0;
-            (void)hipEventElapsedTime(&d, t.pool[e.a], t.pool[e.b]);
-            names[n] = e.name;
-            ms[n] = d;
-            n++;
-        }
-        t.rec.clear();
-        t.used = 0;
-    }
-    return n;
-}
-
-#ifdef GSR_STATS
-__attribute__((visibility("default"))) int gsr_debug_bwd_stats(unsigned long long* out8, int reset) { return gsr::debug_bwd_stats(out8, reset); }
-__attribute__((visibility("default"))) int gsr_debug_scatter_times(unsigned long long* out8, int reset) { return gsr::debug_scatter_times(out8, reset); }
-__attribute__((visibility("default"))) int gsr_debug_fwd_times(unsigned long long* out8, int reset) { return gsr::debug_fwd_times(out8, reset); }
-__attribute__((visibility("default"))) int gsr_debug_fwd_records(unsigned* out, int n) { return gsr::debug_fwd_records(out, n); }
-__attribute__((visibility("default"))) int gsr_debug_bwd_times(unsigned long long* out8, int reset) { return gsr::debug_bwd_times(out8, reset); }
-__attribute__((visibility("default"))) int gsr_debug_bwd_records(unsigned* out, int n) { return gsr::debug_bwd_records(out, n); }
-__attribute__((visibility("default"))) int gsr_debug_dup_times(unsigned long long* out8, int reset) { return gsr::debug_dup_times(out8, reset); }
-#endif
-
 long long gsr_d2h_count(void) { return gsr::g_d2h_count.load(); }
 int gsr_set_forward_half_views(int views) { return gsr::forward_half_views(views); }
 int gsr_set_backward_moments(int mode) { return gsr::backward_subquadrant_moments(mode); }
@@ -1254,7 +760,7 @@ int gsr_last_list_pairs(int64_t* out, int V)
     return GSR_OK;
 }
 
-const char* gsr_last_error(void) { return gsr::g_err; }
+const char* gsr_last_error(void) { return gsr::last_error(); }
 const char* gsr_version(void) { return "gsr-hip 0.3 (gfx950)"; }
 
 }  // extern "C"

@@ -15,6 +15,8 @@
 // Tile ranges (reference CR/rasterizer_impl.cu:116-138 identifyTileRanges + the memset at :310): one thread per tile finds
 // its list in the sorted keys by binary search -- T searches instead of a pass over all R keys.
 #include "common.hpp"
+#include "stats.hpp"
+#include "switches.hpp"
 #include "tile_cull.hpp"
 
 namespace gsr {
@@ -34,27 +36,24 @@ __device__ __forceinline__ void agent_store(uint64_t* p, uint64_t v)
 // one record per workgroup (no atomics: 190 K same-address atomics quadruple the kernel's time and end up being what is measured)
 constexpr int DUP_REC = 65536;
 __device__ unsigned g_dup_rec[DUP_REC][4];
-#define DUP_T(var) const unsigned long long var = wall_clock64()
-#define DUP_ADD(i, v) do { if (threadIdx.x == 0) { const unsigned r_ = blockIdx.y * gridDim.x + s_ticket; if (r_ < DUP_REC) g_dup_rec[r_][i] = (unsigned)(v); } } while (0)
+// phase i of the record of the workgroup that drew `ticket`
+__device__ __forceinline__ void dup_record(unsigned ticket, int i, unsigned long long ticks)
+{
+    const unsigned r = blockIdx.y * gridDim.x + ticket;
+    if (threadIdx.x == 0 && r < DUP_REC) g_dup_rec[r][i] = (unsigned)ticks;
+}
 int debug_dup_times(unsigned long long* out8, int reset)
 {
-    static unsigned host[DUP_REC][4];
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_dup_rec), sizeof(host)) != hipSuccess) return -1;
+    const auto host = read_wave_records(g_dup_rec, reset);
+    if (!host) return -1;
     for (int i = 0; i < 8; i++) out8[i] = 0;
     for (int r = 0; r < DUP_REC; r++) {
         if (host[r][0] == 0 && host[r][1] == 0) continue;
         for (int i = 0; i < 4; i++) out8[i] += host[r][i];
         out8[4]++;
     }
-    if (reset) {
-        for (int r = 0; r < DUP_REC; r++) for (int i = 0; i < 4; i++) host[r][i] = 0;
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_dup_rec), host, sizeof(host)) != hipSuccess) return -1;
-    }
     return 0;
 }
-#else
-#define DUP_T(var) do { } while (0)
-#define DUP_ADD(i, v) do { } while (0)
 #endif
 
 struct DupArgs {
@@ -70,8 +69,8 @@ struct DupArgs {
     uint32_t* vals;
     size_t b_stride;
     int64_t cap;
-    uint64_t* host_land;             // [V][4] host memory mapped into the device: num_rendered, trap flag, stall flag, - (api.hip)
-    int tickets;                     // common.hpp block_tickets
+    uint64_t* host_land;             // [V][4] host memory mapped into the device: num_rendered, trap flag, stall flag, - (host.hpp HostLanding)
+    int tickets;                     // switches.hpp block_tickets
 };
 
 template <typename KeyT>
@@ -92,14 +91,14 @@ __global__ __launch_bounds__(DUP_THREADS) void k_duplicate(DupArgs a)
     uint64_t* status = at_view(a.dup_status, a.g_stride, view);
     // Which DUP_BLOCK Gaussians this workgroup takes is decided by a ticket drawn when it STARTS (a.tickets, the default): a workgroup
     // with a lower number has started earlier, so the look-back below only ever waits for workgroups that are already running or
-    // done, whatever order the hardware dispatches blockIdx in.  (a.tickets == 0: by blockIdx, common.hpp block_tickets.)
+    // done, whatever order the hardware dispatches blockIdx in.  (a.tickets == 0: by blockIdx, switches.hpp block_tickets.)
     // The ticket word follows the status words.
     const uint32_t nblk = gridDim.x;
-    DUP_T(t0);
+    WALK_T(t0);
     if (threadIdx.x == 0) s_ticket = a.tickets ? (uint32_t)atomicAdd((unsigned long long*)&status[DUP_COPIES * nblk], 1ull) : blockIdx.x;
     __syncthreads();
-    DUP_T(t1);
-    DUP_ADD(0, t1 - t0);
+    WALK_T(t1);
+    WALK_STAT(dup_record(s_ticket, 0, t1 - t0);)
     const uint32_t blk = s_ticket;
     const uint32_t npass = depth_sort_passes(at_view(a.sortctl, a.g_stride, view)[SORTCTL_BITS]);
     const uint32_t* order = at_view((npass & 1u) ? a.order[1] : a.order[0], a.g_stride, view);
@@ -174,8 +173,8 @@ __global__ __launch_bounds__(DUP_THREADS) void k_duplicate(DupArgs a)
     // XCDs), and accesses to ONE line of that kind complete at about one per 50 ns -- the first status lines are read by every
     // workgroup behind them (782 at 800 K Gaussians: 40 us, the whole kernel).  A reader takes copy (its number mod DUP_COPIES).
     if (threadIdx.x < DUP_COPIES) agent_store(&status[threadIdx.x * nblk + blk], word);
-    DUP_T(t2);
-    DUP_ADD(1, t2 - t1);
+    WALK_T(t2);
+    WALK_STAT(dup_record(s_ticket, 1, t2 - t1);)
     // look-back: every preceding workgroup's count (published as count + 1; 0 = not yet).  They were dispatched before
     // this one, so waiting for them cannot deadlock.
     uint64_t part = 0, part_ref = 0;
@@ -232,8 +231,8 @@ __global__ __launch_bounds__(DUP_THREADS) void k_duplicate(DupArgs a)
         }
     }
     __syncthreads();
-    DUP_T(t3);
-    DUP_ADD(2, t3 - t2);
+    WALK_T(t3);
+    WALK_STAT(dup_record(s_ticket, 2, t3 - t2);)
     if (a.keys == nullptr) return;   // count-only call (no binning arena yet)
     KeyT* keys = at_view((KeyT*)a.keys, a.b_stride, view);
     uint32_t* vals = at_view(a.vals, a.b_stride, view);
@@ -320,9 +319,7 @@ __global__ __launch_bounds__(DUP_THREADS) void k_duplicate(DupArgs a)
             }
         }
     }
-#ifdef GSR_STATS
-    if (w == 0) { DUP_T(t4); DUP_ADD(3, t4 - t3); }
-#endif
+    WALK_STAT(if (w == 0) { WALK_T(t4); dup_record(s_ticket, 3, t4 - t3); })
 }
 
 int launch_duplicate(const Launch& L, int P, const Batch& B, int gridx, bool key16, uint64_t* host_land)
@@ -513,18 +510,10 @@ __global__ __launch_bounds__(1024) void k_tile_order(int T, const uint2* __restr
     }
 }
 
-static void order_params(float& knee, float& expo)
-{
-    static const float k = [] { const char* e = getenv("GSR_ORDER_KNEE"); return e ? (float)atof(e) : 2048.f; }();
-    static const float x = [] { const char* e = getenv("GSR_ORDER_EXP"); return e ? (float)atof(e) : 0.3f; }();
-    knee = k;
-    expo = x;
-}
-
 int launch_tile_order(const Launch& L, const Batch& B, int T)
 {
     float knee, expo;
-    order_params(knee, expo);
+    tile_order_params(knee, expo);
     hipLaunchKernelGGL(k_tile_order, dim3(B.V), dim3(1024), 0, L.stream, T, B.iv.ranges, B.iv.tile_order, B.iv_stride, knee, expo);
     return check_launch(L, "tile_order");
 }

@@ -396,7 +396,7 @@ struct Batch {
     size_t gr_stride;
 };
 
-int check_launch(const Launch& L, const char* what);  // api.hip
+int check_launch(const Launch& L, const char* what);  // host.hip (host.hpp has the rest of the host mechanisms)
 
 // preprocess.hip
 int launch_preprocess(const Launch& L, const gsr_params& p, const Batch& B, int* radii);
@@ -430,16 +430,6 @@ constexpr uint32_t CULLED_KEY = 0xFFFFFFFFu;   // depth key of a Gaussian that e
 // number of depth-sort passes a frame with SORTCTL_BITS = bits executes; ids in depth order end up in dval[passes & 1]
 __host__ __device__ inline uint32_t depth_sort_passes(uint32_t bits) { return (bits + RADIX_BITS - 1) / RADIX_BITS; }
 int launch_radix_sort_pairs(const Launch& L, const SortJob& job, bool iota_vals, int end_bit, int* result_buffer, bool key16 = false);
-// How the pair emission, whose workgroups wait for lower-numbered workgroups of the same launch, numbers its workgroups.
-// 1 (default): by a ticket drawn with an atomic when the workgroup STARTS -- a lower number has started earlier, so the
-// waits below can only be for workgroups that are running or done, whatever order the hardware dispatches blockIdx in (HIP promises
-// none; rocPRIM's look-back scans draw tickets for the same reason).  The price: every workgroup of a launch hits ONE address, and
-// same-address atomics from eight XCDs complete at about one per 13-70 ns: 10 us of a single view's 52-us emission.
-// 0 (GSR_TICKETS=0, opt-in): by blockIdx -- correct as long as the hardware hands the workgroups of a launch to each XCD in
-// increasing order (it does today: workgroup i goes to XCD i mod 8, each XCD takes its share in order; the lowest-numbered unfinished
-// workgroup is then always resident or next in line, waits for nothing unfinished, and by induction every wait ends), which is an
-// observation about this part, not a contract.  Every wait is bounded either way (CNT_STALL: the frame fails, it does not hang).
-int block_tickets(int set);
 inline bool tile_keys16(int T) { return T <= 65536; }
 // binning.hip
 int launch_duplicate(const Launch& L, int P, const Batch& B, int gridx, bool key16, uint64_t* host_land);
@@ -471,7 +461,7 @@ struct ExtraGrads {
     float* grad;              // like values: [P][nx] / [V][P][nx] (view_stride) / split: [P][4] ...
     float* grad_hi;           // ... and [V][P][4] (hi_view_stride)
 };
-// fast: the RenderFast kernels (render_math.hpp); the caller decides with forward_fast_math and, for a with_ckpt call, notes it in the
+// fast: the RenderFast kernels (render_math.hpp); the caller decides with forward_fast_math (switches.hpp) and, for a with_ckpt call, notes it in the
 // arena's record, because the backward has to run the same arithmetic
 int launch_render_forward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, float* out_color,
                           bool with_ckpt, bool fast, const ExtraChannels* X = nullptr);
@@ -480,13 +470,6 @@ int launch_render_forward(const Launch& L, const gsr_params& p, const Batch& B, 
 int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, const float* dL_dpix,
                            const ExtraChannels* X = nullptr, const ExtraGrads* XG = nullptr, const RenderBwdDet* D = nullptr,
                            bool fast = false);   // fast: the RenderBwdFast colour kernels (X == NULL only), for saves of a fast forward
-int backward_subquadrant_moments(int set);   // render_bwd.hip: set >= 0 stores; 1 = moments about the sub-quadrant centres
-int forward_half_views(int set);   // render_fwd.hip: set >= 0 stores; returns the views per submission up to which the half-quadrant forward runs
-int render_math(int set);           // render_fwd.hip: 0 / 1 stores, < 0 queries, > 1 is refused; returns the arithmetic mode of the inference forwards (0 exact, 1 fast)
-int train_math(int set);            // render_fwd.hip: the same for the colour forwards that save for a backward (need_backward = 1)
-// which arithmetic a render forward runs: the inference switch without saves, the training switch with them; a channels forward that
-// saves stays exact (the channels backward has no fast variant)
-bool forward_fast_math(bool with_ckpt, bool channels);
 int selftest_mm(hipStream_t stream, float* d_scratch256);   // the matrix-core pixel contraction of the render backward
 // det_backward.hip: the steps of the deterministic backward around the storing render backward, on the scratch plan S
 int launch_det_prepare(const Launch& L, const Batch& B, const DetScratch& S, const uint32_t* point_list, int T);

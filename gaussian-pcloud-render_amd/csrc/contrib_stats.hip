@@ -26,10 +26,9 @@
 // (ds_bpermute through the LDS crossbar), stays selectable for measurements (GSR_CONTRIB_REDUCE=1 in the environment) and gives the
 // same bits: both add the same pairs in the same tree.  dominant_count needs no reduction: (best w, best id) per pixel in registers,
 // one atomic per pixel at the end.
-#include <cstdlib>
-
 #include "common.hpp"
 #include "render_walk.hpp"
+#include "switches.hpp"
 #include "tile_cull.hpp"
 
 namespace gsr {
@@ -212,14 +211,6 @@ __global__ __launch_bounds__(64) void k_contrib_stats(ContribArgs a)
     if (a.dominant_count != nullptr && best_w > 0.f) atomicAdd(a.dominant_count + best_id, 1);
 }
 
-// which lane reduction the kernel runs: GSR_CONTRIB_REDUCE in the environment, read at every call (0 or unset: DPP; 1: shuffle
-// butterflies -- for measurements that alternate the two in one process, same results)
-static int contrib_reduce()
-{
-    const char* e = getenv("GSR_CONTRIB_REDUCE");
-    return (e && atoi(e) == 1) ? 1 : 0;
-}
-
 int launch_contrib_stats(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, const float* pixel_weights,
                          float* weight_sum, float* weight_max, int* pixel_count, int* dominant_count)
 {
@@ -235,7 +226,7 @@ int launch_contrib_stats(const Launch& L, const gsr_params& p, const Batch& B, c
     a.pixel_count = pixel_count;
     a.dominant_count = dominant_count;
     const dim3 grid((unsigned)div_up(a.num_tiles, 8) * 32u * (unsigned)B.V);
-    if (contrib_reduce() == 1) hipLaunchKernelGGL(k_contrib_stats<1>, grid, dim3(64), 0, L.stream, a);
+    if (contrib_lane_reduce() == 1) hipLaunchKernelGGL(k_contrib_stats<1>, grid, dim3(64), 0, L.stream, a);
     else hipLaunchKernelGGL(k_contrib_stats<0>, grid, dim3(64), 0, L.stream, a);
     return check_launch(L, "contrib_stats");
 }

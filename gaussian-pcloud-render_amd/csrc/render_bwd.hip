@@ -27,17 +27,14 @@
 // cases, median of the max-element error) the colour and opacity gradients are as accurate as the reference build's (0.95x /
 // 1.06x), the mean2D / conic gradients carry 1.33x / 2.1x its error (3e-7 / 5e-7 of max|g|; 1.85x / 4.3x with the quadrant-centre
 // moments alone, 1.25x / 2.0x with the sub-quadrant ones everywhere): profiles/r06_bwd_accuracy.txt.
-#include <atomic>
-#include <cstdlib>
-
 #include "common.hpp"
 #include "render_walk.hpp"
+#include "switches.hpp"
 #include "tile_cull.hpp"
 
 namespace gsr {
 
 constexpr int BGRP = 4;  // entries evaluated per inner-loop trip
-constexpr int BWD_SUBQ_DEFAULT = 2;   // which moments the contraction takes unless told otherwise (backward_subquadrant_moments)
 // static grids of more groups of 32 workgroups than this pull their work units instead (launch_render_backward;
 // scripts/debug/bwd_fill_ab.sh builds with other values)
 #ifndef GSR_BWD_FILL
@@ -969,24 +966,6 @@ int debug_bwd_stats(unsigned long long* out8, int reset)
 }
 #endif
 
-// Which moments the contraction takes: 0 about the quadrant centre, 1 about the four sub-quadrant centres (mean2D / conic sums at
-// the reference build's accuracy, for more flush arithmetic), 2 (default) the sub-quadrant ones only for the batches that hold a
-// flagged splat (MODE above).  GSR_BWD_SUBQ in the environment when the library is first used, or gsr_set_backward_moments()
-// (tests, scripts/bwd_accuracy.py).
-static std::atomic<int> g_bwd_subq{-1};
-int backward_subquadrant_moments(int set)
-{
-    if (set >= 0) g_bwd_subq.store(set > 2 ? 2 : set);
-    int v = g_bwd_subq.load();
-    if (v < 0) {
-        const char* e = getenv("GSR_BWD_SUBQ");
-        v = e ? atoi(e) : BWD_SUBQ_DEFAULT;
-        v = v < 0 || v > 2 ? BWD_SUBQ_DEFAULT : v;
-        g_bwd_subq.store(v);
-    }
-    return v;
-}
-
 // the runtime moments mode (backward_subquadrant_moments) as the kernel's compile-time MODE
 template <int NX, typename... XS>
 static void launch_bwd_kernel(dim3 grid, hipStream_t stream, const RenderBwdArgs& a, const XS&... xs)
@@ -1045,7 +1024,7 @@ int launch_render_backward(const Launch& L, const gsr_params& p, const Batch& B,
         else launch_bwd_kernel<8>(grid, L.stream, a, x);
         return check_launch(L, "render_backward_channels");
     }
-    // fast: the arenas' saves were written by the fast forward kernels (api.hip: the arena's record says so), and only a backward that
+    // fast: the arenas' saves were written by the fast forward kernels (host.hpp FrameRecord::math says so), and only a backward that
     // takes that forward's decisions fits them
     const RenderBwdFast F{1u};
     if (D != nullptr) {

@@ -26,12 +26,11 @@
 // k_render_forward<NX>, NX = 4 or 8: the same walk also composites NX extra per-Gaussian channels with the colour's alphas
 // (gsr_forward_batch_channels: the reference's callers render world xyz, a hit map and normals as three more full passes,
 // simple_raw_render.py:410-524).  The extra values ride in the pair records next to the colour; NX = 0 is the plain kernel.
-#include <atomic>
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.hpp"
 #include "render_walk.hpp"
+#include "switches.hpp"
 #include "tile_cull.hpp"
 
 namespace gsr {
@@ -550,59 +549,6 @@ __global__ __launch_bounds__(64) void k_render_forward_half(RenderArgs a, Render
 {
     constexpr bool FAST = true;
 #include "render_fwd_half_body.hpp"
-}
-
-// views per submission up to which the forward runs in half-quadrant mode: GSR_FWD_HALF_V in the environment when the library is
-// first used (default 1; 0: never), or gsr_set_forward_half_views() (tests compare the two kernels in one process)
-static std::atomic<int> g_fwd_half_v{-1};
-int forward_half_views(int set)
-{
-    if (set >= 0) g_fwd_half_v.store(set);
-    int v = g_fwd_half_v.load();
-    if (v < 0) {
-        const char* e = getenv("GSR_FWD_HALF_V");
-        v = e ? atoi(e) : 1;
-        if (v < 0) v = 0;
-        g_fwd_half_v.store(v);
-    }
-    return v;
-}
-
-// arithmetic of the forwards that save nothing for a backward: GSR_RENDER_MATH in the environment when the library is first used
-// (0 exact, the default; 1 fast), or gsr_set_render_math().  set < 0 queries; a value above 1 is refused (the value in force stays).
-static std::atomic<int> g_render_math{-1};
-int render_math(int set)
-{
-    if (set == 0 || set == 1) g_render_math.store(set);
-    int v = g_render_math.load();
-    if (v < 0) {
-        const char* e = getenv("GSR_RENDER_MATH");
-        v = (e && atoi(e) == 1) ? 1 : 0;
-        g_render_math.store(v);
-    }
-    return v;
-}
-
-// arithmetic of the colour forwards that DO save for a backward (need_backward = 1; the backward then runs the matching fast kernels,
-// render_bwd.hip RenderBwdFast): GSR_TRAIN_MATH in the environment when the library is first used (0 exact, the default; 1 fast), or
-// gsr_set_train_math().  Same convention as render_math; neither switch moves the other.
-static std::atomic<int> g_train_math{-1};
-int train_math(int set)
-{
-    if (set == 0 || set == 1) g_train_math.store(set);
-    int v = g_train_math.load();
-    if (v < 0) {
-        const char* e = getenv("GSR_TRAIN_MATH");
-        v = (e && atoi(e) == 1) ? 1 : 0;
-        g_train_math.store(v);
-    }
-    return v;
-}
-
-bool forward_fast_math(bool with_ckpt, bool channels)
-{
-    if (!with_ckpt) return render_math(-1) == 1;
-    return !channels && train_math(-1) == 1;
 }
 
 int launch_render_forward(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, float* out_color,

@@ -1,5 +1,5 @@
 // render_walk.hpp -- what the render kernels (render_fwd.hip: k_render_forward<NX>, k_render_forward_half; render_bwd.hip:
-// k_render_backward<MODE, NX, ...>) share.  All three: the hand-retired prefetch loads, the instrumentation macros and the host
+// k_render_backward<MODE, NX, ...>) share.  All three: the hand-retired prefetch loads, the instrumentation macros (stats.hpp) and the host
 // helpers (the vector types and exp_nonpos come with render_math.hpp).  k_render_forward_half and k_render_backward also the quadrant
 // geometry and the wave maximum; k_render_forward<NX> keeps its own copies of those two, because its machine code moves with the shared ones
 // (profiles/r10_render_walk_refactor.txt, which also records why the gather pipeline itself is still written out per kernel).
@@ -7,6 +7,7 @@
 
 #include "common.hpp"
 #include "render_math.hpp"
+#include "stats.hpp"
 
 namespace gsr {
 
@@ -78,27 +79,5 @@ inline void set_frame_args(ARGS& a, const gsr_params& p, const Batch& B)
     a.V = (uint32_t)B.V;
     a.g_stride = B.g_stride; a.b_stride = B.b_stride; a.iv_stride = B.iv_stride;
 }
-
-// ---- instrumentation (builds with -DGSR_STATS only) ------------------------------------------------------------------------
-// The kernels time their phases and count their work through these two macros, which expand to nothing in the product build, so
-// that the arithmetic can be read without the bookkeeping: WALK_T(t) takes a time stamp (10-ns ticks), WALK_STAT(...) holds
-// declarations or statements of the instrumentation build.
-#ifdef GSR_STATS
-#define WALK_T(var) const unsigned long long var = wall_clock64()
-#define WALK_STAT(...) __VA_ARGS__
-// The host's copy of a per-wave record array (one row of W words per wave of the LAST launch -- same-address atomics from 390 K
-// waves would be what gets measured); with `reset` the device's rows are cleared once they are copied.  NULL: a HIP call failed.
-template <int REC, int W>
-const unsigned (*read_wave_records(unsigned (&dev)[REC][W], int reset))[W]
-{
-    static unsigned host[REC][W], zeros[REC][W];
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(dev), sizeof(host)) != hipSuccess) return nullptr;
-    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(dev), zeros, sizeof(zeros)) != hipSuccess) return nullptr;
-    return host;
-}
-#else
-#define WALK_T(var)
-#define WALK_STAT(...)
-#endif
 
 }  // namespace gsr

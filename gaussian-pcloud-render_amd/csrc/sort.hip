@@ -19,6 +19,7 @@
 // are split evenly over the passes (13 bits -> 7 + 6, not 8 + 5): narrower digits mean fewer ballots
 // and longer, better coalesced runs per workgroup.
 #include "common.hpp"
+#include "stats.hpp"
 
 namespace gsr {
 
@@ -211,27 +212,25 @@ __global__ __launch_bounds__(256) void k_radix_rowscan(uint32_t* __restrict__ hi
 // 0 keys/values loaded, 1 ranking, 2 prefix sums, 3 reorder in LDS, 4 stores issued
 constexpr int SC_REC = 65536;
 __device__ unsigned g_sc_rec[SC_REC][5];
-#define SC_T(var) const unsigned long long var = wall_clock64()
-#define SC_PUT(i, v) do { if (threadIdx.x == 0) { const unsigned r_ = blockIdx.y * gridDim.x + blockIdx.x; if (r_ < SC_REC) g_sc_rec[r_][i] = (unsigned)(v); } } while (0)
+// phase i of the calling workgroup's record
+__device__ __forceinline__ void scatter_record(int i, unsigned long long ticks)
+{
+    const unsigned r = blockIdx.y * gridDim.x + blockIdx.x;
+    if (threadIdx.x == 0 && r < SC_REC) g_sc_rec[r][i] = (unsigned)ticks;
+}
+// out8[0..4]: the phases summed over the workgroups that ran, out8[5]: how many did
 int debug_scatter_times(unsigned long long* out8, int reset)
 {
-    static unsigned host[SC_REC][5];
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_sc_rec), sizeof(host)) != hipSuccess) return -1;
+    const auto host = read_wave_records(g_sc_rec, reset);
+    if (!host) return -1;
     for (int i = 0; i < 8; i++) out8[i] = 0;
     for (int r = 0; r < SC_REC; r++) {
         if (host[r][1] == 0) continue;
         for (int i = 0; i < 5; i++) out8[i] += host[r][i];
         out8[5]++;
     }
-    if (reset) {
-        for (int r = 0; r < SC_REC; r++) for (int i = 0; i < 5; i++) host[r][i] = 0;
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_sc_rec), host, sizeof(host)) != hipSuccess) return -1;
-    }
     return 0;
 }
-#else
-#define SC_T(var) do { } while (0)
-#define SC_PUT(i, v) do { } while (0)
 #endif
 
 // ---- pass kernel 3: stable scatter ----------------------------------------------------------------
@@ -272,7 +271,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_scatter(const KeyT* __rest
     const int64_t seg_base = blk_base + (int64_t)w * (RS_TILE / RS_WAVES);
 
     for (int i = lane; i < RADIX; i += 64) wave_cnt[w][i] = 0;
-    SC_T(t0);
+    WALK_T(t0);
 
     // requested before the keys (loads return in order): see gbase_d below
     const uint32_t tot_d = tid <= mask ? totals[tid] : 0u;
@@ -309,11 +308,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_scatter(const KeyT* __rest
     // of sitting between ranking and reorder (a fifth of the workgroup's life there, scripts/dup_times.py).
     uint32_t gbase_d = block_exclusive_scan_256(tot_d, tmp, nullptr) + hist_d;
     __builtin_amdgcn_wave_barrier();
-#ifdef GSR_STATS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    SC_T(t1);
-    SC_PUT(0, t1 - t0);
+    WALK_STAT(asm volatile("s_waitcnt vmcnt(0)" ::: "memory");)   // (the loads belong to the phase that issued them)
+    WALK_T(t1);
+    WALK_STAT(scatter_record(0, t1 - t0);)
 
     // stable rank inside the wave's segment: order is (j, lane).  peers = the lanes holding my digit: one ballot per digit
     // bit, folded in with one three-input bit operation per half (peers & ~(ballot ^ my bit)); the count of peers below me
@@ -339,8 +336,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_scatter(const KeyT* __rest
         __builtin_amdgcn_wave_barrier();
     }
     __syncthreads();
-    SC_T(t2);
-    SC_PUT(1, t2 - t1);
+    WALK_T(t2);
+    WALK_STAT(scatter_record(1, t2 - t1);)
 
     // digit d = tid: exclusive prefix over waves, workgroup-local and global run starts
     {
@@ -357,8 +354,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_scatter(const KeyT* __rest
         global_base[d] = gbase_d;
     }
     __syncthreads();
-    SC_T(t3);
-    SC_PUT(2, t3 - t2);
+    WALK_T(t3);
+    WALK_STAT(scatter_record(2, t3 - t2);)
 
 #pragma unroll
     for (int j = 0; j < RS_ITEMS; j++) {
@@ -370,8 +367,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_scatter(const KeyT* __rest
         }
     }
     __syncthreads();
-    SC_T(t4);
-    SC_PUT(3, t4 - t3);
+    WALK_T(t4);
+    WALK_STAT(scatter_record(3, t4 - t3);)
 
     const int64_t rem = n - blk_base;
     const uint32_t count = rem < RS_TILE ? (uint32_t)rem : (uint32_t)RS_TILE;
@@ -386,9 +383,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_scatter(const KeyT* __rest
             vals_out[g] = s_val[p];
         }
     }
-#ifdef GSR_STATS
-    { SC_T(t5); SC_PUT(4, t5 - t4); }
-#endif
+    WALK_STAT({ WALK_T(t5); scatter_record(4, t5 - t4); })
 }
 
 // Sorts on key bits [0, end_bit).  job.key[0]/val[0] hold the input (val[0] ignored when iota_vals); the

@@ -20,7 +20,7 @@ import util
 from pcrender import camera, synth
 
 F = np.float32
-MAX_VIEWS = 256                       # api.hip
+MAX_VIEWS = 256                       # host.hpp
 N_SMALL = 96
 MEDIUM_BASE = 100000
 # (V, P, W, H): vpt 4 rows 4+1 | vpt 8 rows 8+4 | vpt 2 exact | vpt = V | vpt 2 rows 2+2+2+1 | vpt 4 rows 4+4+4+1 | vpt 2 rows 8x2+1 |
@@ -240,7 +240,7 @@ def preprocess_vpt(V, P):
 
 
 def tile_sort_passes(T):
-    """api.hip tile_bits / sort.hip: ceil(bit_length(T) / 8) passes over the pairs"""
+    """host.hpp tile_bits / sort.hip: ceil(bit_length(T) / 8) passes over the pairs"""
     return _div_up(int(T).bit_length(), 8)
 
 
