@@ -128,10 +128,7 @@ __global__ __launch_bounds__(DUP_THREADS) void k_duplicate(DupArgs a)
             sp2[g] = __float_as_uint(q3.z);
             if (w3 & SPANS_FLAG) {
                 // row spans: one byte per tile row (first column | columns << 4); the pair count is the sum of the high nibbles
-                const uint32_t a4 = (rc[g].y >> 4) & 0x0F0F0F0Fu, b4 = (sp2[g] >> 4) & 0x0F0F0F0Fu;
-                const uint32_t pa = a4 * 0x01010101u;              // byte i = columns of rows 0..i (<= 60)
-                const uint32_t pb = b4 * 0x01010101u + (pa >> 24) * 0x01010101u;   // rows 0..4+i (<= 120)
-                cnt[g] = pb >> 24;
+                cnt[g] = span_pair_count(rc[g].y, sp2[g]);
                 id[g] |= SPANS_FLAG;                               // travels with the id (ids are < 2^31)
             } else {
                 cnt[g] = sp2[g];
@@ -269,11 +266,8 @@ __global__ __launch_bounds__(DUP_THREADS) void k_duplicate(DupArgs a)
             s_id[w][jslot] = id_g;
             s_rect[w][jslot] = rc_g;
             s_sp2[w][jslot] = sp2_g;
-            if (id_g & SPANS_FLAG) {   // running column counts of the rows, one byte each: slot -> row without walking the rows
-                const uint32_t a4 = (rc_g.y >> 4) & 0x0F0F0F0Fu, b4 = (sp2_g >> 4) & 0x0F0F0F0Fu;
-                const uint32_t pa = a4 * 0x01010101u;
-                s_pre[w][jslot] = make_uint2(pa, b4 * 0x01010101u + (pa >> 24) * 0x01010101u);
-            }
+            // running column counts of the rows, one byte each: slot -> row without walking the rows
+            if (id_g & SPANS_FLAG) s_pre[w][jslot] = span_running_counts(rc_g.y, sp2_g);
         }
         __builtin_amdgcn_wave_barrier();
         const uint32_t my_start = lane < n_nz ? s_off[w][lane] : 0xFFFFFFFFu;   // first slot of the lane-th emitting Gaussian
@@ -298,16 +292,10 @@ __global__ __launch_bounds__(DUP_THREADS) void k_duplicate(DupArgs a)
                 const uint32_t t = rel - s_off[w][owner];
                 uint32_t row, col;
                 if (oid & SPANS_FLAG) {
-                    // t-th tile of the row spans: the row is the number of running counts <= t (a byte-wise compare: count byte
-                    // + 127 - t has its top bit set exactly when the count exceeds t; no carries, the counts are <= 120)
-                    const uint2 pre = s_pre[w][owner];
-                    const uint32_t tt = (127u - t) * 0x01010101u;
-                    const uint32_t xa = (pre.x + tt) & 0x80808080u, xb = (pre.y + tt) & 0x80808080u;
-                    row = 8u - (uint32_t)__popc(xa) - (uint32_t)__popc(xb);
-                    const uint32_t rp = row - 1u;                                     // (row 0: nothing before it)
-                    const uint32_t before = row == 0u ? 0u : (((rp < 4u ? pre.x : pre.y) >> (8u * (rp & 3u))) & 0xFFu);
-                    const uint32_t byte = ((row < 4u ? r.y : s_sp2[w][owner]) >> (8u * (row & 3u))) & 0xFFu;
-                    col = (byte & 15u) + (t - before);
+                    // t-th tile of the row spans (tile_cull.hpp)
+                    uint32_t before;
+                    span_slot_row(s_pre[w][owner], t, row, before);
+                    col = span_slot_col(row < 4u ? r.y : s_sp2[w][owner], row, t, before);
                 } else {
                     const uint32_t width = (r.y & 0xFFFFu) - minx;
                     row = t / width;

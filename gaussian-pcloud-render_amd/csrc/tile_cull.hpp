@@ -20,8 +20,9 @@ namespace gsr {
 
 __host__ __device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 
-// The two hardware approximations of the footprint test, 1 ulp each on the device (v_rcp_f32, v_log_f32); the host build, which
-// exists for the test of the bound's algebra (tests/footprint_bound_main.cpp), takes the plain forms.
+// The hardware approximations of the footprint test and of the row spans, 1 ulp each on the device (v_rcp_f32, v_log_f32,
+// v_sqrt_f32); the host build, which exists for the tests of the algebra (tests/footprint_bound_main.cpp,
+// tests/footprint_clip_main.cpp), takes the plain forms.
 __host__ __device__ __forceinline__ float cull_rcp(float x)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -36,6 +37,14 @@ __host__ __device__ __forceinline__ float cull_log2(float x)
     return __builtin_amdgcn_logf(x);
 #else
     return log2f(x);
+#endif
+}
+__host__ __device__ __forceinline__ float cull_sqrt(float x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_sqrtf(x);
+#else
+    return sqrtf(x);
 #endif
 }
 
@@ -115,10 +124,10 @@ __device__ __forceinline__ bool may_touch_8x8(float mx, float my, float A, float
 // *spans_valid = false: rectangle too large for the encoding (or not clipped at all): every tile of rect is emitted.
 constexpr uint32_t SPAN_ROWS = 8;
 constexpr uint32_t SPANS_FLAG = 0x80000000u;   // in the fourth word of Splat::q3 (reference pair counts are < 2^27: api.hip check_params)
-__device__ __forceinline__ uint32_t clip_rect_to_footprint(float px, float py, float sxx, float sxy, float syy, float det,
-                                                            float A, float B, float C, float o, float r, uint2& rect,
-                                                            uint32_t gridx, uint32_t gridy, uint2* spans = nullptr,
-                                                            bool* spans_valid = nullptr)
+__host__ __device__ __forceinline__ uint32_t clip_rect_to_footprint(float px, float py, float sxx, float sxy, float syy, float det,
+                                                                     float A, float B, float C, float o, float r, uint2& rect,
+                                                                     uint32_t gridx, uint32_t gridy, uint2* spans = nullptr,
+                                                                     bool* spans_valid = nullptr)
 {
     if (spans_valid) *spans_valid = false;
     uint32_t minx = rect.x & 0xFFFFu, miny = rect.x >> 16, maxx = rect.y & 0xFFFFu, maxy = rect.y >> 16;
@@ -137,7 +146,7 @@ __device__ __forceinline__ uint32_t clip_rect_to_footprint(float px, float py, f
     const float lim = 4.0e6f;
     const float x_lo = fminf(fmaxf(ceilf(px - hx), -lim), lim), x_hi = fminf(fmaxf(floorf(px + hx), -lim), lim);
     const float y_lo = fminf(fmaxf(ceilf(py - hy), -lim), lim), y_hi = fminf(fmaxf(floorf(py + hy), -lim), lim);
-    if (!(x_lo == x_lo && x_hi == x_hi && y_lo == y_lo && y_hi == y_hi)) return full;   // NaN mean
+    if (!(px == px && py == py)) return full;   // NaN mean (asked of the mean itself: the clamps above turn a NaN into -lim)
     const int tx0 = (int)floorf(x_lo * (1.0f / 16.0f)), tx1 = (int)floorf(x_hi * (1.0f / 16.0f)) + 1;
     const int ty0 = (int)floorf(y_lo * (1.0f / 16.0f)), ty1 = (int)floorf(y_hi * (1.0f / 16.0f)) + 1;
     const uint32_t cx0 = tx0 < 0 ? 0u : ((uint32_t)tx0 > gridx ? gridx : (uint32_t)tx0);
@@ -168,13 +177,13 @@ __device__ __forceinline__ uint32_t clip_rect_to_footprint(float px, float py, f
     const float hyc = hy_raw + 0.02f;
     float d_raw = py - ((float)(miny * 16u) - 0.5f);                                    // dy at the upper boundary of row 0
     float d_hi = fminf(fmaxf(d_raw, -hyc), hyc);
-    float w_b = __builtin_amdgcn_sqrtf(v * fmaxf(k - d_hi * d_hi * inv_syy, 0.f) + root_pad);
+    float w_b = cull_sqrt(v * fmaxf(k - d_hi * d_hi * inv_syy, 0.f) + root_pad);
     float er_hi = -slope * d_hi + w_b, el_hi = slope * d_hi + w_b;                      // (pixel x - px) and (px - pixel x) there
     const int iminx = (int)minx, imaxx = (int)maxx;
     for (uint32_t row = 0; row < h; row++) {
         d_raw -= 16.0f;                                                                 // the next boundary: 16 pixel rows further down
         const float d_lo = fminf(fmaxf(d_raw, -hyc), hyc);
-        const float w_n = __builtin_amdgcn_sqrtf(v * fmaxf(k - d_lo * d_lo * inv_syy, 0.f) + root_pad);
+        const float w_n = cull_sqrt(v * fmaxf(k - d_lo * d_lo * inv_syy, 0.f) + root_pad);
         const float er_lo = -slope * d_lo + w_n, el_lo = slope * d_lo + w_n;
         float right = fmaxf(er_hi, er_lo), left = fmaxf(el_hi, el_lo);
         if (-dstar >= d_lo - 0.05f && -dstar <= d_hi + 0.05f) right = fmaxf(right, hx_raw);
@@ -192,6 +201,48 @@ __device__ __forceinline__ uint32_t clip_rect_to_footprint(float px, float py, f
     *spans = make_uint2(lo, hi);
     *spans_valid = true;
     return total;
+}
+
+// ---- reading the row spans back (pair emission, binning.hip k_duplicate) ----------------------------------------------
+// (lo, hi) = the two span words: the bytes of rows 0-3 and of rows 4-7.  All of it is byte-parallel arithmetic on the two words;
+// the host build is for tests/footprint_clip_main.cpp.
+// Running column counts, one byte each: byte i of .x = columns of rows 0..i (<= 60), byte i of .y = columns of rows 0..4+i (<= 120).
+__host__ __device__ __forceinline__ uint2 span_running_counts(uint32_t lo, uint32_t hi)
+{
+    const uint32_t a4 = (lo >> 4) & 0x0F0F0F0Fu, b4 = (hi >> 4) & 0x0F0F0F0Fu;
+    const uint32_t pa = a4 * 0x01010101u;
+    return make_uint2(pa, b4 * 0x01010101u + (pa >> 24) * 0x01010101u);
+}
+// The pair count: the sum of the high nibbles.
+__host__ __device__ __forceinline__ uint32_t span_pair_count(uint32_t lo, uint32_t hi)
+{
+    return span_running_counts(lo, hi).y >> 24;
+}
+__host__ __device__ __forceinline__ uint32_t span_popc(uint32_t x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)__popc(x);
+#else
+    return (uint32_t)__builtin_popcount(x);
+#endif
+}
+// The t-th tile of the spans in row-major order (t < span_pair_count) -> (row, column relative to the rectangle's first column),
+// in two steps, so that the caller fetches only the span word that holds the row (lo for rows 0-3, hi for rows 4-7).
+// pre = span_running_counts(lo, hi).  The row is the number of running counts <= t (a byte-wise compare: count byte + 127 - t has
+// its top bit set exactly when the count exceeds t; no carries, the counts are <= 120); before = the tiles of the rows above it.
+__host__ __device__ __forceinline__ void span_slot_row(uint2 pre, uint32_t t, uint32_t& row, uint32_t& before)
+{
+    const uint32_t tt = (127u - t) * 0x01010101u;
+    const uint32_t xa = (pre.x + tt) & 0x80808080u, xb = (pre.y + tt) & 0x80808080u;
+    row = 8u - span_popc(xa) - span_popc(xb);
+    const uint32_t rp = row - 1u;                                     // (row 0: nothing before it)
+    before = row == 0u ? 0u : (((rp < 4u ? pre.x : pre.y) >> (8u * (rp & 3u))) & 0xFFu);
+}
+// word = the span word of `row` (row < 4 ? lo : hi)
+__host__ __device__ __forceinline__ uint32_t span_slot_col(uint32_t word, uint32_t row, uint32_t t, uint32_t before)
+{
+    const uint32_t byte = (word >> (8u * (row & 3u))) & 0xFFu;
+    return (byte & 15u) + (t - before);
 }
 
 // Bounding rectangle, in lane coordinates (x = lane & 7, y = lane >> 3), of the lanes set in a ballot of an 8x8
