@@ -26,6 +26,7 @@
 
 #include "common.hpp"
 #include "host.hpp"
+#include "image_loss.hpp"
 #include "switches.hpp"
 
 namespace gsr {
@@ -734,6 +735,74 @@ int gsr_contrib_stats(const gsr_params* p, int V, const int* radii, const void* 
     }
     return launch_contrib_stats(L, *p, B, B.b.val[sorted_buffer(tile_count(p))], pixel_weights, weight_sum, weight_max, pixel_count,
                                 dominant_count);
+}
+
+// ---- the photometric loss and its gradient with respect to the frames (image_loss.hip) ----
+// checks 1 and 2 of the two entries, which the size query shares (what == NULL: no message, the query just answers 0)
+static int image_loss_sizes(const char* what, int V, int W, int H, int ss)
+{
+    if (V < 1 || V > MAX_VIEWS) return what ? fail(GSR_ERR_INVALID, "[gsr] %s: view count %d outside 1..%d", what, V, MAX_VIEWS) : GSR_ERR_INVALID;
+    // (64-bit steps that cannot wrap: W H < 2^62, then 3 V W H < 2^41, then the rate's square)
+    const int64_t lim = 1ll << 31, wh = W >= 1 && H >= 1 ? (int64_t)W * (int64_t)H : lim, s2 = (int64_t)ss * (int64_t)ss;
+    const int64_t n = wh < lim ? 3 * (int64_t)V * wh : lim;
+    if (n >= lim || s2 >= lim || n * (s2 > 0 ? s2 : 1) >= lim || il_parts(W, H) >= (1ll << 24))
+        return what ? fail(GSR_ERR_INVALID, "[gsr] %s: bad sizes W=%d H=%d (both >= 1, 3 V H W ss^2 = 3 x %d x %d x %d x %d^2 below 2^31, at most "
+                           "2^24 tiles x channels)", what, W, H, V, H, W, ss) : GSR_ERR_INVALID;
+    return GSR_OK;
+}
+
+// checks 3 and 4
+static int image_loss_rate_lambda(const char* what, int ss, float lambda)
+{
+    if (ss != 1 && ss != 2)
+        return fail(GSR_ERR_INVALID, "[gsr] %s: super-sample rate %d is not supported: rate 1 compares the frames as they are, rate 2 is the "
+                    "mean of every 2 x 2 block (the bilinear down-filter at that rate); other rates stay with the caller, who down-filters "
+                    "first and passes ss = 1", what, ss);
+    if (!(lambda >= 0.f && lambda <= 1.f)) return fail(GSR_ERR_INVALID, "[gsr] %s: lambda_dssim = %g outside 0..1", what, (double)lambda);
+    return GSR_OK;
+}
+
+size_t gsr_image_loss_state_bytes(int V, int W, int H)
+{
+    if (image_loss_sizes(nullptr, V, W, H, 1) != GSR_OK) return 0;
+    return image_loss_state(nullptr, V, W, H).bytes;
+}
+
+int gsr_image_loss_forward(int V, int W, int H, int ss, float lambda_dssim, const float* image, const float* target, float* loss_terms,
+                           void* state, size_t state_bytes, gsr_stream_t stream)
+{
+    const char* who = "image_loss_forward";
+    if (int e = image_loss_sizes(who, V, W, H, ss)) return e;
+    if (int e = image_loss_rate_lambda(who, ss, lambda_dssim)) return e;
+    if (!image || !target || !loss_terms) return fail(GSR_ERR_INVALID, "[gsr] %s: image, target or loss_terms is NULL", who);
+    ImageLossState S{nullptr, nullptr, 0};
+    if (state) {
+        S = image_loss_state(align256(state), V, W, H);
+        if (state_bytes < S.bytes)
+            return fail(GSR_ERR_CAPACITY, "[gsr] %s: state block too small (%zu < %zu = gsr_image_loss_state_bytes(%d, %d, %d))", who,
+                        state_bytes, S.bytes, V, W, H);
+    }
+    const Launch L{(hipStream_t)stream, 0};
+    const ImageLossArgs a{V, W, H, ss, image, target};
+    ProfScope ps("image_loss_fwd", L.stream);
+    return launch_image_loss_forward(L, a, lambda_dssim, loss_terms, S.partials, S.maps);
+}
+
+int gsr_image_loss_backward(int V, int W, int H, int ss, float lambda_dssim, const float* image, const float* target,
+                            const float* dL_dloss, const void* state, size_t state_bytes, float* dL_dimage, gsr_stream_t stream)
+{
+    const char* who = "image_loss_backward";
+    if (int e = image_loss_sizes(who, V, W, H, ss)) return e;
+    if (int e = image_loss_rate_lambda(who, ss, lambda_dssim)) return e;
+    if (!image || !target || !dL_dimage || !state) return fail(GSR_ERR_INVALID, "[gsr] %s: image, target, dL_dimage or state is NULL", who);
+    const ImageLossState S = image_loss_state(align256(const_cast<void*>(state)), V, W, H);
+    if (state_bytes < S.bytes)
+        return fail(GSR_ERR_CAPACITY, "[gsr] %s: state block too small (%zu < %zu = gsr_image_loss_state_bytes(%d, %d, %d))", who,
+                    state_bytes, S.bytes, V, W, H);
+    const Launch L{(hipStream_t)stream, 0};
+    const ImageLossArgs a{V, W, H, ss, image, target};
+    ProfScope ps("image_loss_bwd", L.stream);
+    return launch_image_loss_backward(L, a, lambda_dssim, dL_dloss, S.maps, dL_dimage);
 }
 
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,

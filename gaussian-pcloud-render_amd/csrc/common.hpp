@@ -523,6 +523,20 @@ int launch_view_stats(const Launch& L, int P, const Batch& B, const int* radii, 
 int launch_contrib_stats(const Launch& L, const gsr_params& p, const Batch& B, const uint32_t* point_list, const float* pixel_weights,
                          float* weight_sum, float* weight_max, int* pixel_count, int* dominant_count);
 
+// image_loss.hip (tile geometry and state layout: image_loss.hpp): the photometric loss (1 - lambda) L1 +
+// lambda (1 - SSIM) per view and its gradient with respect to the rendered frames.  Forward: one launch of a workgroup per (tile,
+// channel, view) that stores the three derivative maps and its three partial sums, then one launch of a workgroup per view that adds the
+// partials by index.  partials == NULL: the metrics-only forward, one launch of ONE workgroup per view that walks the view's tiles in
+// the same order (nothing is stored but loss_terms; same bits).  Backward: one launch.
+struct ImageLossArgs {
+    int V, W, H, ss;       // W, H: the loss's (= the target's) resolution; the frames are ss times as large each way
+    const float* image;    // [V][3][H ss][W ss]
+    const float* target;   // [V][3][H][W]
+};
+int launch_image_loss_forward(const Launch& L, const ImageLossArgs& a, float lambda, float* loss_terms, double* partials, float* maps);
+int launch_image_loss_backward(const Launch& L, const ImageLossArgs& a, float lambda, const float* dL_dloss, const float* maps,
+                               float* dL_dimage);
+
 // device helper: clear [p, p + bytes) (16-B aligned, multiple of 16) with the calling grid's threads
 __device__ __forceinline__ void zero_region(char* p, size_t bytes, size_t gtid, size_t nthreads)
 {

@@ -67,6 +67,9 @@ _DECL = {
     "gsr_backward_cameras": (_int, [_pp, _int, _fp, _fp, _size, _fp, _fp, _fp, _fp, _size, _fp]),
     "gsr_backward_view_stats": (_int, [_pp, _int, _fp, _fp, _size, _int, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "gsr_contrib_stats": (_int, [_pp, _int, _fp] + _ARENAS + [_fp, _int, _fp, _fp, _fp, _fp, _fp]),
+    "gsr_image_loss_state_bytes": (_size, [_int, _int, _int]),
+    "gsr_image_loss_forward": (_int, [_int, _int, _int, _int, C.c_float, _fp, _fp, _fp, _fp, _size, _fp]),
+    "gsr_image_loss_backward": (_int, [_int, _int, _int, _int, C.c_float, _fp, _fp, _fp, _fp, _size, _fp, _fp]),
     "gsr_mark_visible": (_int, [_int, _fp, _fp, _fp, _fp, _fp]),
     "gsr_query": (_int, [_pp, _int, _fp, _fp, _size, _fp, _i64, _fp, _size, _fp]),
     "gsr_set_profiling": (None, [_int]),
@@ -990,6 +993,59 @@ def contrib_stats(background, means3D, radii, colors, scales, rotations, scale_m
                                          _stream_handle(device)))
             del keep, pw
     return None
+
+
+def _loss_frames(who, image, target, super_sample):
+    """(device, V, W, H, ss) of an image-loss call: float32 contiguous HIP tensors, image [V,3,H ss,W ss] and target [V,3,H,W]"""
+    device = image.device
+    _require_hip(device)
+    ss = int(super_sample)
+    for t, name in ((image, "image"), (target, "target")):
+        if t.dtype != _F32 or t.dim() != 4 or t.shape[1] != 3 or t.device != device or not t.is_contiguous():
+            raise RuntimeError("%s: %s must be a contiguous float32 [V,3,H,W] tensor on %s (got %s %s on %s)"
+                               % (who, name, device, t.dtype, tuple(t.shape), t.device))
+    V, _, H, W = target.shape
+    if tuple(image.shape) != (V, 3, H * ss, W * ss):
+        raise RuntimeError("%s: image is %s, the target %s at super_sample = %d needs %s"
+                           % (who, tuple(image.shape), tuple(target.shape), ss, (V, 3, H * ss, W * ss)))
+    return device, V, W, H, ss
+
+
+def image_loss_state(V, W, H, device):
+    """a state block for image_loss_forward / image_loss_backward (C ABI gsr_image_loss_state_bytes)"""
+    return torch.empty(int(lib.gsr_image_loss_state_bytes(V, W, H)), dtype=torch.uint8, device=device)
+
+
+def image_loss_forward(image, target, lambda_dssim, super_sample=1, state=None):
+    """C ABI gsr_image_loss_forward: the [V,4] loss terms (L1, SSIM, MSE, (1 - lambda) L1 + lambda (1 - SSIM)) of the frames `image`
+    against `target`.  state: a block of image_loss_state the backward reads afterwards, or None (metrics only)."""
+    device, V, W, H, ss = _loss_frames("image_loss_forward", image, target, super_sample)
+    terms = torch.empty((V, 4), dtype=_F32, device=device)
+    with _on_device(device):
+        _check(lib.gsr_image_loss_forward(V, W, H, ss, float(lambda_dssim), image.data_ptr(), target.data_ptr(), terms.data_ptr(),
+                                          None if state is None else state.data_ptr(), 0 if state is None else state.numel(),
+                                          _stream_handle(device)))
+    return terms
+
+
+def image_loss_backward(image, target, lambda_dssim, super_sample, state, dL_dloss=None, out=None):
+    """C ABI gsr_image_loss_backward after image_loss_forward with the same arguments and state: dL/d image, shaped like image.
+    dL_dloss: float32 [V] on the device, or None for 1 per view.  out: the tensor to write into (every element is written)."""
+    device, V, W, H, ss = _loss_frames("image_loss_backward", image, target, super_sample)
+    if dL_dloss is not None:
+        if dL_dloss.dtype != _F32 or tuple(dL_dloss.shape) != (V,) or dL_dloss.device != device:
+            raise RuntimeError("image_loss_backward: dL_dloss must be a float32 [%d] tensor on %s (got %s %s on %s)"
+                               % (V, device, dL_dloss.dtype, tuple(dL_dloss.shape), dL_dloss.device))
+        dL_dloss = dL_dloss.contiguous()
+    if out is None:
+        out = torch.empty_like(image)
+    elif out.dtype != _F32 or out.shape != image.shape or out.device != device or not out.is_contiguous():
+        raise RuntimeError("image_loss_backward: out must be a contiguous float32 tensor shaped like image on %s" % device)
+    with _on_device(device):
+        _check(lib.gsr_image_loss_backward(V, W, H, ss, float(lambda_dssim), image.data_ptr(), target.data_ptr(), _ptr(dL_dloss),
+                                           None if state is None else state.data_ptr(), 0 if state is None else state.numel(),
+                                           out.data_ptr(), _stream_handle(device)))
+    return out
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,

@@ -382,6 +382,43 @@ int gsr_contrib_stats(const gsr_params* p, int V, const int* radii /* [V][P], ma
                       float* weight_max /* [P] or NULL */, int* pixel_count /* [P] or NULL */, int* dominant_count /* [P] or NULL */,
                       gsr_stream_t stream);
 
+/* Photometric loss of the rendered frames and its gradient: per view v, loss = (1 - lambda) L1 + lambda (1 - SSIM), the loss nearly
+ * every Gaussian-splat trainer uses, evaluated in HIP from the frames exactly as the forwards return them (out_color: [V][3][..][..],
+ * planar), so that dL_dimage is what gsr_backward_batch takes as dL_dpix.  W and H are the resolution of the loss, which is the
+ * target's; the frames are ss times as large each way.
+ *   Definition, per view and channel.  x = image for ss = 1; for ss = 2, x = ((i00 + i01) + (i10 + i11)) * 0.25 over each 2 x 2 block
+ * (what a bilinear down-filter with align_corners = false does at rate 2).  y = target.  w = the normalised 11 x 11 Gaussian window,
+ * sigma 1.5, separable: g[k] ~ exp(-(k - 5)^2 / 4.5).  conv = correlation with w under zero padding of 5.  mu1 = conv(x), mu2 = conv(y),
+ * s1 = conv(x x) - mu1^2, s2 = conv(y y) - mu2^2, s12 = conv(x y) - mu1 mu2, C1 = 1e-4, C2 = 9e-4,
+ * m = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)).
+ *   loss_terms[v] = { mean |x - y|,  mean m,  mean (x - y)^2,  (1 - lambda) [0] + lambda (1 - [1]) }, means over the 3 H W values of
+ * the view; [3] is formed from the float32 values [0] and [1] with one rounding.
+ *   dL_dimage = dL_dloss[v] * d loss_terms[v][3] / d image (dL_dloss NULL: 1 for every view): the L1 part is
+ * (1 - lambda) sign(x - y) / (3 H W) with sign(0) = 0; the SSIM part is -lambda / (3 H W) (conv(A) + 2 x conv(B) + y conv(C)) with the
+ * three maps A = dm/dmu1 - 2 mu1 B - mu2 C, B = dm/ds1, C = dm/ds12 the forward saved; with ss = 2 each of the four source pixels
+ * receives a quarter.  Every element of dL_dimage is written.  image == target gives an L1 part and an SSIM part of exactly 0.
+ *   state: a caller-owned device block of at least gsr_image_loss_state_bytes(V, W, H) bytes, opaque (the three maps, 36 B per loss
+ * pixel, and the workgroups' partial sums).  The size query is a pure host function; its result is a multiple of 256, does not
+ * decrease in any argument, and is 0 for sizes the forward refuses.  state = NULL in the forward: metrics only -- loss_terms is
+ * written, with the same bits as a call with a state block, by ONE workgroup per view (there is nowhere to keep partial sums: the call
+ * is as slow as one compute unit per view; pass a state block where the time matters).  The backward is valid any number of times
+ * after a forward with the same V, W, H, ss, lambda, image, target and state; that it follows such a forward is the CALLER'S duty:
+ * the library keeps no record of it and cannot refuse a backward on a block some other forward wrote.
+ *   Nothing is read back from the device, no host wait is made, nothing is allocated.  No float atomics: every workgroup stores its
+ * three sums as float64 into the state block and a second small launch adds a view's partials by index and rounds once, so all
+ * outputs are bit-identical from call to call, and view v of a batch is bit-identical to the same view submitted alone.
+ *   Refused, in this order, before any device call: V outside 1..256; W or H < 1, or 3 V H W ss^2 >= 2^31 (or more than 2^24
+ * tiles x channels per view); ss other than 1 and 2 (GSR_ERR_INVALID: other rates are never approximated -- down-filter first and
+ * pass ss = 1); lambda outside 0..1 or NaN; a NULL image, target, loss_terms, dL_dimage, or (backward) state: GSR_ERR_INVALID; a state
+ * block that is too small: GSR_ERR_CAPACITY, the message names the size needed. */
+size_t gsr_image_loss_state_bytes(int V, int W, int H);
+int gsr_image_loss_forward(int V, int W, int H, int ss, float lambda_dssim, const float* image /* [V][3][H ss][W ss] */,
+                           const float* target /* [V][3][H][W] */, float* loss_terms /* [V][4] */, void* state /* or NULL */,
+                           size_t state_bytes, gsr_stream_t stream);
+int gsr_image_loss_backward(int V, int W, int H, int ss, float lambda_dssim, const float* image, const float* target,
+                            const float* dL_dloss /* [V] or NULL */, const void* state, size_t state_bytes,
+                            float* dL_dimage /* [V][3][H ss][W ss] */, gsr_stream_t stream);
+
 /* Pairs in the lists of the calling thread's last forward call, per view (out[V], HOST array): what a binning arena has to
  * hold.  Equal to num_rendered with reference_lists = 1. */
 int gsr_last_list_pairs(int64_t* out, int V);
