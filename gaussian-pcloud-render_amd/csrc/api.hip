@@ -21,9 +21,11 @@
 // GSR_RETRY with the true counts and the caller repeats the binning half with a larger arena (resume = 1).
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
+#include "adam_step.hpp"
 #include "common.hpp"
 #include "host.hpp"
 #include "image_loss.hpp"
@@ -803,6 +805,74 @@ int gsr_image_loss_backward(int V, int W, int H, int ss, float lambda_dssim, con
     const ImageLossArgs a{V, W, H, ss, image, target};
     ProfScope ps("image_loss_bwd", L.stream);
     return launch_image_loss_backward(L, a, lambda_dssim, dL_dloss, S.maps, dL_dimage);
+}
+
+// ---- the optimizer step (adam_step.hip): every refusal precedes the first device call ----
+int gsr_visible_from_radii(int V, int P, const int32_t* radii, uint8_t* visible, gsr_stream_t stream)
+{
+    const char* who = "visible_from_radii";
+    if (V < 1 || V > MAX_VIEWS) return fail(GSR_ERR_INVALID, "[gsr] %s: view count %d outside 1..%d", who, V, MAX_VIEWS);
+    if (P < 1 || (int64_t)V * (int64_t)P >= (1ll << 31))
+        return fail(GSR_ERR_INVALID, "[gsr] %s: bad sizes P=%d (at least 1, V P = %d x %d below 2^31)", who, P, V, P);
+    if (!radii || !visible) return fail(GSR_ERR_INVALID, "[gsr] %s: radii or visible is NULL", who);
+    const Launch L{(hipStream_t)stream, 0};
+    ProfScope ps("visible_from_radii", L.stream);
+    return launch_visible_from_radii(L, V, P, radii, visible);
+}
+
+int gsr_adam_step(int P, int G, const gsr_adam_group* groups, int64_t t, float beta1, float beta2, float eps, const uint8_t* visible,
+                  int zero_grads, gsr_stream_t stream)
+{
+    const char* who = "adam_step";
+    if (G < 1 || G > ADAM_MAX_GROUPS) return fail(GSR_ERR_INVALID, "[gsr] %s: group count %d outside 1..%d", who, G, ADAM_MAX_GROUPS);
+    // (the table is read for its sizes before its pointers are judged: a NULL table has no sizes to refuse and falls to the last check)
+    if (P < 1) return fail(GSR_ERR_INVALID, "[gsr] %s: bad sizes P=%d (at least 1)", who, P);
+    for (int k = 0; groups && k < G; k++)
+        if (groups[k].width < 1 || (int64_t)P * (int64_t)groups[k].width >= (1ll << 31))
+            return fail(GSR_ERR_INVALID, "[gsr] %s: bad sizes in group %d: width %d (at least 1, P width = %d x %d below 2^31)", who, k,
+                        groups[k].width, P, groups[k].width);
+    if (t < 1) return fail(GSR_ERR_INVALID, "[gsr] %s: step count t = %lld (the first step is t = 1)", who, (long long)t);
+    if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f))
+        return fail(GSR_ERR_INVALID, "[gsr] %s: beta1 = %g, beta2 = %g outside [0, 1)", who, (double)beta1, (double)beta2);
+    if (!(eps > 0.f) || !std::isfinite(eps)) return fail(GSR_ERR_INVALID, "[gsr] %s: eps = %g is not a positive finite number", who, (double)eps);
+    for (int k = 0; groups && k < G; k++)
+        if (!(groups[k].lr >= 0.f) || !std::isfinite(groups[k].lr))
+            return fail(GSR_ERR_INVALID, "[gsr] %s: learning rate %g of group %d is negative or not finite", who, (double)groups[k].lr, k);
+    if (!groups) return fail(GSR_ERR_INVALID, "[gsr] %s: groups is NULL", who);
+    for (int k = 0; k < G; k++)
+        if (!groups[k].param || !groups[k].grad || !groups[k].exp_avg || !groups[k].exp_avg_sq)
+            return fail(GSR_ERR_INVALID, "[gsr] %s: param, grad, exp_avg or exp_avg_sq of group %d is NULL", who, k);
+
+    AdamTable T;
+    std::memset(&T, 0, sizeof(T));
+    T.G = G;
+    T.b1 = beta1;
+    T.b2 = beta2;
+    T.c1 = 1.0f - beta1;
+    T.c2 = 1.0f - beta2;
+    T.eps = eps;
+    T.rsq2 = (float)(1.0 / std::sqrt(1.0 - std::pow((double)beta2, (double)t)));
+    T.zero_grads = zero_grads != 0;
+    const double bias1 = 1.0 - std::pow((double)beta1, (double)t);
+    int64_t units = 0;
+    for (int k = 0; k < G; k++) units += div_up((int64_t)P * groups[k].width, ADAM_BLOCK_ELEMS);
+    uint32_t end = 0;
+    for (int k = 0; k < G; k++) {
+        const gsr_adam_group& s = groups[k];
+        AdamGroupDev& d = T.g[k];
+        d.param = s.param;
+        d.grad = s.grad;
+        d.exp_avg = s.exp_avg;
+        d.exp_avg_sq = s.exp_avg_sq;
+        d.n = (uint32_t)((int64_t)P * s.width);
+        d.width = (uint32_t)s.width;
+        d.block_end = end += adam_group_blocks(d.n, units);
+        d.vec = (((uintptr_t)s.param | (uintptr_t)s.grad | (uintptr_t)s.exp_avg | (uintptr_t)s.exp_avg_sq) & 15u) == 0;
+        d.step = (float)((double)s.lr / bias1);
+    }
+    const Launch L{(hipStream_t)stream, 0};
+    ProfScope ps("adam_step", L.stream);
+    return launch_adam_step(L, T, visible);
 }
 
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,

@@ -70,6 +70,8 @@ _DECL = {
     "gsr_image_loss_state_bytes": (_size, [_int, _int, _int]),
     "gsr_image_loss_forward": (_int, [_int, _int, _int, _int, C.c_float, _fp, _fp, _fp, _fp, _size, _fp]),
     "gsr_image_loss_backward": (_int, [_int, _int, _int, _int, C.c_float, _fp, _fp, _fp, _fp, _size, _fp, _fp]),
+    "gsr_visible_from_radii": (_int, [_int, _int, _fp, _fp, _fp]),
+    "gsr_adam_step": (_int, [_int, _int, _fp, _i64, C.c_float, C.c_float, C.c_float, _fp, _int, _fp]),
     "gsr_mark_visible": (_int, [_int, _fp, _fp, _fp, _fp, _fp]),
     "gsr_query": (_int, [_pp, _int, _fp, _fp, _size, _fp, _i64, _fp, _size, _fp]),
     "gsr_set_profiling": (None, [_int]),
@@ -1046,6 +1048,71 @@ def image_loss_backward(image, target, lambda_dssim, super_sample, state, dL_dlo
                                            None if state is None else state.data_ptr(), 0 if state is None else state.numel(),
                                            out.data_ptr(), _stream_handle(device)))
     return out
+
+
+class AdamGroup(C.Structure):
+    """gsr_adam_group of include/gsr.h"""
+    _fields_ = [("param", _fp), ("grad", _fp), ("exp_avg", _fp), ("exp_avg_sq", _fp), ("width", C.c_int), ("lr", C.c_float)]
+
+
+ADAM_MAX_GROUPS = 8
+
+
+def visible_from_radii(radii, out=None):
+    """C ABI gsr_visible_from_radii: the uint8 [P] mask any_v(radii[v] > 0) of the int32 radii [V,P] (or [P]) a rasterize call returned.
+    out: the tensor to write into (every element is written)."""
+    if radii.dtype != torch.int32 or radii.dim() not in (1, 2) or not radii.is_contiguous():
+        raise ValueError("visible_from_radii: radii must be a contiguous int32 [V,P] or [P] tensor (got %s %s)"
+                         % (radii.dtype, tuple(radii.shape)))
+    V, P = (1, radii.shape[0]) if radii.dim() == 1 else radii.shape
+    if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (P,) or not out.is_contiguous() or out.device != radii.device):
+        raise ValueError("visible_from_radii: out must be a contiguous uint8 [%d] tensor on %s (got %s %s on %s)"
+                         % (P, radii.device, out.dtype, tuple(out.shape), out.device))
+    device = radii.device
+    _require_hip(device)
+    if out is None:
+        out = torch.empty((P,), dtype=torch.uint8, device=device)
+    with _on_device(device):
+        _check(lib.gsr_visible_from_radii(V, P, radii.data_ptr(), out.data_ptr(), _stream_handle(device)))
+    return out
+
+
+def adam_step(groups, t, beta1, beta2, eps, visible=None, zero_grads=False):
+    """C ABI gsr_adam_step: one Adam step, number t (1 for the first), of every group in ONE launch, in place.  groups: a list of 1..8
+    (param, grad, exp_avg, exp_avg_sq, lr), the four of them contiguous float32 tensors of one shape [P, ...] on one HIP device, P common
+    to all groups.  visible: a uint8 [P] mask (rows with 0 keep the bits of param and both moments) or None for a dense step.
+    zero_grads: every grad is written to 0 after it has been consumed, masked rows included."""
+    groups = list(groups)
+    if not 1 <= len(groups) <= ADAM_MAX_GROUPS:
+        raise ValueError("adam_step: %d groups, the call takes 1..%d" % (len(groups), ADAM_MAX_GROUPS))
+    table = (AdamGroup * len(groups))()
+    P = None
+    for k, (param, grad, exp_avg, exp_avg_sq, lr) in enumerate(groups):
+        for t_, name in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+            if t_.dtype != _F32 or not t_.is_contiguous():
+                raise ValueError("adam_step: %s of group %d must be a contiguous float32 tensor (got %s, contiguous: %s)"
+                                 % (name, k, t_.dtype, t_.is_contiguous()))
+            if t_.shape != param.shape:
+                raise ValueError("adam_step: %s of group %d is %s, its param %s" % (name, k, tuple(t_.shape), tuple(param.shape)))
+        if param.dim() < 1 or param.shape[0] < 1 or param.numel() < 1:
+            raise ValueError("adam_step: param of group %d is %s: [P, ...] with P >= 1 and at least one element per row" % (k, tuple(param.shape)))
+        P = param.shape[0] if P is None else P
+        if param.shape[0] != P:
+            raise ValueError("adam_step: group %d has %d rows, group 0 has %d: the groups of a call belong to one cloud" % (k, param.shape[0], P))
+        table[k] = AdamGroup(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), param.numel() // P, float(lr))
+    if visible is not None and (visible.dtype != torch.uint8 or tuple(visible.shape) != (P,) or not visible.is_contiguous()):
+        raise ValueError("adam_step: visible must be a contiguous uint8 [%d] tensor (got %s %s)" % (P, visible.dtype, tuple(visible.shape)))
+    device = groups[0][0].device
+    _require_hip(device)
+    for k, g in enumerate(groups):
+        for t_ in g[:4]:
+            if t_.device != device:
+                raise ValueError("adam_step: a tensor of group %d is on %s, group 0 on %s" % (k, t_.device, device))
+    if visible is not None and visible.device != device:
+        raise ValueError("adam_step: visible is on %s, the groups on %s" % (visible.device, device))
+    with _on_device(device):
+        _check(lib.gsr_adam_step(P, len(groups), table, int(t), float(beta1), float(beta2), float(eps),
+                                 None if visible is None else visible.data_ptr(), 1 if zero_grads else 0, _stream_handle(device)))
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,

@@ -419,6 +419,46 @@ int gsr_image_loss_backward(int V, int W, int H, int ss, float lambda_dssim, con
                             const float* dL_dloss /* [V] or NULL */, const void* state, size_t state_bytes,
                             float* dL_dimage /* [V][3][H ss][W ss] */, gsr_stream_t stream);
 
+/* The optimizer step of a training iteration: Adam (torch.optim.Adam without amsgrad, weight_decay or maximize) over the 1..8 parameter
+ * groups of one cloud in ONE launch, with an optional per-Gaussian visibility mask (the "sparse Adam" of splat trainers: a Gaussian no
+ * view of the batch saw keeps its parameters AND its moments, instead of drifting on stale momentum).
+ *   gsr_visible_from_radii: visible[i] = any_v(radii[v][i] > 0) for the radii [V][P] a batch forward returned; every element of
+ * visible [P] is written (0 or 1).
+ *   gsr_adam_step.  A group is four float32 device arrays of P * width elements, row-major [P][width]: param, grad, exp_avg,
+ * exp_avg_sq, with its own width >= 1 and learning rate lr; `groups` is a HOST array of G of them, copied into the kernel's arguments.
+ * t is the number of this step, 1 for the first.  Definition, per element, in float32 with one rounding per written operation, where
+ * b1 = beta1, b2 = beta2 and eps are the float32 values passed:
+ *     c1 = 1.0f - b1,  c2 = 1.0f - b2
+ *     m' = b1 * m + c1 * g
+ *     v' = b2 * v + c2 * (g * g)
+ *     p' = p - step_g * (m' / (sqrtf(v') * rsq2 + eps))
+ * with the two constants formed on the host in double and rounded once to float32:
+ *     step_g = lr_g / (1 - b1^t),   rsq2 = 1 / sqrt(1 - b2^t)
+ * param, exp_avg and exp_avg_sq are updated in place.  A non-finite gradient propagates as it does in torch: there is no guard.
+ *   visible: uint8 [P] on the device, or NULL.  With a mask, the rows i with visible[i] == 0 are untouched: param, exp_avg and
+ * exp_avg_sq keep their bits.  Without a mask every row is updated.
+ *   zero_grads != 0: every element of every group's grad is written to 0 after it has been consumed, masked rows included.
+ *   Pointers need only the 4-byte alignment of their type: a group whose four arrays are all 16-byte aligned is walked 16 B per lane,
+ * any other group, and the last P * width % 4 elements, element by element, with the same bits.
+ *   Nothing is read back from the device, no host wait is made, nothing is allocated.  There are no atomics.  Outputs are bit-identical
+ * from call to call; a group's result does not depend on which other groups share the call; rows [a, b) submitted alone (offset
+ * pointers, P = b - a) get the bits they get in the whole call.
+ *   Refused, in this order, before any device call, each with GSR_ERR_INVALID: G outside 1..8; P < 1, a width < 1 or a
+ * P * width >= 2^31; t < 1; beta1 or beta2 outside [0, 1) or NaN, eps <= 0 or not finite, an lr negative or not finite; groups NULL or
+ * one of a group's four pointers NULL.  gsr_visible_from_radii refuses V outside 1..256, then P < 1 or V * P >= 2^31, then a NULL
+ * radii or visible. */
+typedef struct {
+    float* param;
+    float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int width;
+    float lr;
+} gsr_adam_group;
+int gsr_visible_from_radii(int V, int P, const int32_t* radii /* [V][P] */, uint8_t* visible /* [P] */, gsr_stream_t stream);
+int gsr_adam_step(int P, int G, const gsr_adam_group* groups /* HOST array */, int64_t t, float beta1, float beta2, float eps,
+                  const uint8_t* visible /* [P] or NULL */, int zero_grads, gsr_stream_t stream);
+
 /* Pairs in the lists of the calling thread's last forward call, per view (out[V], HOST array): what a binning arena has to
  * hold.  Equal to num_rendered with reference_lists = 1. */
 int gsr_last_list_pairs(int64_t* out, int V);
