@@ -27,6 +27,7 @@
 
 #include "adam_step.hpp"
 #include "common.hpp"
+#include "density_control.hpp"
 #include "host.hpp"
 #include "image_loss.hpp"
 #include "switches.hpp"
@@ -873,6 +874,121 @@ int gsr_adam_step(int P, int G, const gsr_adam_group* groups, int64_t t, float b
     const Launch L{(hipStream_t)stream, 0};
     ProfScope ps("adam_step", L.stream);
     return launch_adam_step(L, T, visible);
+}
+
+// ---- adaptive density control (density_control.hip): every refusal precedes the first device call, in the header's order ----
+static bool density_sizes_ok(int P) { return P >= 1 && 2 * (int64_t)P < (1ll << 31); }
+
+// a rule the kernels can take: thresholds and sizes are non-negative finite numbers, min_opacity is a number
+static int density_rule_check(const char* who, const gsr_density_rule* r)
+{
+    if (!r) return GSR_OK;   // a NULL rule has no values to refuse and falls to the pointer check
+    if (!(r->grad_threshold >= 0.f) || !std::isfinite(r->grad_threshold) || !(r->dense_size >= 0.f) || !std::isfinite(r->dense_size) ||
+        !(r->max_world_size >= 0.f) || !std::isfinite(r->max_world_size) || r->max_screen_radius < 0 || std::isnan(r->min_opacity))
+        return fail(GSR_ERR_INVALID,
+                    "[gsr] %s: bad rule: grad_threshold = %g, dense_size = %g, max_world_size = %g (non-negative finite numbers), "
+                    "max_screen_radius = %d (at least 0), min_opacity = %g (not NaN)",
+                    who, (double)r->grad_threshold, (double)r->dense_size, (double)r->max_world_size, r->max_screen_radius,
+                    (double)r->min_opacity);
+    return GSR_OK;
+}
+
+static DensityRuleDev density_rule_dev(const gsr_density_rule& r)
+{
+    DensityRuleDev d;
+    d.grad_threshold = r.grad_threshold;
+    d.dense_size = r.dense_size;
+    d.min_opacity = r.min_opacity;
+    d.max_world_size = r.max_world_size;
+    d.max_screen_radius = r.max_screen_radius;
+    d.log_scales = r.log_scales != 0;
+    d.normalize_rotations = r.normalize_rotations != 0;
+    d.key0 = (uint32_t)(r.seed & 0xFFFFFFFFull);
+    d.key1 = (uint32_t)(r.seed >> 32);
+    return d;
+}
+
+size_t gsr_density_scratch_bytes(int P) { return density_sizes_ok(P) ? density_scratch_bytes(P) : 0; }
+
+int gsr_density_plan(int P, const gsr_density_rule* rule, const float* scales, const float* opacities, const float* grad_norm_sum,
+                     const int32_t* visible_views, const int32_t* max_radius, const uint8_t* prune_mask, uint32_t* offsets, uint8_t* action,
+                     int64_t* totals, void* scratch, size_t scratch_bytes, gsr_stream_t stream)
+{
+    const char* who = "density_plan";
+    if (!density_sizes_ok(P)) return fail(GSR_ERR_INVALID, "[gsr] %s: bad sizes P=%d (at least 1, 2 P below 2^31)", who, P);
+    if (int rc = density_rule_check(who, rule)) return rc;
+    if (!rule || !scales || !opacities || !grad_norm_sum || !visible_views || !max_radius || !offsets || !action || !totals || !scratch)
+        return fail(GSR_ERR_INVALID, "[gsr] %s: rule, scales, opacities, grad_norm_sum, visible_views, max_radius, offsets, action, totals or "
+                                     "scratch is NULL", who);
+    if (scratch_bytes < density_scratch_bytes(P))
+        return fail(GSR_ERR_CAPACITY, "[gsr] %s: scratch too small (%zu < %zu: gsr_density_scratch_bytes(%d))", who, scratch_bytes,
+                    density_scratch_bytes(P), P);
+    const DensityPlanArgs a{P, scales, opacities, grad_norm_sum, visible_views, max_radius, prune_mask, offsets, action, totals,
+                            reinterpret_cast<uint32_t*>(scratch)};
+    const Launch L{(hipStream_t)stream, 0};
+    ProfScope ps("density_plan", L.stream);
+    return launch_density_plan(L, density_rule_dev(*rule), a);
+}
+
+int gsr_density_apply(int P, int G, const gsr_density_group* groups, const gsr_density_rule* rule, const uint32_t* offsets,
+                      const uint8_t* action, const float* scales, const float* rotations, const float* noise, int32_t* index, int64_t P_out,
+                      gsr_stream_t stream)
+{
+    const char* who = "density_apply";
+    if (!density_sizes_ok(P)) return fail(GSR_ERR_INVALID, "[gsr] %s: bad sizes P=%d (at least 1, 2 P below 2^31)", who, P);
+    if (G < 1 || G > DENSITY_MAX_GROUPS) return fail(GSR_ERR_INVALID, "[gsr] %s: group count %d outside 1..%d", who, G, DENSITY_MAX_GROUPS);
+    // (the table is read for its sizes and roles before its pointers are judged: a NULL table falls to the pointer check)
+    for (int k = 0; groups && k < G; k++) {
+        const gsr_density_group& s = groups[k];
+        if (s.width < 1 || 2 * (int64_t)P * (int64_t)s.width >= (1ll << 31))
+            return fail(GSR_ERR_INVALID, "[gsr] %s: bad sizes in group %d: width %d (at least 1, 2 P width = 2 x %d x %d below 2^31)", who, k,
+                        s.width, P, s.width);
+        if (s.role < GSR_DENSITY_COPY || s.role > GSR_DENSITY_MOMENT)
+            return fail(GSR_ERR_INVALID, "[gsr] %s: bad sizes in group %d: role %d is none of COPY, MEANS, SCALES, MOMENT", who, k, s.role);
+    }
+    int n_means = 0, n_scales = 0;
+    for (int k = 0; groups && k < G; k++) {
+        const gsr_density_group& s = groups[k];
+        if ((s.role == GSR_DENSITY_MEANS || s.role == GSR_DENSITY_SCALES) && s.width != 3)
+            return fail(GSR_ERR_INVALID, "[gsr] %s: group %d has the role %s and width %d: it takes width 3", who, k,
+                        s.role == GSR_DENSITY_MEANS ? "MEANS" : "SCALES", s.width);
+        n_means += s.role == GSR_DENSITY_MEANS;
+        n_scales += s.role == GSR_DENSITY_SCALES;
+    }
+    if (n_means > 1 || n_scales > 1)
+        return fail(GSR_ERR_INVALID, "[gsr] %s: %d MEANS and %d SCALES groups: at most one of each", who, n_means, n_scales);
+    if (int rc = density_rule_check(who, rule)) return rc;
+    if (!groups || !rule || !offsets || !action) return fail(GSR_ERR_INVALID, "[gsr] %s: groups, rule, offsets or action is NULL", who);
+    for (int k = 0; k < G; k++)
+        if (!groups[k].src || !groups[k].dst) return fail(GSR_ERR_INVALID, "[gsr] %s: src or dst of group %d is NULL", who, k);
+    if (n_means && (!scales || !rotations))
+        return fail(GSR_ERR_INVALID, "[gsr] %s: scales or rotations is NULL and a MEANS group is present", who);
+    if (P_out < 0 || P_out > 2 * (int64_t)P)
+        return fail(GSR_ERR_INVALID, "[gsr] %s: P_out = %lld outside 0..2 P = %lld", who, (long long)P_out, 2 * (long long)P);
+    if (P_out == 0) return GSR_OK;
+
+    DensityTable T;
+    std::memset(&T, 0, sizeof(T));
+    T.G = G;
+    int64_t units = 0;
+    for (int k = 0; k < G; k++) units += div_up(P_out * groups[k].width, DENSITY_BLOCK_ELEMS);
+    uint32_t end = 0;
+    for (int k = 0; k < G; k++) {
+        const gsr_density_group& s = groups[k];
+        DensityGroupDev& d = T.g[k];
+        d.src = s.src;
+        d.dst = s.dst;
+        d.n = (uint32_t)(P_out * s.width);
+        d.width = (uint32_t)s.width;
+        d.block_end = end += density_group_blocks(d.n, units);
+        d.role = s.role;
+        d.vec = (s.role == GSR_DENSITY_COPY || s.role == GSR_DENSITY_MOMENT) && s.width % DENSITY_VEC == 0 &&
+                (((uintptr_t)s.src | (uintptr_t)s.dst) & 15u) == 0;
+    }
+    const DensityApplyArgs a{P, (uint32_t)P_out, offsets, action, scales, rotations, noise, index};
+    const Launch L{(hipStream_t)stream, 0};
+    ProfScope ps("density_apply", L.stream);
+    return launch_density_apply(L, density_rule_dev(*rule), T, a);
 }
 
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,

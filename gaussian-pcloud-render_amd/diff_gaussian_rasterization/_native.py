@@ -72,6 +72,9 @@ _DECL = {
     "gsr_image_loss_backward": (_int, [_int, _int, _int, _int, C.c_float, _fp, _fp, _fp, _fp, _size, _fp, _fp]),
     "gsr_visible_from_radii": (_int, [_int, _int, _fp, _fp, _fp]),
     "gsr_adam_step": (_int, [_int, _int, _fp, _i64, C.c_float, C.c_float, C.c_float, _fp, _int, _fp]),
+    "gsr_density_scratch_bytes": (_size, [_int]),
+    "gsr_density_plan": (_int, [_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _size, _fp]),
+    "gsr_density_apply": (_int, [_int, _int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _fp]),
     "gsr_mark_visible": (_int, [_int, _fp, _fp, _fp, _fp, _fp]),
     "gsr_query": (_int, [_pp, _int, _fp, _fp, _size, _fp, _i64, _fp, _size, _fp]),
     "gsr_set_profiling": (None, [_int]),
@@ -1113,6 +1116,107 @@ def adam_step(groups, t, beta1, beta2, eps, visible=None, zero_grads=False):
     with _on_device(device):
         _check(lib.gsr_adam_step(P, len(groups), table, int(t), float(beta1), float(beta2), float(eps),
                                  None if visible is None else visible.data_ptr(), 1 if zero_grads else 0, _stream_handle(device)))
+
+
+class DensityRuleStruct(C.Structure):
+    """gsr_density_rule of include/gsr.h"""
+    _fields_ = [("grad_threshold", C.c_float), ("dense_size", C.c_float), ("min_opacity", C.c_float), ("max_screen_radius", C.c_int),
+                ("max_world_size", C.c_float), ("log_scales", C.c_int), ("normalize_rotations", C.c_int), ("seed", C.c_uint64)]
+
+
+class DensityGroup(C.Structure):
+    """gsr_density_group of include/gsr.h"""
+    _fields_ = [("src", _fp), ("dst", _fp), ("width", C.c_int), ("role", C.c_int)]
+
+
+DENSITY_MAX_GROUPS = 8
+DENSITY_PRUNED, DENSITY_KEPT, DENSITY_CLONED, DENSITY_CLONED_COPY, DENSITY_SPLIT = range(5)        # GSR_DENSITY_* action codes
+DENSITY_COPY, DENSITY_MEANS, DENSITY_SCALES, DENSITY_MOMENT = range(4)                             # GSR_DENSITY_* roles
+
+
+def _density_input(t, dtype, shape, device, name, who):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError("%s: %s must be a contiguous %s %s tensor (got %s %s, contiguous: %s)"
+                         % (who, name, dtype, list(shape), t.dtype, tuple(t.shape), t.is_contiguous()))
+    if device is not None and t.device != device:
+        raise ValueError("%s: %s is on %s, scales on %s" % (who, name, t.device, device))
+
+
+def density_plan(rule, scales, opacities, grad_norm_sum, visible_views, max_radius, prune_mask=None):
+    """C ABI gsr_density_plan: the decision of adaptive density control for a cloud of P Gaussians.  rule: a DensityRuleStruct;
+    scales float32 [P,3]; opacities float32 [P] or [P,1]; grad_norm_sum float32 [P], visible_views and max_radius int32 [P] as
+    DensityStats holds them; prune_mask uint8 [P] or None.  Returns (offsets uint32-as-int32 [P+1], action uint8 [P], totals int64 [5]),
+    all on the device: nothing is read back."""
+    who = "density_plan"
+    if scales.dim() != 2 or scales.shape[0] < 1:
+        raise ValueError("%s: scales must be [P, 3] with P >= 1 (got %s)" % (who, tuple(scales.shape)))
+    P = scales.shape[0]
+    _density_input(scales, _F32, (P, 3), None, "scales", who)
+    device = scales.device
+    if opacities.dim() == 2 and opacities.shape[1] == 1:
+        opacities = opacities.view(-1) if opacities.is_contiguous() else opacities
+    _density_input(opacities, _F32, (P,), device, "opacities", who)
+    _density_input(grad_norm_sum, _F32, (P,), device, "grad_norm_sum", who)
+    _density_input(visible_views, torch.int32, (P,), device, "visible_views", who)
+    _density_input(max_radius, torch.int32, (P,), device, "max_radius", who)
+    if prune_mask is not None:
+        _density_input(prune_mask, torch.uint8, (P,), device, "prune_mask", who)
+    _require_hip(device)
+    offsets = torch.empty((P + 1,), dtype=torch.int32, device=device)
+    action = torch.empty((P,), dtype=torch.uint8, device=device)
+    totals = torch.empty((5,), dtype=torch.int64, device=device)
+    nbytes = lib.gsr_density_scratch_bytes(P)
+    scratch = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=device)
+    with _on_device(device):
+        _check(lib.gsr_density_plan(P, C.addressof(rule), scales.data_ptr(), opacities.data_ptr(), grad_norm_sum.data_ptr(),
+                                    visible_views.data_ptr(), max_radius.data_ptr(), None if prune_mask is None else prune_mask.data_ptr(),
+                                    offsets.data_ptr(), action.data_ptr(), totals.data_ptr(), scratch.data_ptr(), nbytes,
+                                    _stream_handle(device)))
+    return offsets, action, totals
+
+
+def density_apply(groups, rule, offsets, action, P_out, scales=None, rotations=None, noise=None, index=None):
+    """C ABI gsr_density_apply: the output rows of 1..8 groups from a plan, in ONE gather launch.  groups: a list of (src, dst, role),
+    src a contiguous float32 [P, ...] tensor, dst a contiguous float32 [P_out, ...] tensor with the same row shape, role one of
+    DENSITY_COPY / MEANS / SCALES / MOMENT.  offsets, action: what density_plan returned.  P_out: the host's copy of offsets[P].
+    scales [P,3] and rotations [P,4]: needed with a MEANS group.  noise: float32 [P,2,3] or None for the generator of rule.seed.
+    index: an int32 [P_out] tensor that receives the output-row -> source map, or None."""
+    who = "density_apply"
+    groups = list(groups)
+    if not 1 <= len(groups) <= DENSITY_MAX_GROUPS:
+        raise ValueError("%s: %d groups, the call takes 1..%d" % (who, len(groups), DENSITY_MAX_GROUPS))
+    P_out = int(P_out)
+    if action.dtype != torch.uint8 or action.dim() != 1 or action.shape[0] < 1 or not action.is_contiguous():
+        raise ValueError("%s: action must be a contiguous uint8 [P] tensor (got %s %s)" % (who, action.dtype, tuple(action.shape)))
+    P, device = action.shape[0], action.device
+    _density_input(offsets, torch.int32, (P + 1,), device, "offsets", who)
+    if not 0 <= P_out <= 2 * P:
+        raise ValueError("%s: P_out = %d outside 0..2 P = %d" % (who, P_out, 2 * P))
+    table = (DensityGroup * len(groups))()
+    for k, (src, dst, role) in enumerate(groups):
+        for t_, name, rows in ((src, "src", P), (dst, "dst", P_out)):
+            if t_.dtype != _F32 or not t_.is_contiguous() or t_.dim() < 1 or t_.shape[0] != rows or t_.device != device:
+                raise ValueError("%s: %s of group %d must be a contiguous float32 tensor of %d rows on %s (got %s %s on %s, contiguous: %s)"
+                                 % (who, name, k, rows, device, t_.dtype, tuple(t_.shape), t_.device, t_.is_contiguous()))
+        if src.shape[1:] != dst.shape[1:] or src.numel() < 1:
+            raise ValueError("%s: group %d has source rows of %s and destination rows of %s" % (who, k, tuple(src.shape[1:]), tuple(dst.shape[1:])))
+        if role not in (DENSITY_COPY, DENSITY_MEANS, DENSITY_SCALES, DENSITY_MOMENT):
+            raise ValueError("%s: role %r of group %d is none of DENSITY_COPY, MEANS, SCALES, MOMENT" % (who, role, k))
+        table[k] = DensityGroup(src.data_ptr(), dst.data_ptr(), src.numel() // P, role)
+    if scales is not None:
+        _density_input(scales, _F32, (P, 3), device, "scales", who)
+    if rotations is not None:
+        _density_input(rotations, _F32, (P, 4), device, "rotations", who)
+    if noise is not None:
+        _density_input(noise, _F32, (P, 2, 3), device, "noise", who)
+    if index is not None:
+        _density_input(index, torch.int32, (P_out,), device, "index", who)
+    _require_hip(device)
+    if P_out == 0:       # nothing to write (and an empty destination has no address to pass)
+        return
+    with _on_device(device):
+        _check(lib.gsr_density_apply(P, len(groups), table, C.addressof(rule), offsets.data_ptr(), action.data_ptr(), _ptr(scales),
+                                     _ptr(rotations), _ptr(noise), _ptr(index), P_out, _stream_handle(device)))
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,

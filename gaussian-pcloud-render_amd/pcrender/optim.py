@@ -101,6 +101,27 @@ class GaussianAdam:
         for k, lr in state["lrs"].items():
             self.set_lr(k, lr)
 
+    def adopt(self, new_params, exp_avg, exp_avg_sq):
+        """The checked hand-over after densification or pruning for a caller that has built the new moments itself (pcrender.density
+        does, in HIP): `new_params` (same names, P' rows each) replace the parameters, `exp_avg` and `exp_avg_sq` (same names, each
+        tensor contiguous float32 with its parameter's shape, on its device) replace the moments.  The step count stays."""
+        new_params, moments = dict(new_params), (dict(exp_avg), dict(exp_avg_sq))
+        for part, name in zip((new_params,) + moments, ("parameters", "exp_avg", "exp_avg_sq")):
+            if set(part) != set(self.params):
+                raise ValueError("GaussianAdam.adopt: %s %s, the optimizer has %s" % (name, sorted(part), sorted(self.params)))
+        new_params = {k: new_params[k] for k in self.params}      # the groups keep their order
+        for k, p in new_params.items():
+            if p.shape[1:] != self.params[k].shape[1:]:
+                raise ValueError("GaussianAdam.adopt: %s has rows of %s, they were %s" % (k, tuple(p.shape[1:]), tuple(self.params[k].shape[1:])))
+            for part, name in zip(moments, ("exp_avg", "exp_avg_sq")):
+                m = part[k]
+                if m.shape != p.shape or m.dtype != torch.float32 or not m.is_contiguous() or m.device != p.device:
+                    raise ValueError("GaussianAdam.adopt: %s[%s] must be a contiguous float32 %s tensor on %s (got %s %s on %s)"
+                                     % (name, k, tuple(p.shape), p.device, m.dtype, tuple(m.shape), m.device))
+        self._adopt(new_params)
+        self.exp_avg = {k: moments[0][k] for k in self.params}
+        self.exp_avg_sq = {k: moments[1][k] for k in self.params}
+
     def reindex(self, index, new_params):
         """After densification or pruning: `new_params` (same names, P' rows each) replace the parameters; the moment row of new
         Gaussian i is the old row index[i], or zero where index[i] < 0.  index: an integer [P'] tensor.  The step count stays."""

@@ -459,6 +459,113 @@ int gsr_visible_from_radii(int V, int P, const int32_t* radii /* [V][P] */, uint
 int gsr_adam_step(int P, int G, const gsr_adam_group* groups /* HOST array */, int64_t t, float beta1, float beta2, float eps,
                   const uint8_t* visible /* [P] or NULL */, int zero_grads, gsr_stream_t stream);
 
+/* Adaptive density control: clone, split and prune in one pass.  The decision of 3DGS's densify_and_prune from the statistics
+ * gsr_backward_view_stats leaves, restated so that one pass over the cloud evaluates it (gsr_density_plan), and the new cloud built
+ * from the plan (gsr_density_apply).
+ *   Decision inputs per Gaussian i: scales[i][3], opacities[i], grad_norm_sum[i] (float32), visible_views[i] and max_radius[i]
+ * (int32), and optionally prune_mask[i] (uint8, NULL = none).  The rule (gsr_density_rule, a HOST struct, copied into the kernel's
+ * arguments): grad_threshold; dense_size (3DGS: percent_dense x extent); min_opacity, compared in the STORED domain (a caller that
+ * stores logits passes logit(0.005)); max_screen_radius (int, 0 = test off); max_world_size (float, 0 = test off; 3DGS: 0.1 x extent);
+ * log_scales (0/1); normalize_rotations (0/1); seed.
+ *   Derived, in float32 with one rounding per written operation:
+ *     sigma = scales             (log_scales = 0)        sigma = expf(scales)   (log_scales = 1)
+ *     smax  = max(sigma_x, sigma_y, sigma_z)
+ *     g     = grad_norm_sum / (float)max(visible_views, 1)
+ * A NaN compares false everywhere, as in torch: a NaN gradient densifies nothing.
+ *   Actions, evaluated in this order (the set of rows is what 3DGS produces when clone, split and prune run one after the other):
+ *     hot  = g >= grad_threshold
+ *     dead = opacities[i] < min_opacity || (prune_mask && prune_mask[i])
+ *     big  = (max_screen_radius > 0 && max_radius[i] > max_screen_radius) || (max_world_size > 0 && smax > max_world_size)
+ *     hot && smax <= dense_size   clone:  dead -> no rows (GSR_DENSITY_PRUNED); big -> the copy alone, one row marked new
+ *                                 (GSR_DENSITY_CLONED_COPY); else the original and a bit-identical copy (GSR_DENSITY_CLONED).  The
+ *                                 screen-radius and world-size tests apply to the original only: a copy starts with radius 0
+ *     hot && smax >  dense_size   split:  dead || (max_world_size > 0 && smax / 1.6f > max_world_size) -> no rows
+ *                                 (GSR_DENSITY_PRUNED); else the parent is removed and two children are made (GSR_DENSITY_SPLIT).
+ *                                 The screen-radius test does not apply to children
+ *     otherwise                   dead || big -> no rows (GSR_DENSITY_PRUNED); else one row (GSR_DENSITY_KEPT)
+ * so every Gaussian yields c_i in {0, 1, 2} output rows.
+ *   Output order: ascending source index, a Gaussian's rows adjacent, the original before its copy and child 0 before child 1 (not
+ * 3DGS's "kept, then clones, then children": this one is an exclusive scan of c_i and keeps a spatially ordered cloud ordered).
+ *   gsr_density_plan writes offsets [P + 1], the exclusive prefix of c_i with offsets[P] = P'; action [P], the GSR_DENSITY_* code of
+ * every Gaussian; and totals [5] (int64, DEVICE) = {P', carried rows (kept Gaussians and the originals of clones), copies made,
+ * children made, source Gaussians that left no row}.  Three launches: decide and count per workgroup, a scan of the workgroup counts
+ * by one workgroup (looped: any P up to the limit), the final offsets.  scratch holds the workgroup counts:
+ * gsr_density_scratch_bytes(P) bytes, a pure host function, a multiple of 256, 0 for a refused P.
+ *   gsr_density_apply builds the output rows of 1..8 groups from the plan, which it only reads: it may be called several times with
+ * different group tables (parameters, then exp_avg, then exp_avg_sq).  A group is a float32 source [P][width], a destination
+ * [P_out][width] and a role (`groups` is a HOST array, copied into the kernel's arguments); src and dst must not overlap:
+ *     GSR_DENSITY_COPY     every row takes its source row's bits
+ *     GSR_DENSITY_MEANS    width 3; a child is displaced (below), every other row takes its source row's bits
+ *     GSR_DENSITY_SCALES   width 3; a child's scales are sigma' = sigma / 1.6f (log_scales = 0: one float32 division) or
+ *                          s' = s - 0x1.e148a2p-2f (log_scales = 1: the float32 nearest log(1.6), one subtraction)
+ *     GSR_DENSITY_MOMENT   a carried row (kept, or the original of a clone) takes its source row's bits, a new row (copy or child) +0
+ * index (int32 [P_out], or NULL) receives i for a carried row and -1 - i for a new row made from parent i: negative means "zero
+ * moments" to a re-indexing optimizer, and still names the parent.  P_out is the caller's copy of offsets[P]; every store is bounded
+ * by it, so a stale value can truncate the output but never write past dst.  P_out = 0: GSR_OK, nothing is written.
+ *   Child mean.  Child k in {0, 1} of parent i: with (r, x, y, z) the stored quaternion -- as it is (normalize_rotations = 0: what
+ * the rasterizer renders) or each component divided by n = sqrtf(((r r + x x) + y y) + z z) (normalize_rotations = 1) -- and R the
+ * rotation the rasterizer builds from it,
+ *     R[0] = (1 - 2 (y y + z z),  2 (x y - r z),      2 (x z + r y))
+ *     R[1] = (2 (x y + r z),      1 - 2 (x x + z z),  2 (y z - r x))
+ *     R[2] = (2 (x z - r y),      2 (y z + r x),      1 - 2 (x x + y y))
+ *     t = sigma * eps (componentwise);   d_r = (R[r][0] t0 + R[r][1] t1) + R[r][2] t2;   mu'_r = mu_r + d_r
+ * in float32, one rounding per written operation.  Every other value of a child or a copy is the parent's bits.
+ *   Noise eps: the caller's noise (float32 [P][2][3], indexed by source and child, read for splits only), or with noise = NULL a
+ * counter-based generator: Philox4x32-10 with the multipliers 0xD2511F53 (on word 0) and 0xCD9E8D57 (on word 2), the key increments
+ * 0x9E3779B9 and 0xBB67AE85 (the key is bumped between rounds, nine times), key = (low half of seed, high half of seed), counter =
+ * (i, k, 0, 0); a round maps (c0, c1, c2, c3) to (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)).  The four output
+ * words x_j give, in float32,
+ *     u_j = ((float)(x_j >> 8) + 0.5f) * 0x1p-24f          (the sum rounds to even from x_j >> 8 = 2^23 on: u_j lies in (0, 1])
+ *     r01 = sqrtf(-2.0f * logf(u0));   eps0 = r01 * cosf(6.2831855f * u1);   eps1 = r01 * sinf(6.2831855f * u1)
+ *     eps2 = sqrtf(-2.0f * logf(u2)) * cosf(6.2831855f * u3)
+ * so eps depends on (seed, i, k) alone: not on P, the launch shape or other Gaussians.  Sub-ranges: rows [a, b) planned and applied
+ * alone (offset pointers, P = b - a, caller noise offset likewise) get the bits they get in the whole call; with noise = NULL the
+ * counter is the CALL's i, so a sub-range draws other noise than the whole.
+ *   Nothing is read back from the device, no host wait is made, nothing is allocated.  There are no atomics.  Outputs are
+ * bit-identical from call to call; a group's result does not depend on which other groups share the call.  Groups whose src and dst
+ * are 16-byte aligned and whose width is a multiple of 4 move 16 B per lane, every other group element by element, with the same bits.
+ *   Refused, in this order, before any device call, with GSR_ERR_INVALID unless noted: P < 1 or 2 P >= 2^31; (apply) G outside 1..8, a
+ * width < 1 or 2 P width >= 2^31, a role that is none of the four; (apply) a MEANS or SCALES group whose width is not 3; (apply) more
+ * than one MEANS or more than one SCALES group; a rule with a negative or non-finite grad_threshold, dense_size or max_world_size, a
+ * negative max_screen_radius or a NaN min_opacity; a NULL required pointer (plan: rule, scales, opacities, grad_norm_sum,
+ * visible_views, max_radius, offsets, action, totals, scratch; apply: groups, rule, a group's src or dst, offsets, action, and scales
+ * and rotations when a MEANS group is present); (apply) P_out negative or above 2 P; (plan) scratch smaller than
+ * gsr_density_scratch_bytes(P): GSR_ERR_CAPACITY, the message names the size needed. */
+#define GSR_DENSITY_PRUNED 0      /* no row */
+#define GSR_DENSITY_KEPT 1        /* one row, carried */
+#define GSR_DENSITY_CLONED 2      /* two rows: the original (carried) and its copy (new) */
+#define GSR_DENSITY_CLONED_COPY 3 /* one row: the copy (new); the original failed the screen-radius or world-size test */
+#define GSR_DENSITY_SPLIT 4       /* two rows: the children (new) */
+#define GSR_DENSITY_COPY 0
+#define GSR_DENSITY_MEANS 1
+#define GSR_DENSITY_SCALES 2
+#define GSR_DENSITY_MOMENT 3
+typedef struct {
+    float grad_threshold;
+    float dense_size;
+    float min_opacity;
+    int max_screen_radius;
+    float max_world_size;
+    int log_scales;
+    int normalize_rotations;
+    uint64_t seed;
+} gsr_density_rule;
+typedef struct {
+    const float* src;
+    float* dst;
+    int width;
+    int role;
+} gsr_density_group;
+size_t gsr_density_scratch_bytes(int P);
+int gsr_density_plan(int P, const gsr_density_rule* rule, const float* scales /* [P][3] */, const float* opacities /* [P] */,
+                     const float* grad_norm_sum /* [P] */, const int32_t* visible_views /* [P] */, const int32_t* max_radius /* [P] */,
+                     const uint8_t* prune_mask /* [P] or NULL */, uint32_t* offsets /* [P + 1] */, uint8_t* action /* [P] */,
+                     int64_t* totals /* [5], DEVICE */, void* scratch, size_t scratch_bytes, gsr_stream_t stream);
+int gsr_density_apply(int P, int G, const gsr_density_group* groups /* HOST array */, const gsr_density_rule* rule,
+                      const uint32_t* offsets /* [P + 1] */, const uint8_t* action /* [P] */, const float* scales /* [P][3] or NULL */,
+                      const float* rotations /* [P][4] or NULL */, const float* noise /* [P][2][3] or NULL */,
+                      int32_t* index /* [P_out] or NULL */, int64_t P_out, gsr_stream_t stream);
+
 /* Pairs in the lists of the calling thread's last forward call, per view (out[V], HOST array): what a binning arena has to
  * hold.  Equal to num_rendered with reference_lists = 1. */
 int gsr_last_list_pairs(int64_t* out, int V);
