@@ -1,12 +1,17 @@
 """The Adam step of include/gsr.h (gsr_adam_step) restated on the CPU, the seeded cases the CPU and GPU tests share, and the bars a
 single step is held to.  Importable without the built library or a device.
 
-  kernel_constants / VEC / WAVE / BLOCK     ADAM_VEC, ADAM_THREADS as csrc/adam_step.hpp defines them; the elements of one block round
+  kernel_constants / VEC / WAVE / BLOCK     ADAM_VEC, ADAM_THREADS, ADAM_MAX_BLOCKS (MAX_BLOCKS) as csrc/adam_step.hpp defines them; the
+                                            elements of one block round
+  group_blocks / work_split / rounds_taken  the entry's split of a call's rounds over a capped grid and a workgroup's grid-stride walk,
+                                            restated (density_control.hpp has the same rule: density_ref calls these with its constants)
   host_constants                            step_g and rsq2 as the entry forms them: in double, rounded once to float32
   adam64 / adam32                           the definition in float64 (unrounded constants: what torch.optim.Adam computes in float64)
                                             and op by op in numpy float32 (the arithmetic the kernel is specified to perform)
   CASES / MASKS / TS / case_inputs / mask   the case table (sizes named with the kernel's constants), the mask kinds, the step counts
-  EPS / check_step                          the single-step bars, derived by counting roundings (see check_step)
+  CAP_CASES / CAP_CLAIMS / BENCH_SHAPE      the cases above the grid cap (8 M elements each: a table of their own, walked by one test
+                                            each), what each is there to reach, and the benchmark cloud's shape
+  EPS / check_step / check_step_in_ranges   the single-step bars, derived by counting roundings (see check_step); the same over row ranges
   Quadratic / trajectory_error              the seeded quadratic of the trajectory test and its error metric"""
 import os
 import re
@@ -24,12 +29,59 @@ F = np.float32
 def kernel_constants():
     text = open(os.path.join(ROOT, "gaussian-pcloud-render_amd", "csrc", "adam_step.hpp")).read()
     get = lambda name: int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1))  # noqa: E731
-    return get("ADAM_VEC"), get("ADAM_THREADS")
+    return get("ADAM_VEC"), get("ADAM_THREADS"), get("ADAM_MAX_BLOCKS")
 
 
-VEC, THREADS = kernel_constants()
+VEC, THREADS, MAX_BLOCKS = kernel_constants()
 WAVE = 64
 BLOCK = VEC * THREADS     # elements of a group one workgroup covers per grid-stride round
+
+
+# ---- the work split ---------------------------------------------------------------------------------------------------------------
+def div_up(a, b):
+    return -(-a // b)
+
+
+def group_blocks(n, units, block=None, cap=None):
+    """adam_group_blocks (and density_group_blocks, with that header's constants): the workgroups of a group of n elements when the
+    call's groups hold `units` rounds of `block` elements -- a round each up to `cap` rounds, above it the floor of the proportional
+    share of `cap`, at least one"""
+    block, cap = BLOCK if block is None else block, MAX_BLOCKS if cap is None else cap
+    mine = div_up(n, block)
+    if units <= cap:
+        return mine
+    share = mine * cap // units
+    return 1 if share < 1 else share
+
+
+def work_split(P, widths, block=None, cap=None):
+    """(units, workgroups per group) as the entry fills block_end: units the rounds of all groups of the call, P rows each"""
+    block = BLOCK if block is None else block
+    units = sum(div_up(P * w, block) for w in widths)
+    return units, [group_blocks(P * w, units, block, cap) for w in widths]
+
+
+def rounds_taken(n, nblocks, vec, block=None):
+    """How often each round of `block` elements of a group of n elements is taken when `nblocks` workgroups walk it as k_adam_step
+    does -- the scalar loop (base = block index x BLOCK; base < n; base += nblocks x BLOCK) or, with vec, the 16-B loop over
+    n / VEC slots and one more for the tail (i = block index x THREADS + lane; i < slots; i += nblocks x THREADS), followed for a
+    workgroup's lane 0.  int [rounds]"""
+    block = BLOCK if block is None else block
+    lanes = block // VEC
+    taken = np.zeros(div_up(n, block), np.int64)
+    slots = n // VEC + (1 if n % VEC else 0)
+    for b in range(nblocks):
+        if not vec:
+            base = b * block
+            while base < n:
+                taken[base // block] += 1
+                base += nblocks * block
+        else:
+            first = b * lanes                  # lane 0; a round is taken when its first slot exists
+            while first < slots:
+                taken[first // lanes] += 1
+                first += nblocks * lanes
+    return taken
 
 
 def host_constants(lr, t, b1=BETA1, b2=BETA2):
@@ -94,12 +146,38 @@ CASES = tuple(c for w in WIDTHS for c in _single(w)) + (
     Case("offset1,P=65", 65, (3, 45, 4, 48), LRS[:4], 1),                           # widths 3 and 45 lose their 16-byte alignment
     Case("offset1,P=%d" % (rows_of_a_block(3) + 1), rows_of_a_block(3) + 1, (3, 45, 1), LRS[:3], 1),
 )
+
+
+def cap_cases(cap, block):
+    """The cases above a grid cap of `cap` workgroups of `block` elements per round, each just past cap x block elements:
+      cap,w48      one 16-B group of cap + 1 rounds on cap workgroups: workgroup 0 takes a second round, a partial one
+      cap,offset1  two scalar groups (pointers one row off), second rounds in both, block_end a prefix of floor-divided shares
+      cap,floor    a width-1 group whose share floors to 0 and gets one workgroup, beside a group of odd width cap + 1
+      cap,cloud    the five groups of a training cloud in one call, P x 3 and P x 1 no multiples of 4"""
+    P48 = cap * block // 48 + 1
+    return (Case("cap,w48", P48, (48,), (1e-3,), 0),
+            Case("cap,offset1", P48, (3, 45), LRS[:2], 1),
+            Case("cap,floor", block, (1, cap + 1), (5e-2, 5e-3), 0),
+            Case("cap,cloud", 150001 * (cap * block) // (8192 * 1024) | 1, (3, 48, 1, 3, 4), LRS[:5], 0))   # 150001 today
+
+
+CAP_CASES = cap_cases(MAX_BLOCKS, BLOCK)
+# per case: the groups with a workgroup that takes a second round, and the groups whose share floors to 0
+CAP_CLAIMS = {"cap,w48": ((0,), ()), "cap,offset1": ((0, 1), ()), "cap,floor": ((1,), (0,)), "cap,cloud": ((0, 1, 2, 3, 4), ())}
+CAP_CLOUD_HALVES = ((0, CAP_CASES[3].P // 2 + 1), (CAP_CASES[3].P // 2 + 1, CAP_CASES[3].P))   # each below the cap; the cut is odd
+VISIBLE_CAP_P = MAX_BLOCKS * THREADS + 1      # the smallest P at which k_visible_from_radii's capped grid walks a second round
+BENCH_SHAPE = Case("bench", 800000, (3, 48, 1, 3, 4), LRS[:5], 0)                               # the benchmark cloud
 MASKS = ("zeros", "ones", "alternating", "one_row", "random30")
 TS = (1, 2, 1000, 10 ** 6)
 
 
 def case(name):
-    return next(c for c in CASES if c.name == name)
+    return next(c for c in CASES + CAP_CASES if c.name == name)
+
+
+def on_vector_path(c, width):
+    """whether a group of the case starts 16-B aligned (allocations are; offset_rows rows of `width` floats come before it)"""
+    return (c.offset_rows * width) % VEC == 0
 
 
 def mask(kind, P, seed=0):
@@ -125,6 +203,8 @@ def _log_uniform(rng, lo, hi, shape):
 def case_inputs(c, seed=0):
     """per group (p, g, m, v), float32 [P, width]: |g| and |m| log-uniform in [1e-6, 1e2] with random signs, v log-uniform in
     [1e-12, 1e4], p normal -- no intermediate of the step is subnormal"""
+    if c in CAP_CASES and _CAP_INPUTS.get("key") == (c, seed):
+        return _CAP_INPUTS["inputs"]
     rng = np.random.default_rng(sum(map(ord, c.name)) * 31 + seed)
     out = []
     for w in c.widths:
@@ -132,7 +212,12 @@ def case_inputs(c, seed=0):
         sign = lambda: rng.choice([-1.0, 1.0], shape)  # noqa: E731
         out.append(tuple(a.astype(F) for a in (rng.standard_normal(shape), sign() * _log_uniform(rng, 1e-6, 1e2, shape),
                                                sign() * _log_uniform(rng, 1e-6, 1e2, shape), _log_uniform(rng, 1e-12, 1e4, shape))))
+    if c in CAP_CASES:       # 140 MB and 0.7 s: the last one is kept for the next call with it (nothing writes to a case's inputs)
+        _CAP_INPUTS.update(key=(c, seed), inputs=out)
     return out
+
+
+_CAP_INPUTS = {}
 
 
 # ---- the single-step bars ---------------------------------------------------------------------------------------------------------
@@ -173,6 +258,19 @@ def check_step(got, inputs, lr, t, visible=None, b1=BETA1, b2=BETA2, eps=ADAM_EP
         ratios.append(worst)
         assert not bad.any(), "%s: %s misses its bar at %d elements, worst error / bar = %.3g" % (what, name, int(bad.sum()), worst)
     return tuple(ratios)
+
+
+def check_step_in_ranges(got, inputs, lr, t, visible=None, what="", elems=1 << 20):
+    """check_step over every element, about `elems` of them at a time (it is elementwise: the float64 temporaries of 8 M elements at
+    once are 1 GB).  Returns the largest ratios over the ranges."""
+    P, width = inputs[0].shape
+    step = max(1, elems // width)
+    worst = np.zeros(3)
+    for a in range(0, P, step):
+        b = min(P, a + step)
+        worst = np.maximum(worst, check_step(tuple(x[a:b] for x in got), tuple(x[a:b] for x in inputs), lr, t,
+                                             None if visible is None else visible[a:b], what="%s rows [%d, %d)" % (what, a, b)))
+    return worst
 
 
 # ---- a case through the library ---------------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """Adaptive density control (include/gsr.h gsr_density_plan / gsr_density_apply) restated in numpy, and the seeded cases the CPU and GPU
 tests share.  Importable without the built library or a device.
 
-  kernel_constants / THREADS / SCAN_ROUND / VEC   as csrc/density_control.hpp defines them
+  kernel_constants / THREADS / SCAN_ROUND / VEC / MAX_BLOCKS   as csrc/density_control.hpp defines them
+  apply_split                                     the gather's rounds and workgroups per group (the split rule adam_ref restates)
   header_codes / PRUNED ... SPLIT / COPY ... MOMENT   the GSR_DENSITY_* codes as include/gsr.h defines them
   Rule / make_rule                                the fields of gsr_density_rule (thresholds held as the float32 values the ABI takes)
   actions / plan_of                               the decision op by op in float32; offsets, index and totals from the action codes
@@ -17,6 +18,8 @@ from collections import namedtuple
 
 import numpy as np
 
+import adam_ref
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 U = 2.0 ** -24            # the unit round-off of float32
@@ -29,7 +32,7 @@ MASK32 = 0xFFFFFFFF
 def kernel_constants():
     text = open(os.path.join(ROOT, "gaussian-pcloud-render_amd", "csrc", "density_control.hpp")).read()
     get = lambda name: int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1))  # noqa: E731
-    return get("DENSITY_THREADS"), get("DENSITY_SCAN_ROUND"), get("DENSITY_VEC")
+    return get("DENSITY_THREADS"), get("DENSITY_SCAN_ROUND"), get("DENSITY_VEC"), get("DENSITY_MAX_BLOCKS")
 
 
 def header_codes():
@@ -37,7 +40,8 @@ def header_codes():
     return {m.group(1): int(m.group(2)) for m in re.finditer(r"#define GSR_DENSITY_([A-Z_]+) (\d+)", text)}
 
 
-THREADS, SCAN_ROUND, VEC = kernel_constants()
+THREADS, SCAN_ROUND, VEC, MAX_BLOCKS = kernel_constants()
+BLOCK = VEC * THREADS     # output elements of a group one gather workgroup covers per grid-stride round
 _CODES = header_codes()
 PRUNED, KEPT, CLONED, CLONED_COPY, SPLIT = (_CODES[k] for k in ("PRUNED", "KEPT", "CLONED", "CLONED_COPY", "SPLIT"))
 COPY, MEANS, SCALES, MOMENT = (_CODES[k] for k in ("COPY", "MEANS", "SCALES", "MOMENT"))
@@ -236,6 +240,7 @@ def near_threshold(rule, scales, ulps=4):
 Case = namedtuple("Case", "name P kind log norm mask")
 TWO_ROUNDS_P = THREADS * SCAN_ROUND + 1        # the smallest P whose workgroup counts need a second round of the scan's loop
 assert -(-TWO_ROUNDS_P // THREADS) > SCAN_ROUND >= -(-(TWO_ROUNDS_P - 1) // THREADS)
+THREE_ROUNDS_P = 2 * THREADS * SCAN_ROUND + 1  # ... and a third
 SMALL_P = (1, 2, 255, 256, 257, 1023, 1024, 1025)
 CASES = tuple(Case("mixed,P=%d" % P, P, "mixed", n % 2, (n // 2) % 2, (n // 4) % 2) for n, P in enumerate(SMALL_P)) + (
     Case("mixed,P=%d" % TWO_ROUNDS_P, TWO_ROUNDS_P, "mixed", 0, 1, 1),
@@ -245,6 +250,7 @@ CASES = tuple(Case("mixed,P=%d" % P, P, "mixed", n % 2, (n // 2) % 2, (n // 4) %
     Case("all_split,P=1025", 1025, "all_split", 0, 1, 0),
     Case("all_kept,P=1025", 1025, "all_kept", 0, 1, 0),
     Case("thresholds", 0, "thresholds", 0, 1, 1),      # P follows from the table of on-threshold rows
+    Case("mixed,P=%d" % THREE_ROUNDS_P, THREE_ROUNDS_P, "mixed", 0, 1, 1),     # (appended: a case's seed is its place in the table)
 )
 WIDTHS = (1, 3, 4, 45, 48)
 # the groups of an apply call beside means3D, scales and rotations: name, width, role
@@ -319,6 +325,13 @@ def case_groups(inp):
     """the eight (name, src, role) groups of a case's apply call: widths 3, 3, 4, 1, 45, 48 and two moment groups"""
     return [("means3D", inp["means3D"], MEANS), ("scales", inp["scales"], SCALES), ("rotations", inp["rotations"], COPY)] + [
         (name, inp["opacities"].reshape(-1, 1) if name == "opacities" else inp[name], role) for name, _, role in EXTRA_GROUPS]
+
+
+def apply_split(P_out, widths):
+    """(units, workgroups per group, rounds per group) of a gsr_density_apply call of P_out output rows: density_group_blocks and the
+    entry's loop are adam_step.hpp's rule with this header's constants"""
+    units, blocks = adam_ref.work_split(P_out, widths, BLOCK, MAX_BLOCKS)
+    return units, blocks, [adam_ref.div_up(P_out * w, BLOCK) for w in widths]
 
 
 def census(inputs):

@@ -4,10 +4,13 @@ CPU and GPU tests share, and the comparison of the library against it.  Importab
   window / loss_terms / loss_and_grad     the definition: conv2d with the 121-tap window, avg_pool2d for ss = 2, autograd; float64 is
                                           the reference, float32 the yardstick for rounding (the formulation a trainer writes in torch)
   brute_terms                             the same formula pixel by pixel in numpy loops (what test_cpu_image_loss_ref holds it to)
-  tile_constants                          IL_TILE_W, IL_TILE_H as csrc/image_loss.hpp defines them
-  CASES / case_inputs                     the case table: sizes, views, rate, lambda, content; inputs from the case's seed
+  tile_constants / IL_THREADS             IL_TILE_W, IL_TILE_H, IL_THREADS as csrc/image_loss.hpp defines them
+  CASES / case_inputs / tiles / parts     the case table: sizes, views, rate, lambda, content; inputs from the case's seed; a case's
+                                          tile grid and the (tile, channel) partial sums of one of its views
   GRAD_FLOOR / TERM_FLOOR / grad_error    the accuracy bars' floors and the gradient metric e = max|g - g64| / max|g64| per view
-  measure                                 one case through the library against both formulations: every figure the bars are about"""
+  figures / measure                       the library's results of a case against both formulations: every figure the bars are about
+  offset_view / guards_hold / run_library_offset   a tensor as a view some floats into a larger allocation of guard words; a case run
+                                          on such views"""
 import os
 import re
 from collections import namedtuple
@@ -76,12 +79,17 @@ def brute_terms(image, target, lam):
     return np.array([l1, ssim, mse, (1 - lam) * l1 + lam * (1 - ssim)])
 
 
-def tile_constants():
+def _constants(*names):
     text = open(os.path.join(ROOT, "gaussian-pcloud-render_amd", "csrc", "image_loss.hpp")).read()
-    return tuple(int(re.search(r"constexpr int %s = (\d+);" % n, text).group(1)) for n in ("IL_TILE_W", "IL_TILE_H"))
+    return tuple(int(re.search(r"constexpr int %s = (\d+);" % n, text).group(1)) for n in names)
+
+
+def tile_constants():
+    return _constants("IL_TILE_W", "IL_TILE_H")
 
 
 TW, TH = tile_constants()
+IL_THREADS, = _constants("IL_THREADS")      # the lanes of k_image_loss_sum: partial i goes to lane i % IL_THREADS
 Case = namedtuple("Case", "name V W H ss lam content seed")
 CASES = (
     Case("1x1", 1, 1, 1, 1, 0.2, "noise", 1),
@@ -102,7 +110,24 @@ CASES = (
     Case("smooth,37x19", 1, 37, 19, 1, 1.0, "smooth", 16),
     Case("constant", 1, 40, 24, 1, 0.2, "constant", 17),
     Case("identical", 1, 37, 19, 1, 0.2, "identical", 18),
+    # more partial sums than k_image_loss_sum has lanes (its index wraps), and tile grids that are not square
+    Case("long", 1, 11 * TW, 8 * TH, 1, 0.2, "noise", 19),                     # 264 parts, 11 x 8 tiles, 16-B rows
+    Case("long,odd", 2, 11 * TW - 3, 8 * TH - 1, 1, 0.2, "smooth", 20),        # the same on element loads, partial last tiles both ways
+    Case("ss2,long", 1, 9 * TW + 4, 10 * TH, 2, 0.2, "noise", 21),             # 300 parts at rate 2, taller than wide
+    Case("ss2,odd,tiles", 1, TW + 5, 2 * TH + 3, 2, 0.2, "noise", 22),         # rate 2 on element loads across tile borders, 2 x 3 tiles
+    Case("3x1", 1, 3 * TW, TH, 1, 0.2, "noise", 23),                           # one row of tiles
+    Case("1x3", 1, TW, 3 * TH, 1, 0.2, "noise", 24),                           # ... and one column
 )
+
+
+def tiles(c):
+    """(tiles_x, tiles_y) of a case's loss-resolution frame"""
+    return -(-c.W // TW), -(-c.H // TH)
+
+
+def parts(c):
+    """the (tile, channel) partial sums of one view: il_parts of csrc/image_loss.hpp"""
+    return tiles(c)[0] * tiles(c)[1] * 3
 
 
 def case_inputs(c):
@@ -167,10 +192,65 @@ def run_library(N, c, dev, dL=None, with_state=True):
     return terms, grad, state
 
 
-def measure(N, c, dev):
-    """every figure the accuracy bars are about, per view: e, e32 (gradient), term_err, term_err32 ([V,3], absolute), terms, grad"""
+_GUARD = 0x7FC0FEED      # a NaN pattern no kernel produces
+_PAD = 8                 # guard words on either side (a multiple of 4: `shift` alone decides the alignment)
+
+
+def offset_view(t, shift, fill=None):
+    """(whole allocation, view shaped like t): a copy of the float32 device tensor t -- or, with fill, that value -- `shift` floats
+    past a 16-B boundary, inside an allocation whose other words hold a guard pattern"""
+    n = t.numel()
+    whole = torch.full((2 * _PAD + shift + n,), _GUARD, dtype=torch.int32, device=t.device).view(torch.float32)
+    view = whole[_PAD + shift:_PAD + shift + n].view(t.shape)
+    view.copy_(t) if fill is None else view.fill_(fill)
+    assert view.is_contiguous() and (view.data_ptr() % 16 == 0) == (shift % 4 == 0)
+    return whole, view
+
+
+def guards_hold(whole, view):
+    w, n = whole.view(torch.int32), view.numel()
+    at = (view.data_ptr() - whole.data_ptr()) // 4
+    return bool((w[:at] == _GUARD).all()) and bool((w[at + n:] == _GUARD).all())
+
+
+def run_library_offset(N, c, dev, shift_inputs, shift_out):
+    """The case with image and target `shift_inputs` floats and the gradient `shift_out` floats past a 16-B boundary (the state block
+    starts 4 B into its allocation; the entry aligns it, as it does for every caller).  The forward goes through the C ABI itself so
+    that loss_terms too lies between guard words.  Asserts that the words around every output and the inputs hold: (terms, grad)."""
+    img, tgt = references(c)[:2]
+    x0, y0 = torch.from_numpy(img.copy()).to(dev), torch.from_numpy(tgt.copy()).to(dev)
+    held = dict(image=offset_view(x0, shift_inputs), target=offset_view(y0, shift_inputs),
+                terms=offset_view(torch.empty((c.V, 4), device=dev), 1, fill=float("nan")),
+                grad=offset_view(x0, shift_out, fill=float("nan")))
+    x, y, terms, out = (held[k][1] for k in ("image", "target", "terms", "grad"))
+    nbytes, pad = int(N.lib.gsr_image_loss_state_bytes(c.V, c.W, c.H)), 64 + 4
+    block = torch.full((pad + nbytes + pad,), 0x5A, dtype=torch.uint8, device=dev)
+    state = block[pad:pad + nbytes].fill_(255)
+    rc = N.lib.gsr_image_loss_forward(c.V, c.W, c.H, c.ss, float(c.lam), x.data_ptr(), y.data_ptr(), terms.data_ptr(), state.data_ptr(),
+                                      state.numel(), torch.cuda.current_stream(dev).cuda_stream)
+    assert rc == 0, N.lib.gsr_last_error()
+    grad = N.image_loss_backward(x, y, c.lam, c.ss, state, out=out)
+    assert grad.data_ptr() == out.data_ptr()
+    for name, (whole, view) in held.items():
+        assert guards_hold(whole, view), "%s: a word next to %s was written" % (c.name, name)
+    assert bool((block[:pad] == 0x5A).all()) and bool((block[pad + nbytes:] == 0x5A).all()), "%s: a byte next to the state was written" % c.name
+    assert torch.equal(x, x0) and torch.equal(y, y0)
+    return terms.clone(), grad.clone()
+
+
+def figures(c, terms, grad=None):
+    """every figure the accuracy bars are about, per view, of the library's terms (and gradient) of a case: e, e32 (gradient),
+    term_err, term_err32 ([V,3], absolute), terms, grad"""
     _, _, t64, g64, t32, g32 = references(c)
+    terms = terms.cpu().double().numpy()
+    out = dict(term_err=np.abs(terms[:, :3] - t64[:, :3]), term_err32=np.abs(t32[:, :3] - t64[:, :3]), terms=terms)
+    if grad is not None:
+        grad = grad.cpu().double().numpy()
+        out.update(e=grad_error(grad, g64), e32=grad_error(g32, g64), grad=grad)
+    return out
+
+
+def measure(N, c, dev):
+    """figures of the case run through the library"""
     terms, grad, _ = run_library(N, c, dev)
-    terms, grad = terms.cpu().double().numpy(), grad.cpu().double().numpy()
-    return dict(e=grad_error(grad, g64), e32=grad_error(g32, g64), term_err=np.abs(terms[:, :3] - t64[:, :3]),
-                term_err32=np.abs(t32[:, :3] - t64[:, :3]), terms=terms, grad=grad)
+    return figures(c, terms, grad)

@@ -71,6 +71,65 @@ def test_the_case_table_reaches_the_kernel_s_edges():
             assert (1 - float(R.F(R.BETA2))) * float(np.abs(g).min()) ** 2 > 2.0 ** -126
 
 
+def _split_of(c):
+    """(units, workgroups per group, rounds per group, how often each round is taken per group) of a case's call"""
+    units, blocks = R.work_split(c.P, c.widths)
+    rounds = [R.div_up(c.P * w, R.BLOCK) for w in c.widths]
+    taken = [R.rounds_taken(c.P * w, nb, R.on_vector_path(c, w)) for w, nb in zip(c.widths, blocks)]
+    return units, blocks, rounds, taken
+
+
+@pytest.mark.parametrize("c", R.CASES + R.CAP_CASES + (R.BENCH_SHAPE,), ids=[c.name for c in R.CASES + R.CAP_CASES + (R.BENCH_SHAPE,)])
+def test_work_split_takes_every_round_of_every_group_exactly_once(c):
+    """the entry's block_end table and the kernel's two grid-stride loops, restated at the granularity of one round"""
+    units, blocks, rounds, taken = _split_of(c)
+    assert units == sum(rounds)
+    assert all(nb >= 1 for nb in blocks), (c.name, blocks)
+    assert sum(blocks) <= R.MAX_BLOCKS + len(c.widths) - 1, (c.name, blocks)
+    for k, (r, t) in enumerate(zip(rounds, taken)):
+        assert len(t) == r and (t == 1).all(), (c.name, k, np.flatnonzero(t != 1)[:5])
+    if units <= R.MAX_BLOCKS:
+        assert blocks == rounds                      # below the cap every round has its own workgroup
+
+
+def test_the_cap_cases_are_what_they_claim_to_be():
+    assert R.BLOCK == R.VEC * R.THREADS and [c.name for c in R.CAP_CASES] == list(R.CAP_CLAIMS)
+    for c in R.CASES:                                # the first table stops short of the cap, which is why the second exists
+        assert R.work_split(c.P, c.widths)[0] <= R.MAX_BLOCKS
+    for c in R.CAP_CASES:
+        units, blocks, rounds, _ = _split_of(c)
+        second, floored = R.CAP_CLAIMS[c.name]
+        assert units > R.MAX_BLOCKS, (c.name, units)
+        assert units <= R.MAX_BLOCKS + R.MAX_BLOCKS // 16, (c.name, units)          # ... and just above it: no larger than it has to be
+        for k in second:                             # a workgroup with (at least) two rounds
+            assert rounds[k] > blocks[k], (c.name, k, rounds[k], blocks[k])
+        for k in range(len(c.widths)):
+            share = rounds[k] * R.MAX_BLOCKS // units
+            assert (share == 0) == (k in floored) and blocks[k] == max(share, 1), (c.name, k, share)
+    w48, off1, floor, cloud = R.CAP_CASES
+    assert R.work_split(w48.P, w48.widths) == (R.MAX_BLOCKS + 1, [R.MAX_BLOCKS]) and R.on_vector_path(w48, 48)
+    assert 0 < (w48.P * 48) % R.BLOCK < R.BLOCK      # workgroup 0's second round is a partial one
+    assert off1.offset_rows == 1 and not any(R.on_vector_path(off1, w) for w in off1.widths)
+    assert floor.widths[1] == R.MAX_BLOCKS + 1 and floor.widths[1] % 2 == 1 and floor.P * floor.widths[0] <= R.BLOCK
+    assert cloud.widths == R.BENCH_SHAPE.widths and (cloud.P * 3) % R.VEC != 0 and cloud.P % R.VEC != 0
+    assert all(R.on_vector_path(cloud, w) for w in cloud.widths)
+    # the two halves of the cloud case: together every row, each below the cap, the cut no multiple of 4
+    (a0, b0), (a1, b1) = R.CAP_CLOUD_HALVES
+    assert (a0, b0, b1) == (0, a1, cloud.P) and a1 % R.VEC != 0
+    assert all(R.work_split(b - a, cloud.widths)[0] <= R.MAX_BLOCKS for a, b in R.CAP_CLOUD_HALVES)
+    # the share arithmetic itself, on hand values: a round each up to the cap, floored shares above it, never none
+    assert R.group_blocks(5 * R.BLOCK + 1, R.MAX_BLOCKS) == 6 and R.group_blocks(5 * R.BLOCK + 1, R.MAX_BLOCKS + 1) == 5
+    assert R.group_blocks(1, 10 * R.MAX_BLOCKS) == 1 and R.group_blocks(30 * R.BLOCK, 10 * R.MAX_BLOCKS) == 3
+    # the benchmark cloud runs the capped path with several rounds per workgroup
+    units, blocks, rounds, _ = _split_of(R.BENCH_SHAPE)
+    assert units > 2 * R.MAX_BLOCKS and all(r >= 2 * b for r, b in zip(rounds, blocks))
+    # the mask kernel's own stride loop needs more Gaussians than its capped grid has lanes
+    assert R.div_up(R.VISIBLE_CAP_P, R.THREADS) == R.MAX_BLOCKS + 1
+    # the inputs of the big cases are the table's: no subnormal intermediate
+    p, g, m, v = R.case_inputs(floor)[0]
+    assert 1e-6 * 0.999 <= np.abs(g).min() and np.abs(g).max() <= 1e2 * 1.001 and v.min() > 0
+
+
 @pytest.mark.parametrize("c", R.CASES, ids=[c.name for c in R.CASES])
 def test_float32_restatement_meets_the_single_step_bars(c):
     worst = np.zeros(3)

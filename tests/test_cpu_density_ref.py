@@ -114,7 +114,27 @@ def test_every_action_and_every_threshold_side_occurs_in_the_cases():
     # the P that needs a second round of the scan of the workgroup counts, from the kernel's constants
     blocks = -(-R.TWO_ROUNDS_P // R.THREADS)
     assert blocks == R.SCAN_ROUND + 1 and any(c.P == R.TWO_ROUNDS_P for c in R.CASES)
+    # ... and the P that needs a third
+    assert -(-R.THREE_ROUNDS_P // R.THREADS) == 2 * R.SCAN_ROUND + 1 and R.CASES[-1].P == R.THREE_ROUNDS_P
     assert max(i["P"] for i in inputs) <= 300_000
+    # the eight-group gather above its grid cap (DENSITY_MAX_BLOCKS rounds of DENSITY_BLOCK_ELEMS): some case's call has a workgroup
+    # with a second round in EVERY group, and the last case's has workgroups with a third; every round is taken exactly once
+    assert R.BLOCK == R.VEC * R.THREADS
+    splits = {}
+    for c, i in zip(R.CASES, inputs):
+        groups = R.case_groups(i)
+        widths = [int(np.prod(src.shape[1:])) for _, src, _ in groups]
+        P_out = int(R.plan_of(R.case_actions(i))[2][0])
+        units, blocks, rounds = splits[c.name] = R.apply_split(P_out, widths)
+        assert sum(blocks) <= R.MAX_BLOCKS + len(widths) - 1 and all(b >= 1 for b in blocks) or P_out == 0
+        for (_, _, role), w, nb, r in zip(groups, widths, blocks, rounds):
+            vec = role in (R.COPY, R.MOMENT) and w % R.VEC == 0
+            assert P_out == 0 or (R.adam_ref.rounds_taken(P_out * w, nb, vec, R.BLOCK) == 1).all(), (c.name, w)
+    above = {name: s for name, s in splits.items() if s[0] > R.MAX_BLOCKS}
+    print({name: s[0] for name, s in above.items()})
+    assert any(all(r > b for b, r in zip(s[1], s[2])) for name, s in above.items() if name != R.CASES[-1].name), above
+    units, blocks, rounds = splits[R.CASES[-1].name]
+    assert units > 2 * R.MAX_BLOCKS and any(r > 2 * b for b, r in zip(blocks, rounds))
     # the log-scale cases leave fewer than 0.1 % of their rows out of the exact comparison
     for c, i in zip(R.CASES, inputs):
         if c.log:

@@ -53,7 +53,16 @@ def test_case_table_is_seeded_and_covers_the_kernel_paths():
         assert want in sizes, want
     assert any(c.W % 2 == 1 and c.W % 4 != 0 for c in R.CASES) and {0.0, 0.2, 1.0} <= {c.lam for c in R.CASES}
     assert {"noise", "smooth", "constant", "identical"} == {c.content for c in R.CASES} and any(c.V == 3 for c in R.CASES)
-    assert len({c.name for c in R.CASES}) == len(R.CASES)
+    assert len({c.name for c in R.CASES}) == len(R.CASES) and len({c.seed for c in R.CASES}) == len(R.CASES)
+    # more partial sums than k_image_loss_sum has lanes -- on 16-B rows, on element loads and at rate 2 -- and tile grids that are
+    # wider than tall and taller than wide (il_tile's tile % tiles_x, tile / tiles_x), a single row and a single column of tiles
+    long = [c for c in R.CASES if R.parts(c) > R.IL_THREADS]
+    assert any(c.W % 4 == 0 and c.ss == 1 for c in long) and any(c.W % 4 != 0 and c.ss == 1 for c in long) and any(c.ss == 2 for c in long)
+    assert R.parts(R.CASES[3]) == 3 and R.tiles(R.CASES[4]) == (2, 2)
+    grids = {R.tiles(c) for c in R.CASES}
+    assert any(x > y > 1 for x, y in grids) and any(y > x > 1 for x, y in grids) and {(3, 1), (1, 3)} <= grids
+    assert any(c.ss == 2 and c.W % 4 != 0 and min(R.tiles(c)) > 1 for c in R.CASES)      # rate 2 on element loads across tile borders
+    assert max(c.V * c.W * c.H * c.ss * c.ss for c in R.CASES) <= 2 ** 19                # the float64 reference stays a second or two
     for c in R.CASES[:3] + R.CASES[-2:]:
         a, b = R.case_inputs(c), R.case_inputs(c)
         assert a[0].shape == (c.V, 3, c.H * c.ss, c.W * c.ss) and a[1].shape == (c.V, 3, c.H, c.W) and a[0].dtype == np.float32

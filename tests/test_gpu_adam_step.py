@@ -1,6 +1,7 @@
 """The fused Adam step on the device (gsr_adam_step / gsr_visible_from_radii, pcrender.optim.GaussianAdam) against the definition in
 float64 (adam_ref), on the smallest shapes at which the kernel can go wrong: the case table names them with the kernel's own constants.
 Every array sits between guard rows, masked rows are compared with the inputs bit for bit, and the mask output is prefilled.
+The capped grid and its multi-round loops -- what a training cloud runs -- need 8 M elements: adam_ref.CAP_CASES, one test each.
 
 Single-step bars (adam_ref.check_step; EPS = 2^-24, none taken from the kernel's results):
     |m' - m64| <= 4 EPS (|b1 m| + |c1 g|),  |v' - v64| <= 5 EPS v64,  |p' - (p - u64)| <= EPS |p - u64| + 8 EPS |u64|
@@ -114,6 +115,67 @@ def test_visible_from_radii_is_exact(N, dev, V, P):
     assert (N.visible_from_radii(r).cpu().numpy() == want.astype(np.uint8)).all()
     if V == 1:                                                            # the [P] radii of a single-view call
         assert (N.visible_from_radii(r[0].contiguous()).cpu().numpy() == want.astype(np.uint8)).all()
+
+
+def _gradients_as_the_flag_says(out, inputs, flag, what):
+    for o, i in zip(out, inputs):          # exactly 0 under zero_grads, the input's bits without it
+        assert (not o[3].view(np.uint32).any()) if flag else R.same_bits(o[3], i[1]), what
+
+
+CAP_RUNS = ((None, 1, False), ("random30", 3, True))     # mask kind, step count, zero_grads
+
+
+@pytest.mark.parametrize("c", R.CAP_CASES, ids=[c.name for c in R.CAP_CASES])
+def test_above_the_grid_cap_every_element_against_float64(N, dev, c):
+    """More rounds than ADAM_MAX_BLOCKS (adam_ref.cap_cases says what each case reaches): a capped grid, floor-divided shares and
+    workgroups that walk a second round -- what every call on a training cloud runs.  EVERY element is held to the single-step bars:
+    a round that is skipped or taken twice shows in its own elements alone."""
+    assert R.work_split(c.P, c.widths)[0] > R.MAX_BLOCKS
+    before = N.lib.gsr_d2h_count()
+    for kind, t, flag in CAP_RUNS:
+        what = "%s %s t=%d" % (c.name, kind or "dense", t)
+        out, inputs, vis = R.run_library(N, c, dev, kind, t, zero_grads=flag)     # (asserts that the guard rows are intact)
+        worst = np.zeros(3)
+        for k, (got, inp) in enumerate(zip(out, inputs)):
+            worst = np.maximum(worst, R.check_step_in_ranges(got[:3], inp, c.lrs[k], t, vis, "%s group %d (width %d)" % (what, k, c.widths[k])))
+        _gradients_as_the_flag_says(out, inputs, flag, what)
+        print("%s: worst error / bar  m %.3f  v %.3f  p %.3f" % (what, *worst))
+    assert N.lib.gsr_d2h_count() == before
+    torch.cuda.empty_cache()               # (the case's 140 MB blocks go back: the tests after this one find the allocator as before)
+
+
+def test_the_cloud_above_the_cap_in_two_halves_below_it_carries_the_same_bits(N, dev):
+    """neither the workgroup nor the path enters a result: the rows of cap,cloud submitted as two calls, each below the cap and the
+    second from a row that is no multiple of 4 (its width-3 and width-1 groups lose their alignment), against the one call"""
+    c = R.case("cap,cloud")
+    kind, t, flag = CAP_RUNS[1]
+    whole, inputs, _ = R.run_library(N, c, dev, kind, t, zero_grads=flag)
+    for a, b in R.CAP_CLOUD_HALVES:
+        part, _, _ = R.run_library(N, c, dev, kind, t, zero_grads=flag, rows=(a, b))
+        for k in range(len(c.widths)):
+            assert all(R.same_bits(x[a:b], y[a:b]) for x, y in zip(part[k], whole[k])), (k, a, b)
+            for j, s in ((0, 0), (1, 2), (2, 3), (3, 1)):                                           # the other half stays
+                assert R.same_bits(part[k][j][:a], inputs[k][s][:a]) and R.same_bits(part[k][j][b:], inputs[k][s][b:]), (k, a, b)
+    torch.cuda.empty_cache()
+
+
+def test_visible_from_radii_past_its_grid_cap(N, dev):
+    """one Gaussian more than ADAM_MAX_BLOCKS workgroups have lanes: the kernel's stride loop runs a second round, for the last one"""
+    V, P = 2, R.VISIBLE_CAP_P
+    rng = np.random.default_rng(100 * V + 7)
+    radii = rng.choice(np.array([-7, -1, 0, 0, 0, 0, 0, 0, 0, 1, 2, 300], np.int32), (V, P))
+    radii[:, P - 1] = 0
+    radii[V - 1, P - 1] = 9                       # the last Gaussian is positive in the last view alone
+    radii[:, 0] = -5
+    want = (radii > 0).any(0)
+    assert want[P - 1] and not want[0] and 0.3 < want.mean() < 0.7
+    r = torch.from_numpy(radii).to(dev)
+    out = torch.full((P + 2,), 255, dtype=torch.uint8, device=dev)
+    got = N.visible_from_radii(r, out=out[1:P + 1])
+    assert got.data_ptr() == out[1:].data_ptr() and out[0] == 255 and out[P + 1] == 255
+    assert (got.cpu().numpy() == want.astype(np.uint8)).all()             # every element written: 0 or 1, never the prefill
+    del r, out, got
+    torch.cuda.empty_cache()
 
 
 def _device_trajectory(N, dev, q, masked):

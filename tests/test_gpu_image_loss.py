@@ -1,6 +1,7 @@
 """The fused photometric loss on the device (gsr_image_loss_forward / gsr_image_loss_backward, pcrender.losses) against the float64
 reference of image_loss_ref, on the smallest shapes at which the kernels can go wrong (the case table names them with the kernel's
-own tile constants).  Every output is prefilled with NaN before every call.
+own tile constants; the `long` cases have more partial sums than the sum kernel has lanes).  Every output is prefilled with NaN
+before every call.
 
 Accuracy bars (per view, none taken from the kernel's own results): the gradient metric e = max|g - g64| / max|g64| is at most
 max(4 e32, 64 2^-24), e32 being the float32 torch formulation's e on the same case -- 4 for the other summation order (two 11-tap
@@ -53,6 +54,45 @@ def test_terms_and_gradient_against_float64(N, dev, c):
         lam = float(np.float32(c.lam))
         want = (1.0 - lam) * t[0] + lam * (1.0 - t[1])
         assert abs(t[3] - want) <= 2.0 ** -24 * abs(want), (c.name, v, t, want)
+
+
+def _assert_the_bars(c, r, what):
+    """the module's bars on figures of image_loss_ref.figures: the terms, and the gradient where there is one"""
+    assert np.isfinite(r["terms"]).all()
+    for v in range(c.V):
+        for k in range(3):
+            assert r["term_err"][v, k] <= max(4 * r["term_err32"][v, k], R.TERM_FLOOR), (what, v, k, r["term_err"][v], r["term_err32"][v])
+        if "e" in r:
+            assert np.isfinite(r["grad"]).all() and r["e"][v] <= max(4 * r["e32"][v], R.GRAD_FLOOR), (what, v, r["e"][v], r["e32"][v])
+
+
+@pytest.mark.parametrize("name", ["long", "long,odd"])
+def test_metrics_only_forward_past_the_sum_kernel_s_lanes(N, dev, name):
+    """more (tile, channel) pairs than IL_THREADS: the metrics-only walk adds pair i to accumulator i % IL_THREADS, the state path's
+    k_image_loss_sum gives lane t the partials i = t mod IL_THREADS -- both against float64, and the same bits (the header's promise)"""
+    c = _case(name)
+    assert R.parts(c) > R.IL_THREADS
+    with_state, _, _ = R.run_library(N, c, dev)
+    metrics, _, _ = R.run_library(N, c, dev, with_state=False)
+    r = R.figures(c, metrics)
+    print("%s: term errors %s (float32 formulation %s)" % (c.name, r["term_err"].tolist(), r["term_err32"].tolist()))
+    _assert_the_bars(c, r, c.name + " metrics only")
+    _assert_the_bars(c, R.figures(c, with_state), c.name + " with a state")
+    assert torch.equal(metrics, with_state)
+
+
+@pytest.mark.parametrize("name", ["40x24", "long"])
+def test_misaligned_pointers_with_16_byte_rows_carry_the_aligned_bits(N, dev, name):
+    """W % 4 == 0 on pointers 4 B off a 16-B boundary: image and target (element loads and stores in both directions), then the
+    gradient alone (a 16-B forward followed by an element backward).  The path does not enter a result."""
+    c = _case(name)
+    assert c.W % 4 == 0 and c.ss == 1
+    terms, grad, _ = R.run_library(N, c, dev)
+    _assert_the_bars(c, R.figures(c, terms, grad), c.name)
+    for shift_inputs, shift_out in ((0, 0), (1, 0), (0, 1)):           # (the first: the 16-B path itself between the guard words)
+        t, g = R.run_library_offset(N, c, dev, shift_inputs, shift_out)
+        _assert_the_bars(c, R.figures(c, t, g), (c.name, shift_inputs, shift_out))
+        assert torch.equal(t, terms) and torch.equal(g, grad), (c.name, shift_inputs, shift_out)
 
 
 @pytest.mark.parametrize("name", ["64x48,V=3", "ss2,17x16,V=3"])
