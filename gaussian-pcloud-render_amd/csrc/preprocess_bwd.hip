@@ -128,6 +128,7 @@ __global__ __launch_bounds__(256) void k_preprocess_backward(PreBwdArgs a)
         for (int i = 0; i < NSH; i++) shv[i] = shp[i];
     }
 
+    bool seen = false;   // visible in some view of the batch
     for (int vw = 0; vw < a.V; vw++) {
         // the render-level sums of this Gaussian in this view: one 64-B record (zeros when nothing was accumulated)
         const float* recp = at_view(a.grad_rec, a.gr_stride, (uint32_t)vw) + (size_t)idx * GRAD_REC_WORDS;
@@ -138,6 +139,7 @@ __global__ __launch_bounds__(256) void k_preprocess_backward(PreBwdArgs a)
         gcol = gcol + v3(rec1.y, rec1.z, rec1.w);
         gop += rec8;
         if (!(a.radii[(size_t)vw * a.P + idx] > 0)) continue;   // invisible in this view: no geometric gradient
+        seen = true;
 
         const float* view = a.view + 16 * vw;
         const float* proj = a.proj + 16 * vw;
@@ -230,7 +232,9 @@ __global__ __launch_bounds__(256) void k_preprocess_backward(PreBwdArgs a)
     // writes each array's 256 rows as one run of 16-B chunks.
     float dsc[3] = {0.f, 0.f, 0.f};
     float4 dq = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a.scales) scale_rot_backward(sc, q, a.scale_modifier, gS, dsc, dq);
+    // (a Gaussian no view saw keeps the +0 of dsc and dq, what the reference's zero-filled outputs hold for it: the products of
+    // its quaternion with the zero sums gS would leave -0 in dL_drot)
+    if (a.scales && seen) scale_rot_backward(sc, q, a.scale_modifier, gS, dsc, dq);
     if (a.stage_out) {
         __syncthreads();   // the dL_dsh rows have left the staging area
         float* o = s_rows;

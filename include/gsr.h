@@ -97,7 +97,15 @@ typedef struct gsr_params {
 } gsr_params;
 
 /* Scratch arena sizes in bytes for ONE view (256-B aligned sub-arrays inside); a batch of V views needs V times as much.
- * gsr_binning_bytes(n) is an arena that holds n pairs per view: the library derives the capacity from the arena's size. */
+ * gsr_binning_bytes(n) is an arena that holds n pairs per view: the library derives the capacity from the arena's size.
+ * The arena contract.  Arenas (and the extra-state block of the channels calls) need NOT be initialised: any bytes will do,
+ * the bytes of an earlier frame included -- the usual state in a training loop, where every frame renders into the allocation of
+ * the one before.  What they hold between calls is the library's: a caller neither reads nor changes it between a forward and the
+ * calls that follow it on the same arenas.  No result of a call depends on what the arenas held BEFORE the forward (or the stage
+ * pair) that starts a frame: every output, private list and gradient is the one the same calls give on zero-filled arenas, bit for
+ * bit wherever this header promises repeatable bits, with another V, another need_backward, another arithmetic mode or another
+ * kind of call (colour, channels, recolor, a retried and resumed frame) before it (tests/test_gpu_arena_state.py; which kernel writes
+ * and reads which part under which condition: DESIGN.md section 6). */
 size_t gsr_geom_bytes(int P);
 /* The geometry arena of a call with need_backward = 0 (inference): without the 64-B per-Gaussian gradient records that only
  * the backward accumulates into (they follow the V per-view arenas inside the allocation, so the layout of everything else

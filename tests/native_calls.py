@@ -13,6 +13,10 @@ are imported inside the functions).
                                              a forward's arguments and run tuple, permuted for the call that follows it
   colour_backward / channels_backward        forward + backward, numpy gradient dicts
   longest_list                               the longest tile list of a batch
+  alloc_arenas / forward_on / stage_pair_on / colour_det_backward_on / ckpt_region
+                                             the raw calls on caller-given arenas: a zero-filled set, a (channels-train, resumed)
+                                             forward, the stage pair, the deterministic colour backward with a given scratch block,
+                                             and the bytes of a view's slice-boundary states inside the binning arena
   render_math / half_views / train_math / moments / reference_lists
                                              a switch set for a block and restored whatever happens inside
   RGB_TOL / RENDER_SCENES / renders          the inference renders of the test scenes in both arithmetic modes, rendered once"""
@@ -165,6 +169,108 @@ def longest_list(N, geom, binning, img, counts, P, W, H, V):
         r = N.query("RANGES", P, W, H, counts[v], geom, binning, img, view=v, n_views=V).reshape(-1, 2).long()
         best = max(best, int((r[:, 1] - r[:, 0]).max()))
     return best
+
+
+# ---- raw calls on caller-given arenas --------------------------------------------------------------------------------------------
+def alloc_arenas(N, P, W, H, V, capacity, dev, nx=0):
+    """(geom, binning, img, extra state or None): zero-filled arenas of V views with need_backward, the binning arena for
+    `capacity` pairs per view, the extra-state block for nx channels at that capacity"""
+    import torch
+    z = lambda n: torch.zeros((int(n),), dtype=torch.uint8, device=dev)  # noqa: E731
+    return (z(V * N.lib.gsr_geom_bytes(P)), z(V * N.lib.gsr_binning_bytes(int(capacity))), z(V * N.lib.gsr_image_bytes(W, H)),
+            z(V * N.lib.gsr_extra_state_bytes(W, H, int(capacity), nx) + 256) if nx else None)
+
+
+def forward_on(N, args, geom, binning, img, need_backward, resume=0, extra=None, xstate=None, out=None):
+    """gsr_forward_batch on the given arenas -- with extra = (values, view scales or None, bg_extra): gsr_forward_batch_channels_train
+    into the block xstate (need_backward) or gsr_forward_batch_channels.  Returns (status, run): run = (counts, color, radii, geom,
+    binning, img[, out_extra]) like rasterize_gaussians_batch.  out: the output tensors (color, radii, out_extra) of an earlier
+    attempt, for a resumed call.  (fp64_pins.raw_forward is the older, narrower form -- colour only, no resume, status asserted,
+    counts dropped -- and stays as the tests that import it have it)"""
+    import ctypes as C
+    import torch
+    dev = args[MEANS3D].device
+    P, V, H, W = args[MEANS3D].shape[0], args[VIEWMATRIX].numel() // 16, args[HEIGHT], args[WIDTH]
+    nx = 0
+    if extra is not None:
+        nx, layout, xv, xs, xb = N._extra_layout(extra, P, V, dev)
+        xv, xs, xb = N._extra_f32(xv, xs, xb, dev)
+    if out is None:
+        out = (torch.empty((V, 3, H, W), dtype=torch.float32, device=dev), torch.empty((V, P), dtype=torch.int32, device=dev),
+               torch.empty((V, nx, H, W), dtype=torch.float32, device=dev) if nx else None)
+    color, radii, out_x = out
+    p, keep = N._params(*args, need_backward=need_backward)
+    counts = (C.c_int64 * V)()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        head = (C.byref(p), V, geom.data_ptr(), geom.numel(), img.data_ptr(), img.numel(), binning.data_ptr(), binning.numel(),
+                radii.data_ptr(), color.data_ptr(), counts, int(resume))
+        if not nx:
+            rc = N.lib.gsr_forward_batch(*head, stream)
+        else:
+            x = (nx, layout, xv.data_ptr(), None if xs is None else xs.data_ptr(), xb.data_ptr(), out_x.data_ptr())
+            if need_backward:
+                rc = N.lib.gsr_forward_batch_channels_train(*head, *x, xstate.data_ptr(), xstate.numel(), stream)
+            else:
+                rc = N.lib.gsr_forward_batch_channels(*head, *x, stream)
+    torch.cuda.synchronize()
+    del keep
+    run = ([int(c) for c in counts], color, radii, geom, binning, img)
+    return rc, run + ((out_x,) if nx else ())
+
+
+def stage_pair_on(N, args, geom, binning, img):
+    """gsr_forward_stage1 + gsr_forward_stage2 of ONE view (args with [1,4,4] matrices) on the given arenas; returns the run tuple"""
+    import ctypes as C
+    import torch
+    dev = args[MEANS3D].device
+    P, H, W = args[MEANS3D].shape[0], args[HEIGHT], args[WIDTH]
+    color = torch.empty((1, 3, H, W), dtype=torch.float32, device=dev)
+    radii = torch.empty((1, P), dtype=torch.int32, device=dev)
+    p, keep = N._params(*args, need_backward=True)
+    n = (C.c_int64 * 1)()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = N.lib.gsr_forward_stage1(C.byref(p), geom.data_ptr(), geom.numel(), img.data_ptr(), img.numel(), radii.data_ptr(), n, stream)
+        assert rc == 0, N.lib.gsr_last_error()
+        rc = N.lib.gsr_forward_stage2(C.byref(p), geom.data_ptr(), geom.numel(), binning.data_ptr(), binning.numel(), img.data_ptr(),
+                                      img.numel(), n[0], color.data_ptr(), stream)
+        assert rc == 0, N.lib.gsr_last_error()
+    torch.cuda.synchronize()
+    del keep
+    return ([int(n[0])], color, radii, geom, binning, img)
+
+
+def colour_det_backward_on(N, args, run, dL, scratch):
+    """gsr_backward_batch_det on the arenas of `run` with the caller's scratch block: the numpy gradient dict"""
+    import torch
+    a = colour_backward_args(args, run, dL)
+    dev = args[MEANS3D].device
+    with torch.cuda.device(dev):
+        p, keep, radii, dpix = N._bwd_inputs(*a[:16], False)
+        g = N._grad_tensors(p.P, p.M, dev, args[SCALES].numel() != 0)
+        head = N._bwd_head(p, int(dL.shape[0]), radii, N._arena_args(*a[16:19]), dpix, g)
+        rc = N.lib.gsr_backward_batch_det(*head, scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize()
+    assert rc == 0, N.lib.gsr_last_error()
+    del keep
+    return {n: t.cpu().numpy() for n, t in zip(util.GRAD_NAMES, g)}
+
+
+CKPT_SHIFT = 9            # common.hpp BWD_CHUNK_SHIFT_MIN: the boundary-state area is carved for slices of 512 entries
+CKPT_SLOT_BYTES = 4096    # 256 float4 per slot (tests/test_cpu_arena_cases.py holds both to the header)
+
+
+def ckpt_region(N, binning, V, v):
+    """the bytes of view v's slice-boundary states (BinView::ckpt, the last array of a view's binning arena) in a binning arena of
+    V views, as a view of the tensor: common.hpp bin_view / bin_capacity_from_bytes restated"""
+    per_view = ((binning.numel() - 256) // V) // 256 * 256
+    lo, hi = 1, per_view // 16 + 1
+    while lo < hi:                              # the largest capacity whose arena fits a view's share
+        mid = lo + (hi - lo + 1) // 2
+        lo, hi = (mid, hi) if N.lib.gsr_binning_bytes(mid) - 256 <= per_view else (lo, mid - 1)
+    end = N.lib.gsr_binning_bytes(lo) - 256
+    return binning[v * per_view + end - ((lo >> CKPT_SHIFT) + 2) * CKPT_SLOT_BYTES:v * per_view + end]
 
 
 # ---- the switches -----------------------------------------------------------------------------------------------------------------
