@@ -18,7 +18,7 @@ LIB = os.path.join(OUT_DIR, "libgsr_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 UNITS = ["api", "host", "inspect", "preprocess", "sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "det_backward", "camera_bwd",
-         "view_stats", "contrib_stats", "image_loss", "adam_step", "density_control"]
+         "view_stats", "contrib_stats", "image_loss", "adam_step", "density_control", "cloud_geometry"]
 
 # -ffp-contract=off : one rounding per written operation (integer outputs reproducible, DESIGN.md "Numerics")
 # -munsafe-fp-atomics: float atomicAdd -> global_atomic_add_f32 / ds_add_f32 instead of a CAS loop

@@ -75,6 +75,9 @@ _DECL = {
     "gsr_density_scratch_bytes": (_size, [_int]),
     "gsr_density_plan": (_int, [_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _size, _fp]),
     "gsr_density_apply": (_int, [_int, _int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _fp]),
+    "gsr_knn_scratch_bytes": (_size, [_int, _int]),
+    "gsr_knn": (_int, [_int, _fp, _int, _fp, _fp, _fp, _size, _fp]),
+    "gsr_cloud_geometry": (_int, [_int, _fp, _int, _fp, _int, _int, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "gsr_mark_visible": (_int, [_int, _fp, _fp, _fp, _fp, _fp]),
     "gsr_query": (_int, [_pp, _int, _fp, _fp, _size, _fp, _i64, _fp, _size, _fp]),
     "gsr_set_profiling": (None, [_int]),
@@ -1217,6 +1220,74 @@ def density_apply(groups, rule, offsets, action, P_out, scales=None, rotations=N
     with _on_device(device):
         _check(lib.gsr_density_apply(P, len(groups), table, C.addressof(rule), offsets.data_ptr(), action.data_ptr(), _ptr(scales),
                                      _ptr(rotations), _ptr(noise), _ptr(index), P_out, _stream_handle(device)))
+
+
+CLOUD_MAX_K = 32
+CLOUD_OUTPUTS = ("spacing", "cov6", "eigenvalues", "normals", "rotations")      # gsr_cloud_geometry's outputs, in its argument order
+_CLOUD_WIDTH = dict(spacing=(), cov6=(6,), eigenvalues=(3,), normals=(3,), rotations=(4,))
+
+
+def _cloud_points(points, who):
+    if points.dim() != 2 or points.shape[0] < 1 or points.shape[1] != 3:
+        raise ValueError("%s: points must be [P, 3] with P >= 1 (got %s)" % (who, tuple(points.shape)))
+    if points.dtype != _F32 or not points.is_contiguous():
+        raise ValueError("%s: points must be a contiguous torch.float32 tensor (got %s, contiguous: %s)"
+                         % (who, points.dtype, points.is_contiguous()))
+    return points.shape[0]
+
+
+def knn(points, K, want_d2=True):
+    """C ABI gsr_knn: the exact K nearest neighbours of every point of a contiguous float32 [P, 3] cloud, ties to the lower index.
+    Returns (idx int32 [P, K], d2 float32 [P, K] or None), ascending, padded with -1 / +inf; on the device, nothing is read back."""
+    who = "knn"
+    P = _cloud_points(points, who)
+    K = int(K)
+    if not 1 <= K <= CLOUD_MAX_K:
+        raise ValueError("%s: K = %d outside 1..%d" % (who, K, CLOUD_MAX_K))
+    device = points.device
+    _require_hip(device)
+    idx = torch.empty((P, K), dtype=torch.int32, device=device)
+    d2 = torch.empty((P, K), dtype=_F32, device=device) if want_d2 else None
+    nbytes = lib.gsr_knn_scratch_bytes(P, K)
+    scratch = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=device)
+    with _on_device(device):
+        _check(lib.gsr_knn(P, points.data_ptr(), K, idx.data_ptr(), _ptr(d2), scratch.data_ptr(), scratch.numel(), _stream_handle(device)))
+    return idx, d2
+
+
+def cloud_geometry(points, knn_idx, k_s=3, k_n=None, orient_to=None, want=CLOUD_OUTPUTS):
+    """C ABI gsr_cloud_geometry: per-point geometry from neighbour lists.  points float32 [P, 3], knn_idx int32 [P, K] (as knn returns
+    it).  k_s: neighbours of the spacing (3: 3DGS's initial scale), clipped to K; k_n: neighbours of the covariance (None: K).
+    orient_to: three numbers the normals are turned away from, or None.  want: the outputs to compute, names of CLOUD_OUTPUTS.
+    Returns a dict name -> tensor (spacing [P], cov6 [P, 6], eigenvalues [P, 3] ascending, normals [P, 3], rotations [P, 4])."""
+    who = "cloud_geometry"
+    P = _cloud_points(points, who)
+    device = points.device
+    if knn_idx.dtype != torch.int32 or knn_idx.dim() != 2 or knn_idx.shape[0] != P or not knn_idx.is_contiguous() or \
+            not 1 <= knn_idx.shape[1] <= CLOUD_MAX_K:
+        raise ValueError("%s: knn_idx must be a contiguous torch.int32 [P = %d, K in 1..%d] tensor (got %s %s, contiguous: %s)"
+                         % (who, P, CLOUD_MAX_K, knn_idx.dtype, tuple(knn_idx.shape), knn_idx.is_contiguous()))
+    if knn_idx.device != device:
+        raise ValueError("%s: knn_idx is on %s, points on %s" % (who, knn_idx.device, device))
+    K = knn_idx.shape[1]
+    k_s, k_n = min(int(k_s), K), K if k_n is None else int(k_n)
+    if k_s < 1 or not 1 <= k_n <= K:
+        raise ValueError("%s: k_s = %d (at least 1), k_n = %d (1..K = %d)" % (who, k_s, k_n, K))
+    want = tuple(want)
+    if not want or any(w not in CLOUD_OUTPUTS for w in want):
+        raise ValueError("%s: want = %r: one or more of %s" % (who, want, ", ".join(CLOUD_OUTPUTS)))
+    o = None
+    if orient_to is not None:
+        o = [float(v) for v in (orient_to.tolist() if hasattr(orient_to, "tolist") else orient_to)]
+        if len(o) != 3:
+            raise ValueError("%s: orient_to takes three numbers (got %d)" % (who, len(o)))
+        o = (C.c_float * 3)(*o)
+    _require_hip(device)
+    out = {w: torch.empty((P,) + _CLOUD_WIDTH[w], dtype=_F32, device=device) for w in CLOUD_OUTPUTS if w in want}
+    with _on_device(device):
+        _check(lib.gsr_cloud_geometry(P, points.data_ptr(), K, knn_idx.data_ptr(), k_s, k_n, None if o is None else C.addressof(o),
+                                      *[_ptr(out.get(w)) for w in CLOUD_OUTPUTS], _stream_handle(device)))
+    return out
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,

@@ -574,6 +574,73 @@ int gsr_density_apply(int P, int G, const gsr_density_group* groups /* HOST arra
                       const float* rotations /* [P][4] or NULL */, const float* noise /* [P][2][3] or NULL */,
                       int32_t* index /* [P_out] or NULL */, int64_t P_out, gsr_stream_t stream);
 
+/* Point-cloud neighbourhoods: exact k nearest neighbours, spacing, PCA normals and orientations (cloud_geometry.hip).  What a raw
+ * point cloud needs to become Gaussians: the mean nearest-neighbour distance that sets the scale (3DGS's distCUDA2 with k_s = 3), a
+ * normal per point, and the frame of an oriented disc.
+ *   gsr_knn.  points is float32 [P][3] on the device.  A point with a non-finite coordinate is absent: it is nobody's neighbour and
+ * its own row is all padding.  For present points i and j, in float32 with one rounding per written operation,
+ *     dx = x_i - x_j;  dy = y_i - y_j;  dz = z_i - z_j;      d2(i, j) = (dx dx + dy dy) + dz dz
+ * Row i of the result holds the K present points j != i with the smallest (d2, j) in lexicographic order -- ties go to the lower
+ * index --, ascending, in idx [P][K] (int32) and d2 [P][K] (float32, or NULL: not wanted).  Slots beyond the available neighbours hold
+ * idx = -1 and d2 = +inf; a neighbour whose d2 overflowed to +inf still precedes the padding.  Coincident points are each other's
+ * neighbours at d2 = 0.  The result is a function of the input alone: the search is exact, its traversal order cannot show, and two
+ * calls give the same bits.  K in 1..32, 1 <= P < 2^30.
+ *   How: the bounding box of the present points from a two-stage min/max reduction (it stays on the device), a 30-bit Morton key per
+ * point (absent points keyed last), the library's radix sort, a tight box around every run of 64 sorted points and around every 64
+ * such runs, and one wave per run that answers its 64 queries: it walks its own run, the runs of its own coarse box, then the other
+ * coarse boxes and the runs inside those that survive.  A box is skipped only when, for every lane, the float32 bound
+ *     g_a = max(lo_a - q_a, q_a - hi_a, 0)   per axis a;      bound = (g_x g_x + g_y g_y) + g_z g_z
+ * is strictly greater than the lane's current K-th distance: rounding is monotone, so the bound is <= d2 of every point inside the
+ * box, and on equality a lower index may still be inside.  Every box is walked at most once per run, whatever the cloud.
+ *   scratch: gsr_knn_scratch_bytes(P, K) bytes from the caller (a pure host function, a multiple of 256, monotone in P and K, 0 for a
+ * refused P or K); its contents on entry do not matter.  Nothing is read back from the device, no host wait is made, nothing is
+ * allocated.  There are no atomics.
+ *   Refused before any device call, in this order: P < 1 or P >= 2^30 or K outside 1..32 (GSR_ERR_INVALID); points, idx or scratch
+ * NULL (GSR_ERR_INVALID); scratch_bytes < gsr_knn_scratch_bytes(P, K) (GSR_ERR_CAPACITY, the message names the size needed).
+ *
+ *   gsr_cloud_geometry.  One lane per point, no scratch.  knn_idx is [P][K] as gsr_knn writes it; any int32 is allowed in it.  Entry j
+ * of row i is PRESENT when 0 <= j < P and point j has three finite coordinates; a point i that has a non-finite coordinate has no
+ * present entry.  Every other entry (-1, out of range) contributes nothing.  With delta_j = p_j - p_i (componentwise, float32):
+ *   spacing [P]: over the first n_s = min(k_s, present) present entries in list order, sum = sum + ((dx dx + dy dy) + dz dz) starting
+ * from 0;  spacing = sqrtf(sum / (float)n_s), and 0 when n_s = 0.  With k_s = 3 this is 3DGS's initial scale.
+ *   cov6 [P][6]: the neighbourhood is the point itself (delta = 0) and its first n_n = min(k_n, present) present entries, n = n_n + 1
+ * samples.  s = sum of delta_j in list order starting from 0;  m = s / (float)n;  with e_j = delta_j - m and e_self = 0 - m,
+ *     acc_ab = e_self_a e_self_b, then acc_ab = acc_ab + e_j_a e_j_b in list order;      C_ab = acc_ab / (float)n
+ * stored as (C_xx, C_xy, C_xz, C_yy, C_yz, C_zz).  n_n < 2 is a DEGENERATE ROW: cov6 = 0, eigenvalues = 0, normal (0, 0, 1), rotation
+ * (1, 0, 0, 0); its spacing is still the formula above.  No output of a degenerate row is NaN.
+ *   eigenvalues [P][3], ascending: cyclic Jacobi on A = C with V = I, GSR_CLOUD_JACOBI_SWEEPS sweeps over the pairs (p, q) = (0, 1),
+ * (0, 2), (1, 2), r the third index.  A pair with A_pq == 0 is left alone; otherwise
+ *     theta = (A_qq - A_pp) / (2 A_pq);   t = sgn / (|theta| + sqrtf(theta theta + 1)), sgn = 1 for theta >= 0 else -1
+ *     c = 1 / sqrtf(t t + 1);   s = t c;   h = t A_pq
+ *     A_pp = A_pp - h;   A_qq = A_qq + h;   A_pq = 0;   (A_rp, A_rq) = (c A_rp - s A_rq, s A_rp + c A_rq)
+ *     (V_kp, V_kq) = (c V_kp - s V_kq, s V_kp + c V_kq) for k = 0, 1, 2
+ * using only + - x / sqrtf: no closed-form trigonometric solver.  The diagonal and the columns of V are then ordered by three
+ * compare-exchanges on the positions (0, 1), (1, 2), (0, 1), each a swap when the left value is greater.
+ *   normals [P][3]: u = column 0 of the ordered V;  n = u / sqrtf((u_x u_x + u_y u_y) + u_z u_z).  Sign: with orient_to (HOST
+ * float[3], copied into the kernel's arguments) n is negated when (n_x (x_i - o_x) + n_y (y_i - o_y)) + n_z (z_i - o_z) < 0, so that
+ * n . (p - orient_to) >= 0; without it n is negated when its first non-zero component is negative.
+ *   rotations [P][4], a unit quaternion (r, x, y, z) with r >= 0 in the convention of the density-control section above: its rotation
+ * matrix has the columns (a, b, n) with a = column 2 of the ordered V normalised like n, and b = n x a = (n_y a_z - n_z a_y,
+ * n_z a_x - n_x a_z, n_x a_y - n_y a_x).  With R_i0 = a_i, R_i1 = b_i, R_i2 = n_i and tr = (R_00 + R_11) + R_22:
+ *     tr > 0:                      w = sqrtf(tr + 1) 2;            (r, x, y, z) = (w / 4, (R_21 - R_12) / w, (R_02 - R_20) / w, (R_10 - R_01) / w)
+ *     else R_00 > R_11, R_00 > R_22: w = sqrtf(((1 + R_00) - R_11) - R_22) 2;  ((R_21 - R_12) / w, w / 4, (R_01 + R_10) / w, (R_02 + R_20) / w)
+ *     else R_11 > R_22:            w = sqrtf(((1 + R_11) - R_00) - R_22) 2;  ((R_02 - R_20) / w, (R_01 + R_10) / w, w / 4, (R_12 + R_21) / w)
+ *     else                         w = sqrtf(((1 + R_22) - R_00) - R_11) 2;  ((R_10 - R_01) / w, (R_02 + R_20) / w, (R_12 + R_21) / w, w / 4)
+ * then every component is divided by sqrtf(((r r + x x) + y y) + z z), and all four are negated when r < 0.  The matching scales of an
+ * oriented Gaussian are sqrt of (lambda_2, lambda_1, lambda_0).
+ *   Every output pointer is optional (NULL: not wanted); an output's bits do not depend on which others are asked for.  Nothing is
+ * read back, no host wait is made, nothing is allocated, there are no atomics, and two calls give the same bits.
+ *   Refused before any device call, in this order, with GSR_ERR_INVALID: P < 1 or P >= 2^30, K outside 1..32, k_s or k_n outside
+ * 1..K; points or knn_idx NULL; every output NULL. */
+#define GSR_CLOUD_JACOBI_SWEEPS 5
+size_t gsr_knn_scratch_bytes(int P, int K);
+int gsr_knn(int P, const float* points /* [P][3] */, int K, int32_t* idx /* [P][K] */, float* d2 /* [P][K] or NULL */, void* scratch,
+            size_t scratch_bytes, gsr_stream_t stream);
+int gsr_cloud_geometry(int P, const float* points /* [P][3] */, int K, const int32_t* knn_idx /* [P][K] */, int k_s, int k_n,
+                       const float* orient_to /* HOST [3] or NULL */, float* spacing /* [P] or NULL */, float* cov6 /* [P][6] or NULL */,
+                       float* eigenvalues /* [P][3] or NULL */, float* normals /* [P][3] or NULL */, float* rotations /* [P][4] or NULL */,
+                       gsr_stream_t stream);
+
 /* Pairs in the lists of the calling thread's last forward call, per view (out[V], HOST array): what a binning arena has to
  * hold.  Equal to num_rendered with reference_lists = 1. */
 int gsr_last_list_pairs(int64_t* out, int V);
